@@ -18,6 +18,9 @@ The JSON line also carries: `roofline` (bytes the dominant kernel must touch / H
 HBM traffic from two rocprofv3 --pmc passes of a child of this script), `verify` (the timed result checked
 against the oracle and the counter identities), `cpu_baseline` / `cpu_baseline_1core` (the oracle on host cores,
 same sample) and `end_to_end` (FASTQ text in host memory / a file -> counts, PCIe inclusive; never `value`).
+
+`--dump-outputs DIR` writes what the last timed step computed (the read statistics, and the count vector or the
+Extract+Count key table) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import csv
@@ -56,6 +59,8 @@ HBM_PEAK_GBS = 8000.0
 HBM_STREAM_COPY_GBS = 6290.0        # what a streaming copy reaches on MI355X (MI355X_MICROARCH.md: ~6.3 TB/s achievable)
 SEED = 0xBEEF
 PMC_CHILD_STEPS = 4
+DUMP_LIMIT = 64 << 20               # bytes of all --dump-outputs arrays together
+DUMP_SAMPLE_SEED = 0xD0             # the fixed sample of an Extract+Count key table larger than that
 
 
 def parse_args(argv=None):
@@ -78,8 +83,13 @@ def parse_args(argv=None):
     ap.add_argument("--ms", type=int, default=1, help="--msu/--msd of the anchored workloads (experiments)")
     ap.add_argument("--read-len", type=int, default=150, help="override the read length (experiments)")
     ap.add_argument("--p-n", type=float, default=0.005, help="share of reads with an N in the window (experiments)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, <= 64 MB in all)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def resolve(a, world):
@@ -315,6 +325,37 @@ def end_to_end(pkg, c, fq, n_fq):
     return out
 
 
+def dump_outputs(d, c, w, counts, stats):
+    """--dump-outputs: the arrays the timed path hands its caller after the last step, as d/<name>.npy.  Every workload:
+    stats (reads, perfect, imperfect, non-aligned, quality-failed).  Counter mode: counts, one per feature in library
+    order.  Extract+Count: the key table in first-occurrence order -- ec_key (byte codes, zero-padded), ec_count,
+    ec_first_read and ec_row (row number in that order); above DUMP_LIMIT a fixed seeded sample of its rows.
+    Integers are stored as float64, which holds them exactly (< 2^53).  Returns {name: shape} and the key-table size."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {"stats": np.asarray(stats, dtype=np.float64)}
+    n_keys = None
+    if w.get("ec"):
+        rows = c.ec_results()
+        n_keys = len(rows)
+        width = max((len(k) for k, _, _ in rows), default=0)
+        room = (DUMP_LIMIT - (1 << 16) - arrays["stats"].nbytes) // (3 * 8 + 8 * width)    # (1 << 16: the .npy headers)
+        idx = np.arange(n_keys)
+        if n_keys > room:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_keys, room, replace=False))
+        keys = b"".join(rows[i][0].encode("latin-1").ljust(width, b"\0") for i in idx)
+        arrays["ec_key"] = np.frombuffer(keys, dtype=np.uint8).reshape(len(idx), width).astype(np.float64)
+        arrays["ec_count"] = np.array([rows[i][1] for i in idx], dtype=np.float64)
+        arrays["ec_first_read"] = np.array([rows[i][2] for i in idx], dtype=np.float64)
+        arrays["ec_row"] = idx.astype(np.float64)
+    else:
+        arrays["counts"] = np.asarray(counts, dtype=np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+    assert sum(os.path.getsize(os.path.join(d, name + ".npy")) for name in arrays) <= DUMP_LIMIT
+    return {name: list(v.shape) for name, v in arrays.items()}, n_keys
+
+
 def timed_steps(c, blk, steps, warmup, allreduce=None, barrier=None, sync=None):
     path = 0
     for _ in range(warmup):
@@ -454,6 +495,12 @@ def main(argv=None, engine=None):
         mx = chk.clone(); dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         assert bool((mx == chk).all()), "ranks disagree on the all-reduced result"
         verify["all_ranks_hold_the_same_result"] = True
+    dumped = None
+    if rank == 0 and a.dump_outputs:                # before the oracle legs below reuse the context
+        shapes, n_keys = dump_outputs(a.dump_outputs, c, w, counts, stats)
+        dumped = {"dir": a.dump_outputs, "dtype": "float64", "arrays": shapes}
+        if n_keys is not None:
+            dumped["ec_keys_total"] = n_keys
 
     if rank == 0:
         b_req = required_bytes_per_read(w, a.read_len)
@@ -483,6 +530,8 @@ def main(argv=None, engine=None):
                                   "leaves the rows outside the window untouched) and may therefore exceed the HBM peak")},
             "verify": verify,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if not a.no_cpu_baseline:                   # rank 0 of any world size (the other ranks wait at the closing barrier)
             base, one, prefix, fq = cpu_legs(pkg, c, w, a, guides, spec)
             out["cpu_baseline"], out["cpu_baseline_1core"] = base, one

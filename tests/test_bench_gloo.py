@@ -1,13 +1,15 @@
 """bench.py's N > 1 path on a machine without GPUs: two ranks over gloo, the counting engine replaced by the host
 emulation of the product's lane logic (tests/_bench_gloo_worker.py).  What is checked is bench.py: every rank takes its
 slice of the stream, each step ends with one all-reduce, rank 0 prints ONE JSON line whose whole-job numbers equal the
-oracle's single pass, and the line carries the N > 1 fields (scaling, collective, cpu_baseline on rank 0)."""
+oracle's single pass, the line carries the N > 1 fields (scaling, collective, cpu_baseline on rank 0), and
+--dump-outputs writes the same whole-job result."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import synth
@@ -27,7 +29,7 @@ def free_port():
 def test_bench_two_ranks_gloo(tmp_path, scaling):
     port = free_port()
     args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--workload", "cfg3_50M_10k_m1", "--reads", "20000",
-            "--guides", "300", "--no-pmc", "--no-extras", "--scaling", scaling]
+            "--guides", "300", "--no-pmc", "--no-extras", "--scaling", scaling, "--dump-outputs", str(tmp_path / "out")]
     procs = []
     for r in range(2):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), PYTHONPATH=ROOT)
@@ -51,5 +53,10 @@ def test_bench_two_ranks_gloo(tmp_path, scaling):
     orc = O.Oracle(features=[(str(i), g) for i, g in enumerate(guides)], miss=1, phred=30, length=20, start="0")
     orc.count_fastq(fq)
     assert v["stats"] == orc.stats()
+    # --dump-outputs: rank 0 wrote the last step's all-reduced result, float64, one count per guide
+    assert d["dump_outputs"]["arrays"] == {"stats": [5], "counts": [300]}
+    dumped = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in ("stats", "counts")}
+    assert all(a.dtype == np.float64 for a in dumped.values())
+    assert dumped["stats"].tolist() == orc.stats() and dumped["counts"].tolist() == orc.counts()
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0 and v["prefix_vs_oracle"]["equals_oracle"]
     assert abs(d["value"] - total * 2 / (d["ms_per_step"] * 2e-3) / 1e6) < 1e-6 * d["value"] + 1e-9
