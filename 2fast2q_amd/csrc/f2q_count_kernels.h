@@ -507,7 +507,9 @@ __global__ __launch_bounds__(F2Q_V2_THREADS, 4) void k_count_multi4(const RunDev
 // Fixed-offset Counter mode for uniform libraries of 14..21-base features searched with --m <= 1 (the reference's
 // default, and BASELINE configs 2 and 3): the tile walk of k_count_fixed4, but every lookup -- exact hit and the
 // unique-feature-at-distance-1 search -- is answered from two cuckoo tables of 32-bit tags held in the workgroup's LDS
-// (f2q_device.h, "LDS tables"): four 8-byte LDS reads per read, no table traffic to L2 at all, no ring, no second pass.
+// (f2q_device.h, "LDS tables"), no table traffic to L2 at all, no ring, no second pass.  Two stages per tile: every read
+// probes table 0 for its exact hit (two 8-byte LDS reads); the reads that still need the distance-1 search are gathered
+// into consecutive lanes with a lane permute and decided 64 at a time by the full routine (four 8-byte LDS reads).
 // One 1024-thread workgroup per CU owns the whole 160 KiB: 2 x 64 KiB of tags + a 32 KiB histogram of u16 counters
 // (two per word, indexed by table-0 slot).  A counter that reaches 0x8000 moves 0x8000 counts to the global vector
 // (lt_count), so no count is lost however skewed the library's popularity is.  The rows of the wave's next tile are
@@ -522,16 +524,22 @@ __device__ __forceinline__ U2 lds_u2(const uint32_t *p)
     return U2{v.x, v.y};
 }
 
+__device__ __forceinline__ uint32_t lt_count_add(uint32_t *cnt, uint32_t slot)      // the word's old value
+{
+    return atomicAdd(&cnt[slot >> 1], 1u << ((slot & 1u) << 4));
+}
+__device__ __forceinline__ bool lt_count_passed(uint32_t old, uint32_t slot) { return ((old >> ((slot & 1u) << 4)) & 0xFFFFu) == 0x7FFFu; }
+// exactly one adder sees the counter pass 0x7FFF -> 0x8000; it takes 0x8000 out again (no borrow: the counter only
+// grows until then, and by far less than another 0x8000 -- also when the adder tests its old value some LDS operations
+// later) and credits the feature's global counter
+__device__ __forceinline__ void lt_count_handoff(uint32_t *cnt, uint32_t slot, const Accum &acc, const LtDesc &lt)
+{
+    atomicSub(&cnt[slot >> 1], 0x8000u << ((slot & 1u) << 4));
+    acc_add(&acc.counts[gp(lt.feat_of)[slot]], 0x8000ull);
+}
 __device__ __forceinline__ void lt_count(uint32_t *cnt, uint32_t slot, const Accum &acc, const LtDesc &lt)
 {
-    const uint32_t sh = (slot & 1u) << 4;
-    const uint32_t old = atomicAdd(&cnt[slot >> 1], 1u << sh);
-    // exactly one adder sees the counter pass 0x7FFF -> 0x8000; it takes 0x8000 out again (no borrow: the counter only
-    // grows until then, and by far less than another 0x8000) and credits the feature's global counter
-    if (((old >> sh) & 0xFFFFu) == 0x7FFFu) {
-        atomicSub(&cnt[slot >> 1], 0x8000u << sh);
-        acc_add(&acc.counts[gp(lt.feat_of)[slot]], 0x8000ull);
-    }
+    if (lt_count_passed(lt_count_add(cnt, slot), slot)) lt_count_handoff(cnt, slot, acc, lt);
 }
 
 // A20: the window is 20 bases starting at a multiple of 16 (--l 20 with --st 0, 16, ...: the usual guide-counting run):
@@ -554,15 +562,8 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
     LtDesc lt = lib.lt;
     if (A20) { lt.hb0 = 20u; lt.hb1 = 20u; lt.len = 20u; }      // constants for the compiler
     const uint32_t nf = lib.n_features;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    {
-        typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-        const v4 F2Q_GLOBAL *src = (const v4 F2Q_GLOBAL *)gp(lt.tags);
-        v4 *dst = reinterpret_cast<v4 *>(tg);
-        for (uint32_t i = tid; i < NT * F2Q_LT_SLOTS / 4u; i += F2Q_LT_THREADS) dst[i] = src[i];
-        for (uint32_t i = tid; i < F2Q_LT_BUCKETS; i += F2Q_LT_THREADS) cnt[i] = 0;
-    }
-    __syncthreads();
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));    // wave-uniform for the compiler
     FixedGeom g = MW ? fixed_geom_at(0, run.n_iter * run.length, run.thr) : fixed_geom(run);
     if (A20) { g.L = 20; g.nq = 5; g.nb = 2; g.sh = 0; g.qm_first = 0x80808080u; g.qm_last = 0x80808080u; g.kmask = (1ull << 40) - 1ull; }
     const int need = g.st + g.L;
@@ -589,6 +590,22 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
         typedef uint32_t v2 __attribute__((ext_vector_type(2)));
         const v2 lv = __builtin_nontemporal_load((const v2 F2Q_GLOBAL *)(l_base + (uint64_t)t * F2Q_TILE));
         r.len01 = lv.x; r.len23 = lv.y;
+    };
+    // Histogram adds leave the chain: a stage's returning adds are tested by the next stage, after the LDS wait that
+    // stage has anyway (a wave's LDS operations complete in order), instead of right away.  n_pend (wave-uniform): adds
+    // of the last stage in pend_old / pend_slot (a lane without an add holds 0, which tests as not passing).
+    uint32_t pend_old[4] = {0, 0, 0, 0}, pend_slot[4] = {0, 0, 0, 0}, n_pend = 0;
+    auto settle = [&]() {
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if ((uint32_t)k < n_pend) any |= lt_count_passed(pend_old[k], pend_slot[k]);
+        if (any) {                                              // rare: a counter of the lane passed 0x8000
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if ((uint32_t)k < n_pend && lt_count_passed(pend_old[k], pend_slot[k])) lt_count_handoff(cnt, pend_slot[k], acc, lt);
+        }
+        n_pend = 0;
     };
     auto decide_tile = [&](const Rows &r) {
         uint32_t bad[4] = {0, 0, 0, 0};
@@ -618,50 +635,97 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
                     if (NQ || i < g.nq) fixed4_qrow(g, i, r.q[i], bad);
             }
         }
-        // two reads at a time: both reads' eight bucket reads are in flight together, and nothing below branches except the
-        // rare cases (flagged symbols, features sharing a half, a hit found through table 1, a counter passing 0x8000)
+        // exact stage: table 0 only, the eight bucket reads of the lane's four reads in flight together
+        LtProbe0 p[4]; U2 e0[4], e1[4]; uint32_t klo[4], khi[4], forced[4]; bool cand[4];
 #pragma unroll
-        for (int jp = 0; jp < 4; jp += 2) {
-            LtProbe q[2]; U2 e[2][4]; uint32_t forced[2]; bool cand[2];
+        for (int j = 0; j < 4; j++) {
+            const uint32_t l = ((j < 2 ? r.len01 : r.len23) >> (16 * (j & 1))) & 0xFFFFu;
+            const bool live = l != F2Q_LEN_SKIP, qf = live && bad[j] != 0u;
+            // a read that ends inside the window gives a shorter key (:354); every feature is L long, so it can equal
+            // or approach none (:683); its bytes past the end are stored as 0 and never fail the Phred test
+            cand[j] = live && !qf && (int)(l & F2Q_LEN_MASK) >= need && !(MW && part_fail[j]);
+            w_reads += (uint32_t)__popcll(__ballot(live));
+            w_qfail += (uint32_t)__popcll(__ballot(qf));
+            forced[j] = 0;
+            if ((l & F2Q_LEN_FLAG) && cand[j]) forced[j] = fixed4_flags(g, r.q, j);   // non-ACGT symbols in the window (rare)
+            uint64_t key = fixed4_key(g, r.b, j);
+            if (MW && lt.mix) { key = mw_mix(key, lt.mix); if (forced[j]) forced[j] = mw_mix_mask(forced[j], lt.mix); }
+            p[j] = lt_probe0(lt, key);
+            e0[j] = lds_u2(tg + 2u * p[j].b0);
+            e1[j] = lds_u2(tg + 2u * p[j].b1);
+            klo[j] = (uint32_t)key; khi[j] = lt_rec_hi(key, forced[j]);
+        }
+        LtExact x[4];
 #pragma unroll
-            for (int a = 0; a < 2; a++) {
-                const int j = jp + a;
-                const uint32_t l = ((j < 2 ? r.len01 : r.len23) >> (16 * (j & 1))) & 0xFFFFu;
-                const bool live = l != F2Q_LEN_SKIP, qf = live && bad[j] != 0u;
-                // a read that ends inside the window gives a shorter key (:354); every feature is L long, so it can equal
-                // or approach none (:683); its bytes past the end are stored as 0 and never fail the Phred test
-                cand[a] = live && !qf && (int)(l & F2Q_LEN_MASK) >= need && !(MW && part_fail[j]);
-                w_reads += (uint32_t)__popcll(__ballot(live));
-                w_qfail += (uint32_t)__popcll(__ballot(qf));
-                forced[a] = 0;
-                if ((l & F2Q_LEN_FLAG) && cand[a]) forced[a] = fixed4_flags(g, r.q, j);   // non-ACGT symbols in the window (rare)
-                uint64_t key = fixed4_key(g, r.b, j);
-                if (MW && lt.mix) { key = mw_mix(key, lt.mix); if (forced[a]) forced[a] = mw_mix_mask(forced[a], lt.mix); }
-                q[a] = lt_probe(lt, key);
+        for (int j = 0; j < 4; j++) x[j] = lt_exact_stage(p[j], e0[j], e1[j], cand[j], forced[j]);
+        settle();                                               // the previous stage's histogram adds have returned by now
 #pragma unroll
-                for (int k = 0; k < (NEAR ? 4 : 2); k++) e[a][k] = lds_u2(tg + (uint32_t)(k >> 1) * F2Q_LT_SLOTS + 2u * q[a].b[k]);
-                if (!NEAR) { e[a][2] = U2{F2Q_LT_EMPTY, F2Q_LT_EMPTY}; e[a][3] = e[a][2]; }
+        for (int j = 0; j < 4; j++) {
+            pend_old[j] = 0;
+            if (x[j].hit) pend_old[j] = lt_count_add(cnt, x[j].slot);
+            pend_slot[j] = x[j].slot;
+            w_perfect += (uint32_t)__popcll(__ballot(x[j].hit));
+        }
+        n_pend = 4;
+        if (!NEAR) return;                                      // --m 0: a read without an exact hit matches nothing
+        // batch stage: the wave's candidates numbered slot by slot, moved to consecutive lanes with a forward permute
+        // (no LDS memory), and decided 64 at a time by the whole --m 1 routine
+        uint32_t pre[5], pos[4];
+        pre[0] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const unsigned long long m = __ballot(x[j].batch);
+            pos[j] = pre[j] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            pre[j + 1] = pre[j] + (uint32_t)__popcll(m);
+        }
+        for (uint32_t lo = 0; lo < pre[4]; lo += 64u) {
+            const uint32_t at = lo + lane;
+            uint32_t rlo = 0, rhi = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (!lt_batch_has(pre, j, lo)) continue;
+                const bool send = x[j].batch && pos[j] - lo < 64u;
+                const int to = (int)(4u * (send ? pos[j] - lo : lt_dump(pre, j, lo)));
+                const uint32_t a = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)klo[j]);
+                const uint32_t b = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)khi[j]);
+                const bool mine = at >= pre[j] && at < pre[j + 1];
+                rlo = mine ? a : rlo; rhi = mine ? b : rhi;
             }
+            const bool valid = at < pre[4];
+            const LtProbe q = lt_probe(lt, lt_rec_key(rlo, rhi));
+            U2 e[4];
 #pragma unroll
-            for (int a = 0; a < 2; a++) {
-                const LtVerdict v = lt_decide<NEAR>(lt, q[a], e[a], forced[a], [&](uint32_t bk) { return lds_u2(tg + 2u * bk); });
-                const LtPred cm = LT_P(cand[a]), perfect = v.perfect & cm, imperfect = v.imperfect & cm;
-                if (LT_TRUE(perfect | imperfect)) lt_count(cnt, v.slot, acc, lt);
-                w_perfect += (uint32_t)__popcll(perfect);
-                w_imperfect += (uint32_t)__popcll(imperfect);
-            }
+            for (int k = 0; k < 4; k++) e[k] = lds_u2(tg + (uint32_t)(k >> 1) * F2Q_LT_SLOTS + 2u * q.b[k]);
+            const LtVerdict v = lt_decide<NEAR>(lt, q, e, lt_rec_forced(rhi), [&](uint32_t bk) { return lds_u2(tg + 2u * bk); });
+            settle();
+            const LtPred cm = LT_P(valid), perfect = v.perfect & cm, imperfect = v.imperfect & cm;
+            pend_old[0] = 0;
+            if (LT_TRUE(perfect | imperfect)) pend_old[0] = lt_count_add(cnt, v.slot);
+            pend_slot[0] = v.slot;
+            n_pend = 1;
+            w_perfect += (uint32_t)__popcll(perfect);
+            w_imperfect += (uint32_t)__popcll(imperfect);
         }
     };
 
     const uint32_t stride = gridDim.x * F2Q_LT_WAVES;
     uint32_t tile = blockIdx.x * F2Q_LT_WAVES + wave;
     const uint32_t last = pb.n_tiles - 1u;
+    // two register sets of rows, used alternately: the next tile's rows travel while this tile is decided (past the
+    // end the last tile is requested again and dropped: an unconditional request keeps the wait counts exact).  The
+    // first tile's rows are requested before the tables are copied in, so that HBM serves both at once.
+    Rows ra, rb;
+    if (PIPE && tile < pb.n_tiles) request_tile(ra, tile);
+    {
+        typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+        const v4 F2Q_GLOBAL *src = (const v4 F2Q_GLOBAL *)gp(lt.tags);
+        v4 *dst = reinterpret_cast<v4 *>(tg);
+        for (uint32_t i = tid; i < NT * F2Q_LT_SLOTS / 4u; i += F2Q_LT_THREADS) dst[i] = src[i];
+        for (uint32_t i = tid; i < F2Q_LT_BUCKETS; i += F2Q_LT_THREADS) cnt[i] = 0;
+    }
+    __syncthreads();
     if (PIPE) {
-        // two register sets of rows, used alternately: the next tile's rows travel while this tile is decided (past the
-        // end the last tile is requested again and dropped: an unconditional request keeps the wait counts exact)
-        Rows ra, rb;
         if (tile < pb.n_tiles) {
-            request_tile(ra, tile);
             for (;;) {
                 __builtin_amdgcn_sched_barrier(0);
                 request_tile(rb, min(tile + stride, last));
@@ -680,6 +744,7 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
     } else {
         for (; tile < pb.n_tiles; tile += stride) { Rows r; request_tile(r, tile); decide_tile(r); }
     }
+    settle();
     __syncthreads();
     // the histogram leaves as one slab row in feature order; k_reduce_slabs sums the rows
     {

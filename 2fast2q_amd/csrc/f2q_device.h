@@ -1581,6 +1581,49 @@ F2Q_HD LtVerdict lt_decide(const LtDesc &lt, const LtProbe &q, const U2 (&e)[4],
     return v;
 }
 
+// k_count_fixed4_lds decides a read in two stages.  The EXACT stage probes only table 0 (lt_probe0: two hashes, two
+// buckets): a key equal to a stored tag is the unique distance-0 feature whatever else shares its halves, so lt_decide
+// would call it perfect with that slot (lt_exact).  The reads lt_decide could still count otherwise -- aligned, passing
+// the Phred test, and flagged or without an exact hit -- go to the BATCH stage, which runs lt_probe + lt_decide on them
+// unchanged, 64 at a time in the lanes of a wave.
+struct LtProbe0 { uint32_t b0, b1, w0, w1; };          // table-0 buckets of a key and the tag it would have in each
+F2Q_HD LtProbe0 lt_probe0(const LtDesc &lt, uint64_t key)
+{
+    const uint32_t h0 = (uint32_t)key & ((1u << lt.hb0) - 1u), h1 = (uint32_t)(key >> lt.hb0);
+    LtProbe0 p;
+    uint32_t c0, c1;
+    lt_hash(h0, lt.hb0, lt.hb1, 0, p.b0, c0);
+    lt_hash(h0, lt.hb0, lt.hb1, 1, p.b1, c1);
+    p.w0 = lt_tag(c0, h1, lt.hb1); p.w1 = lt_tag(c1, h1, lt.hb1);
+    return p;
+}
+// cand: the read is live, passes its Phred test (every part of it, MW) and covers the window
+struct LtExact { bool hit, batch; uint32_t slot; };
+F2Q_HD LtExact lt_exact_stage(const LtProbe0 &p, const U2 &e0, const U2 &e1, bool cand, uint32_t forced)
+{
+    const bool a0 = e0.x == p.w0, a1 = e0.y == p.w0, b0 = e1.x == p.w1, b1 = e1.y == p.w1;
+    LtExact r;
+    r.hit = cand && forced == 0u && (a0 | a1 | b0 | b1);      // a flagged base equals no feature's base
+    r.batch = cand && !r.hit;
+    r.slot = (a0 | a1) ? 2u * p.b0 + (uint32_t)a1 : 2u * p.b1 + (uint32_t)b1;
+    return r;
+}
+// a batch record: two dwords, the key (2L <= 42 bits) and the flagged-base mask (L <= 21 bits)
+F2Q_HD uint32_t lt_rec_hi(uint64_t key, uint32_t forced) { return (uint32_t)(key >> 32) | (forced << 10); }
+F2Q_HD uint64_t lt_rec_key(uint32_t lo, uint32_t hi) { return ((uint64_t)(hi & 0x3FFu) << 32) | lo; }
+F2Q_HD uint32_t lt_rec_forced(uint32_t hi) { return hi >> 10; }
+// Compaction of a tile's batch candidates: the candidates of read slot j of the wave (j = 0..3) take positions
+// pre[j] .. pre[j+1]-1 in lane order, position i goes to lane i % 64 of batch i / 64.  In the batch starting at position
+// lo, read slot j sends to the lanes [s, e) below; a lane of the wave that sends nothing must still write somewhere (a
+// permute moves data of every active lane), and lt_dump is a lane outside [s, e) -- there is one unless all 64 lanes
+// send.  A receiving lane takes the value of the one slot whose range holds its position.
+F2Q_HD uint32_t lt_dump(const uint32_t (&pre)[5], int j, uint32_t lo)
+{
+    const uint32_t s = (pre[j] > lo ? pre[j] : lo) - lo, e = pre[j + 1] - lo < 64u ? pre[j + 1] - lo : 64u;
+    return e < 64u ? e : (s ? s - 1u : 0u);
+}
+F2Q_HD bool lt_batch_has(const uint32_t (&pre)[5], int j, uint32_t lo) { return pre[j] < lo + 64u && pre[j + 1] > lo; }
+
 // ---------------------------------------------------------------------------------------------
 // fast path, anchored (--us / --ds): one lane = one read held as two bit-planes.
 // Planar tile layout (anchored runs): base rows 0..NW-1 hold the LOW bit of 32 bases per word,
