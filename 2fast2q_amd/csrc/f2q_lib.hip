@@ -68,7 +68,7 @@ struct f2q_ctx {
     uint64_t acc_n = 0;
     uint32_t *slab_d = nullptr;          // per-workgroup histogram rows of the v2 kernel
     size_t slab_n = 0;
-    unsigned long long *stat_slab_d = nullptr;
+    unsigned long long *stat_slab_d = nullptr;   // per-workgroup stats rows of 8
     size_t stat_slab_n = 0;
     uint32_t *hit_buf_d = nullptr;       // large libraries: feature index per read slot of the block being counted
     size_t hit_buf_n = 0;
@@ -583,9 +583,10 @@ static int ec_reserve(f2q_ctx *c, uint64_t keys64, uint64_t reads, uint64_t key_
     return F2Q_OK;
 }
 
-// ---- the partitioned path (f2q_part_kernels.h) -------------------------------------------------------------------
+// ---- launching ----------------------------------------------------------------------------------
+// a device buffer of at least `want` elements; it only grows (the old contents are not kept)
 template <class T>
-static int pt_grow(f2q_ctx *c, T **buf, size_t &have, size_t want, bool zero)
+static int grow_buf(f2q_ctx *c, T **buf, size_t &have, size_t want, bool zero)
 {
     if (want <= have) return F2Q_OK;
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -596,6 +597,169 @@ static int pt_grow(f2q_ctx *c, T **buf, size_t &have, size_t want, bool zero)
     have = want;
     return F2Q_OK;
 }
+// the per-workgroup rows of a launch that reduces through k_reduce_slabs: `rows` histogram rows of n_features counts and
+// `stat_rows` rows of 8 stats; acc points at them
+static int slab_rows(f2q_ctx *c, size_t rows, size_t stat_rows, Accum &acc)
+{
+    int rc;
+    if ((rc = grow_buf(c, &c->slab_d, c->slab_n, std::max<size_t>(rows * c->lib_h.n_features, 1), false))) return rc;
+    if ((rc = grow_buf(c, &c->stat_slab_d, c->stat_slab_n, stat_rows * 8, false))) return rc;
+    acc.slab = c->slab_d; acc.stat_slab = c->stat_slab_d;
+    return F2Q_OK;
+}
+// k_reduce_slabs: the launch's `rows` histogram rows and `stat_rows` stats rows into the accumulators
+static int reduce_slabs(f2q_ctx *c, const Accum &acc, uint32_t rows, uint32_t stat_rows, uint32_t &launches)
+{
+    const uint32_t nf = c->lib_h.n_features;
+    hipLaunchKernelGGL(k_reduce_slabs, dim3(std::max<uint32_t>(1u, (nf + 63) / 64), F2Q_RED_SPLIT), dim3(256), 0, c->stream,
+                       c->slab_d, rows, nf, acc.counts, c->stat_slab_d, stat_rows, acc.stats);
+    HIPC(c, hipGetLastError());
+    launches++;
+    return F2Q_OK;
+}
+static bool same_q(const RunDev &r) { return r.thr_up == r.thr && r.thr_down == r.thr; }
+
+// calls f(NW, KB, SQ) with the std::integral_constant arguments of an anchored geometry: nw 3 or 5, kb 0, 1 or 3,
+// SQ = sameq.  WIDE: nw 10 (reads of 161 .. 320 bases) has one general instantiation, <10, 3, false> (any --msu/--msd
+// <= 7, any --qsu/--qsd); only k_count_anchor and k_count_anchor_pairs have it.
+template <int N> using int_c = std::integral_constant<int, N>;
+template <bool WIDE = false, class F>
+static void anchored_geom(int nw, int kb, bool sameq, F &&f)
+{
+    if constexpr (WIDE) {
+        if (nw == 10) return f(int_c<10>(), int_c<3>(), std::false_type());
+    }
+    auto by_kb = [&](auto NW) {
+        auto by_sq = [&](auto KB) { if (sameq) f(NW, KB, std::true_type()); else f(NW, KB, std::false_type()); };
+        if (kb == 0) by_sq(int_c<0>()); else if (kb == 1) by_sq(int_c<1>()); else by_sq(int_c<3>());
+    };
+    if (nw == 3) by_kb(int_c<3>()); else by_kb(int_c<5>());
+}
+
+// the specialisation of the fixed-window kernels for a window: spec52 (5 quality rows, 2 base rows), a20 (spec52 with
+// a 20-base window at a 16-aligned start) or the run-time geometry
+enum FixedVariant { FV_GENERIC, FV_SPEC52, FV_A20 };
+static FixedVariant fixed_variant(const f2q_ctx *c, const FixedGeom &g)
+{
+    if (c->force_generic || g.nq != 5 || g.nb != 2 || c->run_h.thr < 33) return FV_GENERIC;
+    return g.L == 20 && (g.st & 15) == 0 ? FV_A20 : FV_SPEC52;
+}
+
+// the kernel family that counts a view's packed tiles (F2Q_PATH_*; pb.n_tiles > 0)
+static uint32_t choose_path(const f2q_ctx *c, const PackedBlock &pb)
+{
+    const bool ecm = c->prm.mode == 1;
+    // the library in LDS: uniform 14..21-base library, --m <= 1
+    const bool lt = c->lib_h.n_features <= F2Q_HIST_MAX && !c->no_lt && c->lib_h.lt.ok && c->run_h.miss <= 1 && pb.len != nullptr;
+    if (pb.planar_nw) {
+        if (c->plan.multi_pair) return F2Q_PATH_PAIRS;           // several --us/--ds pairs on the planes
+        if (ecm) return F2Q_PATH_EXTRACT;
+        return lt && same_q(c->run_h) && pb.planar_nw != 10 ? F2Q_PATH_ANCHOR_LDS : F2Q_PATH_ANCHOR;
+    }
+    if (ecm) return F2Q_PATH_EXTRACT;
+    if (c->plan.multi) {
+        // several windows per read, every feature with one part per window: the joined keys on the library-in-LDS
+        // kernel (the tiles hold the windows back to back: one window of n_iter * length bases)
+        const uint32_t mw_total = (uint32_t)(c->run_h.n_iter * c->run_h.length);
+        const bool mw_lt = lt && c->lib_h.lt.len == mw_total && (mw_total + 3) / 4 <= pb.wq && (mw_total + 15) / 16 <= pb.wb;
+        return mw_lt ? F2Q_PATH_MULTI_LDS : F2Q_PATH_MULTI;
+    }
+    const uint32_t len = (uint32_t)c->run_h.length;
+    const bool v2 = !c->force_v1 && c->lib_h.pk.len == len && len > 0 && c->lib_h.n_irregular == 0;
+    const FixedGeom g = fixed_geom(c->run_h);
+    // the tiles hold every row under the window
+    const bool rows = v2 && c->run_h.miss <= 1 && (uint32_t)(g.qw0 + g.nq) <= pb.wq && (uint32_t)(g.bw0 + g.nb) <= pb.wb && pb.len != nullptr;
+    const bool use_lt = rows && lt && c->lib_h.lt.len == len;
+    // a library beyond one workgroup's LDS, dealt into partitions (or F2Q_PT_PARTS set: that path whatever the size)
+    if (rows && !c->no_pt && c->lib_h.pt.ok && c->lib_h.pt.len == len &&
+        (c->ix.pt_force_parts > 0 || (!use_lt && (uint64_t)pb.n_tiles * F2Q_TILE >= c->pt_min_reads)))
+        return F2Q_PATH_FIXED_PART;
+    if (use_lt) return F2Q_PATH_FIXED_LDS;
+    return v2 ? F2Q_PATH_FIXED_PACKED : F2Q_PATH_FIXED_V1;
+}
+
+// several --us/--ds pairs on the planes
+static int launch_pairs(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
+{
+    const bool lds = c->prm.mode == 0 && c->lib_h.n_features <= F2Q_HIST_MAX;
+    const uint32_t grid = std::min<uint32_t>(pb.n_tiles, (uint32_t)c->n_cu * 8u);          // (four workgroups of 256 threads are resident per CU at 128 VGPRs: two rounds)
+    const size_t shmem = lds ? std::max<size_t>(4, (((size_t)c->lib_h.n_features + 1) / 2) * 4) : 4;
+    anchored_geom<true>(pb.planar_nw, c->plan.kb, same_q(c->run_h), [&](auto NW, auto KB, auto SQ) {
+        auto kern = lds ? k_count_anchor_pairs<NW, KB, SQ, true> : k_count_anchor_pairs<NW, KB, SQ, false>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_AN_THREADS), shmem, c->stream, c->run_d, c->lib_d, c->ec, pb, acc, c->reads_seen);
+    });
+    HIPC(c, hipGetLastError());
+    launches++;
+    return F2Q_OK;
+}
+
+// packed anchored path: Counter mode (per-workgroup histogram in LDS up to F2Q_HIST_MAX features) or Extract+Count
+static int launch_anchor(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
+{
+    const bool ecm = c->prm.mode == 1;
+    const uint32_t nf = c->lib_h.n_features;
+    const bool lds = !ecm && nf <= F2Q_HIST_MAX;
+    const uint32_t grid = std::min<uint32_t>(pb.n_tiles, (uint32_t)c->n_cu * 4u);
+    const size_t shmem = (size_t)F2Q_AN_WAVES * F2Q_AN_QCAP * 12 + (lds ? (size_t)nf * 4 : 0);
+    int rc;
+    if (lds && (rc = slab_rows(c, grid, grid, acc))) return rc;
+    anchored_geom<true>(pb.planar_nw, c->plan.kb, same_q(c->run_h), [&](auto NW, auto KB, auto SQ) {
+        auto kern = ecm ? k_count_anchor<NW, KB, true, false, SQ> : lds ? k_count_anchor<NW, KB, false, true, SQ> : k_count_anchor<NW, KB, false, false, SQ>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_AN_THREADS), shmem, c->stream, c->run_d, c->lib_d, c->ec, pb, acc, c->reads_seen);
+    });
+    HIPC(c, hipGetLastError());
+    launches++;
+    return lds && nf ? reduce_slabs(c, acc, grid, grid, launches) : F2Q_OK;
+}
+
+// anchored tiles with the library in LDS (Counter mode, default --qsu/--qsd)
+static int launch_anchor_lds(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
+{
+    const uint32_t groups = (pb.n_tiles + F2Q_ALT_GROUPS - 1) / F2Q_ALT_GROUPS;
+    const uint32_t grid = std::min<uint32_t>(groups, (uint32_t)c->n_cu);
+    const bool near = c->run_h.miss > 0;
+    const size_t shmem = ((near ? 2u : 1u) * (size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4;
+    int rc = slab_rows(c, grid, grid, acc);
+    if (rc) return rc;
+    // (this path is taken with sameq only: the kernel has no SAMEQ = false instance)
+    anchored_geom(pb.planar_nw, c->plan.kb, true, [&](auto NW, auto KB, auto) {
+        auto kern = near ? k_count_anchor_lt<NW, KB, true, true> : k_count_anchor_lt<NW, KB, true, false>;
+        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_ALT_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
+    });
+    HIPC(c, hipGetLastError());
+    launches++;
+    return reduce_slabs(c, acc, grid, grid, launches);
+}
+
+// Extract+Count on fixed-window tiles, one step of the block (where the hot-key kernels are not taken: ec_hot_path)
+static int launch_extract_fixed(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
+{
+    const uint32_t wgs = (pb.n_tiles + F2Q_V2_WAVES - 1) / F2Q_V2_WAVES;
+    const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 4u);
+    hipLaunchKernelGGL(k_extract_fixed4, dim3(grid), dim3(F2Q_V2_THREADS), 0, c->stream, c->run_d, c->ec, pb, acc, c->reads_seen);
+    HIPC(c, hipGetLastError());
+    launches++;
+    return F2Q_OK;
+}
+
+// several windows per read (--st a,b,...): k-part keys against the k-part features
+static int launch_multi(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
+{
+    const uint32_t nf = c->lib_h.n_features;
+    const bool lds = nf <= F2Q_HIST_MAX;
+    const uint32_t wgs = (pb.n_tiles + F2Q_V2_WAVES - 1) / F2Q_V2_WAVES;
+    const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 2u);
+    const size_t shmem = (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 12 + (lds ? (size_t)nf * 4 : 0);
+    int rc = slab_rows(c, lds ? grid : 0u, grid, acc);
+    if (rc) return rc;
+    auto kern = lds ? k_count_multi4<true> : k_count_multi4<false>;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_V2_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc, c->plan.need);
+    HIPC(c, hipGetLastError());
+    launches++;
+    return reduce_slabs(c, acc, lds ? grid : 0u, grid, launches);
+}
+
 // fixed-offset Counter mode on a partitioned library: the block's tiles in chunks, each scattered and then counted
 static int launch_part(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
 {
@@ -617,18 +781,16 @@ static int launch_part(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &
     if ((grid1 + K - 1) / K > 64) return fail(c, F2Q_EUNSUPPORTED, "partitioned path: more than 64 streams per counting workgroup");
     const uint32_t n_slots1 = 2u << pt.bb1, rows = grid1 + grid2;
     int rc;
-    if ((rc = pt_grow(c, &c->pt_s.streams, c->pt_streams_n, (size_t)grid1 * P * cap, false))) return rc;
-    if ((rc = pt_grow(c, &c->pt_s.cnt, c->pt_cnt_n, (size_t)grid1 * P, false))) return rc;
-    if ((rc = pt_grow(c, &c->pt_slab0_d, c->pt_slab0_n, (size_t)grid2 * std::max<uint32_t>(pt.max_part, 1u), true))) return rc;
-    if ((rc = pt_grow(c, &c->pt_slab1_d, c->pt_slab1_n, (size_t)n_slots1, true))) return rc;
-    if ((rc = pt_grow(c, &c->pt_stat_d, c->pt_stat_n, (size_t)rows * 8, true))) return rc;     // rows accumulate; k_part_reduce clears them
+    if ((rc = grow_buf(c, &c->pt_s.streams, c->pt_streams_n, (size_t)grid1 * P * cap, false))) return rc;
+    if ((rc = grow_buf(c, &c->pt_s.cnt, c->pt_cnt_n, (size_t)grid1 * P, false))) return rc;
+    if ((rc = grow_buf(c, &c->pt_slab0_d, c->pt_slab0_n, (size_t)grid2 * std::max<uint32_t>(pt.max_part, 1u), true))) return rc;
+    if ((rc = grow_buf(c, &c->pt_slab1_d, c->pt_slab1_n, (size_t)n_slots1, true))) return rc;
+    if ((rc = grow_buf(c, &c->pt_stat_d, c->pt_stat_n, (size_t)rows * 8, true))) return rc;     // rows accumulate; k_part_reduce clears them
     PartScratch ps = c->pt_s;
     ps.cap = cap; ps.n_wg1 = grid1;
     Accum a1 = acc, a2 = acc;
     a1.stat_slab = c->pt_stat_d; a2.stat_slab = a1.stat_slab + (size_t)grid1 * 8;
-    const FixedGeom fg = fixed_geom(c->run_h);
-    const bool spec52 = !c->force_generic && fg.nq == 5 && fg.nb == 2 && c->run_h.thr >= 33;
-    const bool a20 = spec52 && fg.L == 20 && (fg.st & 15) == 0;
+    const FixedVariant fv = fixed_variant(c, fixed_geom(c->run_h));
     const bool near = c->run_h.miss > 0;
     const size_t shmem1 = (size_t)pw * P * F2Q_PS_RING * 8 + (size_t)(pw + 1) * P * 4;
     const size_t shmem2 = ((size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4 + (near ? (size_t)cw * (F2Q_PC_RING * 8 + F2Q_PC_VIA * 4) : 0);
@@ -636,14 +798,12 @@ static int launch_part(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &
     (void)hipFuncSetAttribute((const void *)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem2);
     for (uint32_t t0 = 0; t0 < pb.n_tiles; t0 += chunk_tiles) {
         const uint32_t t1 = std::min<uint32_t>(pb.n_tiles, t0 + chunk_tiles);
-#define F2Q_LAUNCH_PS(PW_)                                                                                             \
-        do {                                                                                                           \
-            auto k1 = a20 ? k_part_scatter<5, 2, true, PW_> : spec52 ? k_part_scatter<5, 2, false, PW_> : k_part_scatter<0, 0, false, PW_>; \
-            (void)hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem1);      \
-            hipLaunchKernelGGL(k1, dim3(grid1), dim3(64 * PW_), shmem1, c->stream, c->run_d, c->lib_d, pb, a1, ps, t0, t1); \
-        } while (0)
-        if (pw == 16) F2Q_LAUNCH_PS(16); else if (pw == 8) F2Q_LAUNCH_PS(8); else F2Q_LAUNCH_PS(4);
-#undef F2Q_LAUNCH_PS
+        auto scatter = [&](auto PW) {
+            auto k1 = fv == FV_A20 ? k_part_scatter<5, 2, true, PW> : fv == FV_SPEC52 ? k_part_scatter<5, 2, false, PW> : k_part_scatter<0, 0, false, PW>;
+            (void)hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem1);
+            hipLaunchKernelGGL(k1, dim3(grid1), dim3(64 * PW), shmem1, c->stream, c->run_d, c->lib_d, pb, a1, ps, t0, t1);
+        };
+        if (pw == 16) scatter(int_c<16>()); else if (pw == 8) scatter(int_c<8>()); else scatter(int_c<4>());
         HIPC(c, hipGetLastError());
         hipLaunchKernelGGL(kern2, dim3(grid2), dim3(64 * cw), shmem2, c->stream, c->run_d, c->lib_d, a2, ps, c->pt_slab0_d, c->pt_slab1_d);
         HIPC(c, hipGetLastError());
@@ -656,310 +816,105 @@ static int launch_part(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &
     return F2Q_OK;
 }
 
-// ---- launching ----------------------------------------------------------------------------------
+// the library in LDS (k_count_fixed4_lds): one fixed window (tiles that hold every row under it), or, mw, several
+// windows joined into one (Phred rule per part)
+template <bool MW>
+static auto fixed_lds_kernel(bool near, FixedVariant fv)
+{
+    if (near) return fv == FV_A20 ? k_count_fixed4_lds<5, 2, true, true, MW> : fv == FV_SPEC52 ? k_count_fixed4_lds<5, 2, true, false, MW> : k_count_fixed4_lds<0, 0, true, false, MW>;
+    return fv == FV_A20 ? k_count_fixed4_lds<5, 2, false, true, MW> : fv == FV_SPEC52 ? k_count_fixed4_lds<5, 2, false, false, MW> : k_count_fixed4_lds<0, 0, false, false, MW>;
+}
+static int launch_fixed_lds(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches, bool mw)
+{
+    const uint32_t wgs = (pb.n_tiles + F2Q_LT_WAVES - 1) / F2Q_LT_WAVES;
+    const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu);
+    const bool near = c->run_h.miss > 0;
+    const size_t shmem = ((near ? 2u : 1u) * (size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4;
+    const FixedVariant fv = fixed_variant(c, mw ? fixed_geom_at(0, c->run_h.n_iter * c->run_h.length, c->run_h.thr) : fixed_geom(c->run_h));
+    auto kern = mw ? fixed_lds_kernel<true>(near, fv) : fixed_lds_kernel<false>(near, fv);
+    int rc = slab_rows(c, grid, grid, acc);
+    if (rc) return rc;
+    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_LT_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
+    HIPC(c, hipGetLastError());
+    launches++;
+    return reduce_slabs(c, acc, grid, grid, launches);
+}
+
+// packed tables in L2 (k_count_fixed4): histogram in LDS, or, beyond F2Q_HIST_MAX features, a feature index per read slot
+// binned by k_hist_ranges
+static int launch_fixed_packed(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
+{
+    const uint32_t nf = c->lib_h.n_features;
+    const bool lds = nf <= F2Q_HIST_MAX;
+    const uint32_t wgs = (pb.n_tiles + F2Q_V2_WAVES - 1) / F2Q_V2_WAVES;
+    const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 2u);
+    const size_t shmem = (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 12 + (lds ? (size_t)nf * 4 : (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 4);
+    const bool spec52 = fixed_variant(c, fixed_geom(c->run_h)) != FV_GENERIC;      // (no a20 instance: spec52 serves it)
+    auto kern = lds ? (spec52 ? k_count_fixed4<true, 5, 2> : k_count_fixed4<true, 0, 0>)
+                    : (spec52 ? k_count_fixed4<false, 5, 2> : k_count_fixed4<false, 0, 0>);
+    const uint32_t n_ranges = lds ? 1u : (nf + F2Q_HIST_RANGE - 1) / F2Q_HIST_RANGE;
+    const uint32_t n_parts = lds ? grid : std::max<uint32_t>(1u, (uint32_t)c->n_cu / n_ranges);
+    // slab rows: one per counting workgroup (LDS histogram) or one per part of k_hist_ranges; stats rows per workgroup
+    int rc = slab_rows(c, n_parts, grid, acc);
+    if (rc) return rc;
+    if (!lds) {
+        if ((rc = grow_buf(c, &c->hit_buf_d, c->hit_buf_n, pb.n_slots, false))) return rc;
+        acc.hit_buf = c->hit_buf_d;                          // (the kernel writes every slot: no clearing)
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_V2_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
+    HIPC(c, hipGetLastError());
+    launches++;
+    if (!lds && nf) {
+        (void)hipFuncSetAttribute((const void *)k_hist_ranges, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(F2Q_HIST_RANGE * 4));
+        hipLaunchKernelGGL(k_hist_ranges, dim3(n_ranges * n_parts), dim3(1024), (size_t)F2Q_HIST_RANGE * 4, c->stream,
+                           c->hit_buf_d, (uint64_t)pb.n_slots, nf, n_parts, c->slab_d);
+        HIPC(c, hipGetLastError());
+        launches++;
+    }
+    return nf ? reduce_slabs(c, acc, n_parts, grid, launches) : F2Q_OK;
+}
+
+// one read per lane, wide tables: libraries the packed tables do not serve, or F2Q_FORCE_V1=1
+static int launch_fixed_v1(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
+{
+    const uint32_t grid = std::min<uint32_t>(pb.n_tiles, (uint32_t)c->n_cu * 8u);
+    if (c->lib_h.n_features <= F2Q_HIST_MAX) {
+        const size_t shmem = std::max<size_t>(4, (size_t)c->lib_h.n_features * 4);
+        hipLaunchKernelGGL(k_count_fixed<true>, dim3(grid), dim3(F2Q_TILE), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
+    } else {
+        hipLaunchKernelGGL(k_count_fixed<false>, dim3(grid), dim3(F2Q_TILE), 0, c->stream, c->run_d, c->lib_d, pb, acc);
+    }
+    HIPC(c, hipGetLastError());
+    launches++;
+    return F2Q_OK;
+}
+
 // one set of launches over a view of a block (all of it in Counter mode, a step of it in Extract+Count mode)
 static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, Accum &acc, uint32_t &launches)
 {
-    if (pb.n_tiles) c->last_path = F2Q_PATH_NONE;
-    if (pb.n_tiles && pb.planar_nw && c->plan.multi_pair) {
-        // several --us/--ds pairs on the planes
-        c->last_path = F2Q_PATH_PAIRS;
-        const bool lds = c->prm.mode == 0 && c->lib_h.n_features <= F2Q_HIST_MAX;
-        const uint32_t grid = std::min<uint32_t>(pb.n_tiles, (uint32_t)c->n_cu * 8u);          // (four workgroups of 256 threads are resident per CU at 128 VGPRs: two rounds)
-        const size_t shmem = lds ? std::max<size_t>(4, (((size_t)c->lib_h.n_features + 1) / 2) * 4) : 4;
-        const int nw = (int)pb.planar_nw, kb = c->plan.kb;
-        const bool sameq = c->run_h.thr_up == c->run_h.thr && c->run_h.thr_down == c->run_h.thr;
-#define F2Q_LAUNCH_MP2(NW_, KB_, SQ_)                                                                                  \
-        do {                                                                                                           \
-            if (lds) hipLaunchKernelGGL((k_count_anchor_pairs<NW_, KB_, SQ_, true>), dim3(grid), dim3(F2Q_AN_THREADS), shmem, \
-                                        c->stream, c->run_d, c->lib_d, c->ec, pb, acc, c->reads_seen);                 \
-            else hipLaunchKernelGGL((k_count_anchor_pairs<NW_, KB_, SQ_, false>), dim3(grid), dim3(F2Q_AN_THREADS), shmem, \
-                                    c->stream, c->run_d, c->lib_d, c->ec, pb, acc, c->reads_seen);                     \
-        } while (0)
-#define F2Q_LAUNCH_MP(NW_, KB_) do { if (sameq) F2Q_LAUNCH_MP2(NW_, KB_, true); else F2Q_LAUNCH_MP2(NW_, KB_, false); } while (0)
-        if (nw == 10) F2Q_LAUNCH_MP2(10, 3, false);      // reads of 161 .. 320 bases: the general instantiation (any --msu/--msd <= 7, any --qsu/--qsd)
-        else if (nw == 3 && kb == 0) F2Q_LAUNCH_MP(3, 0);
-        else if (nw == 3 && kb == 1) F2Q_LAUNCH_MP(3, 1);
-        else if (nw == 3) F2Q_LAUNCH_MP(3, 3);
-        else if (kb == 0) F2Q_LAUNCH_MP(5, 0);
-        else if (kb == 1) F2Q_LAUNCH_MP(5, 1);
-        else F2Q_LAUNCH_MP(5, 3);
-#undef F2Q_LAUNCH_MP
-#undef F2Q_LAUNCH_MP2
-        HIPC(c, hipGetLastError());
-        launches++;
-    } else if (pb.n_tiles && pb.planar_nw) {
-        // packed anchored path
-        const bool ecm = c->prm.mode == 1;
-        const bool lds = !ecm && c->lib_h.n_features <= F2Q_HIST_MAX;
-        c->last_path = ecm ? F2Q_PATH_EXTRACT : F2Q_PATH_ANCHOR;
-        uint32_t an_mult = 4u; { const char *e = getenv("F2Q_AN_GRID"); if (e && atoi(e) > 0) an_mult = (uint32_t)atoi(e); }
-        const uint32_t grid = std::min<uint32_t>(pb.n_tiles, (uint32_t)c->n_cu * an_mult);
-        const size_t shmem = (size_t)F2Q_AN_WAVES * F2Q_AN_QCAP * 12 + (lds ? (size_t)c->lib_h.n_features * 4 : 0);
-        if (!ecm) {
-            const size_t need = lds ? (size_t)grid * c->lib_h.n_features : 0;
-            if (need > c->slab_n || (size_t)grid > c->stat_slab_n) {
-                if (c->slab_d) (void)hipFree(c->slab_d);
-                if (c->stat_slab_d) (void)hipFree(c->stat_slab_d);
-                c->slab_d = nullptr; c->slab_n = 0; c->stat_slab_d = nullptr; c->stat_slab_n = 0;
-                HIPC(c, hipMalloc((void **)&c->slab_d, std::max<size_t>(need, 1) * sizeof(uint32_t)));
-                HIPC(c, hipMalloc((void **)&c->stat_slab_d, (size_t)grid * 8 * sizeof(unsigned long long)));
-                c->slab_n = need; c->stat_slab_n = grid;
-            }
-            if (lds) { acc.slab = c->slab_d; acc.stat_slab = c->stat_slab_d; }
-        }
-        const int nw = (int)pb.planar_nw, kb = c->plan.kb;
-        const bool sameq = c->run_h.thr_up == c->run_h.thr && c->run_h.thr_down == c->run_h.thr;
-        // the library in LDS (Counter mode, uniform 14..21-base library, --m <= 1, default --qsu/--qsd)
-        if (!ecm && lds && sameq && !c->no_lt && c->lib_h.lt.ok && c->run_h.miss <= 1 && pb.len != nullptr && nw != 10) {
-            c->last_path = F2Q_PATH_ANCHOR_LDS;
-            const uint32_t groups = (pb.n_tiles + F2Q_ALT_GROUPS - 1) / F2Q_ALT_GROUPS;
-            const uint32_t lgrid = std::min<uint32_t>(groups, (uint32_t)c->n_cu);
-            const bool near = c->run_h.miss > 0;
-            const size_t lshmem = ((near ? 2u : 1u) * (size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4;
-            const uint32_t nf_ = c->lib_h.n_features;
-            const size_t need = (size_t)lgrid * nf_;
-            if (need > c->slab_n || (size_t)lgrid > c->stat_slab_n) {
-                if (c->slab_d) (void)hipFree(c->slab_d);
-                if (c->stat_slab_d) (void)hipFree(c->stat_slab_d);
-                c->slab_d = nullptr; c->slab_n = 0; c->stat_slab_d = nullptr; c->stat_slab_n = 0;
-                HIPC(c, hipMalloc((void **)&c->slab_d, std::max<size_t>(need, 1) * sizeof(uint32_t)));
-                HIPC(c, hipMalloc((void **)&c->stat_slab_d, (size_t)lgrid * 8 * sizeof(unsigned long long)));
-                c->slab_n = need; c->stat_slab_n = lgrid;
-            }
-            acc.slab = c->slab_d; acc.stat_slab = c->stat_slab_d;
-#define F2Q_LAUNCH_ALT(NW_, KB_)                                                                                       \
-            do {                                                                                                       \
-                auto kern = near ? k_count_anchor_lt<NW_, KB_, true, true> : k_count_anchor_lt<NW_, KB_, true, false>;  \
-                (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lshmem);\
-                hipLaunchKernelGGL(kern, dim3(lgrid), dim3(F2Q_ALT_THREADS), lshmem, c->stream, c->run_d, c->lib_d, pb, acc); \
-            } while (0)
-            if (nw == 3 && kb == 0) F2Q_LAUNCH_ALT(3, 0);
-            else if (nw == 3 && kb == 1) F2Q_LAUNCH_ALT(3, 1);
-            else if (nw == 3) F2Q_LAUNCH_ALT(3, 3);
-            else if (kb == 0) F2Q_LAUNCH_ALT(5, 0);
-            else if (kb == 1) F2Q_LAUNCH_ALT(5, 1);
-            else F2Q_LAUNCH_ALT(5, 3);
-#undef F2Q_LAUNCH_ALT
-            HIPC(c, hipGetLastError());
-            hipLaunchKernelGGL(k_reduce_slabs, dim3((nf_ + 63) / 64, F2Q_RED_SPLIT), dim3(256), 0, c->stream,
-                               c->slab_d, lgrid, nf_, acc.counts, c->stat_slab_d, lgrid, acc.stats);
-            HIPC(c, hipGetLastError());
-            launches += 2;
-        } else {
-#define F2Q_LAUNCH_AN2(NW_, KB_, SQ_)                                                                                \
-        do {                                                                                                         \
-            if (ecm) hipLaunchKernelGGL((k_count_anchor<NW_, KB_, true, false, SQ_>), dim3(grid), dim3(F2Q_AN_THREADS),   \
-                                        shmem, c->stream, c->run_d, c->lib_d, c->ec, pb, acc, c->reads_seen);     \
-            else if (lds) hipLaunchKernelGGL((k_count_anchor<NW_, KB_, false, true, SQ_>), dim3(grid),               \
-                                             dim3(F2Q_AN_THREADS), shmem, c->stream, c->run_d, c->lib_d, c->ec,      \
-                                             pb, acc, c->reads_seen);                                             \
-            else hipLaunchKernelGGL((k_count_anchor<NW_, KB_, false, false, SQ_>), dim3(grid), dim3(F2Q_AN_THREADS),  \
-                                    shmem, c->stream, c->run_d, c->lib_d, c->ec, pb, acc, c->reads_seen);         \
-        } while (0)
-#define F2Q_LAUNCH_AN(NW_, KB_) do { if (sameq) F2Q_LAUNCH_AN2(NW_, KB_, true); else F2Q_LAUNCH_AN2(NW_, KB_, false); } while (0)
-        if (nw == 10) F2Q_LAUNCH_AN2(10, 3, false);      // reads of 161 .. 320 bases: the general instantiation
-        else if (nw == 3 && kb == 0) F2Q_LAUNCH_AN(3, 0);
-        else if (nw == 3 && kb == 1) F2Q_LAUNCH_AN(3, 1);
-        else if (nw == 3) F2Q_LAUNCH_AN(3, 3);
-        else if (kb == 0) F2Q_LAUNCH_AN(5, 0);
-        else if (kb == 1) F2Q_LAUNCH_AN(5, 1);
-        else F2Q_LAUNCH_AN(5, 3);
-#undef F2Q_LAUNCH_AN
-#undef F2Q_LAUNCH_AN2
-        HIPC(c, hipGetLastError());
-        launches++;
-        if (lds && c->lib_h.n_features) {
-            hipLaunchKernelGGL(k_reduce_slabs, dim3((c->lib_h.n_features + 63) / 64, F2Q_RED_SPLIT), dim3(256), 0, c->stream,
-                               c->slab_d, grid, c->lib_h.n_features, acc.counts, c->stat_slab_d, grid, acc.stats);
-            HIPC(c, hipGetLastError());
-            launches++;
-        }
-        }
-    } else if (pb.n_tiles && c->prm.mode == 1) {
-        const uint32_t wgs = (pb.n_tiles + F2Q_V2_WAVES - 1) / F2Q_V2_WAVES;
-        const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 4u);
-        c->last_path = F2Q_PATH_EXTRACT;
-        hipLaunchKernelGGL(k_extract_fixed4, dim3(grid), dim3(F2Q_V2_THREADS), 0, c->stream, c->run_d, c->ec, pb, acc, c->reads_seen);
-        HIPC(c, hipGetLastError());
-        launches++;
-    } else if (pb.n_tiles) {
-        const bool lds = c->lib_h.n_features <= F2Q_HIST_MAX;
-        const bool v2 = !c->force_v1 && c->lib_h.pk.len == (uint32_t)c->run_h.length && c->lib_h.pk.len > 0 &&
-                        c->lib_h.n_irregular == 0;
-        const int mw_total = c->run_h.n_iter * c->run_h.length;
-        const bool mw_lt = c->plan.multi && lds && !c->no_lt && c->lib_h.lt.ok && c->lib_h.lt.len == (uint32_t)mw_total && c->run_h.miss <= 1 &&
-                           pb.len != nullptr && (uint32_t)((mw_total + 3) / 4) <= pb.wq && (uint32_t)((mw_total + 15) / 16) <= pb.wb;
-        if (mw_lt) {
-            // several windows per read, every feature with one part per window: the joined keys on the library-in-LDS kernel
-            // (the tiles hold the windows back to back: one window of n_iter * length bases, Phred rule per part)
-            c->last_path = F2Q_PATH_MULTI_LDS;
-            const uint32_t wgs = (pb.n_tiles + F2Q_LT_WAVES - 1) / F2Q_LT_WAVES;
-            const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu);
-            const bool near = c->run_h.miss > 0;
-            const size_t shmem = ((near ? 2u : 1u) * (size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4;
-            const FixedGeom fg = fixed_geom_at(0, mw_total, c->run_h.thr);
-            const bool spec52 = !c->force_generic && fg.nq == 5 && fg.nb == 2 && c->run_h.thr >= 33;
-            const bool a20 = spec52 && mw_total == 20;              // (two 10-base or four 5-base windows: the usual 20-base geometry)
-            auto kern = near ? (a20 ? k_count_fixed4_lds<5, 2, true, true, true> : spec52 ? k_count_fixed4_lds<5, 2, true, false, true> : k_count_fixed4_lds<0, 0, true, false, true>)
-                             : (a20 ? k_count_fixed4_lds<5, 2, false, true, true> : spec52 ? k_count_fixed4_lds<5, 2, false, false, true> : k_count_fixed4_lds<0, 0, false, false, true>);
-            const uint32_t nf_ = c->lib_h.n_features;
-            const size_t need = (size_t)grid * nf_;
-            if (need > c->slab_n || (size_t)grid > c->stat_slab_n) {
-                if (c->slab_d) (void)hipFree(c->slab_d);
-                if (c->stat_slab_d) (void)hipFree(c->stat_slab_d);
-                c->slab_d = nullptr; c->slab_n = 0; c->stat_slab_d = nullptr; c->stat_slab_n = 0;
-                HIPC(c, hipMalloc((void **)&c->slab_d, std::max<size_t>(need, 1) * sizeof(uint32_t)));
-                HIPC(c, hipMalloc((void **)&c->stat_slab_d, (size_t)grid * 8 * sizeof(unsigned long long)));
-                c->slab_n = need; c->stat_slab_n = grid;
-            }
-            acc.slab = c->slab_d; acc.stat_slab = c->stat_slab_d;
-            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_LT_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
-            HIPC(c, hipGetLastError());
-            hipLaunchKernelGGL(k_reduce_slabs, dim3((nf_ + 63) / 64, F2Q_RED_SPLIT), dim3(256), 0, c->stream,
-                               c->slab_d, grid, nf_, acc.counts, c->stat_slab_d, grid, acc.stats);
-            launches++;
-        } else if (c->plan.multi) {
-            // several windows per read (--st a,b,...): k-part keys against the k-part features
-            c->last_path = F2Q_PATH_MULTI;
-            const uint32_t wgs = (pb.n_tiles + F2Q_V2_WAVES - 1) / F2Q_V2_WAVES;
-            const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 2u);
-            const size_t shmem = (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 12 + (lds ? (size_t)c->lib_h.n_features * 4 : 0);
-            const uint32_t nf_ = c->lib_h.n_features;
-            const size_t need = lds ? (size_t)grid * nf_ : 0;
-            if (need > c->slab_n || (size_t)grid > c->stat_slab_n) {
-                if (c->slab_d) (void)hipFree(c->slab_d);
-                if (c->stat_slab_d) (void)hipFree(c->stat_slab_d);
-                c->slab_d = nullptr; c->slab_n = 0; c->stat_slab_d = nullptr; c->stat_slab_n = 0;
-                HIPC(c, hipMalloc((void **)&c->slab_d, std::max<size_t>(need, 1) * sizeof(uint32_t)));
-                HIPC(c, hipMalloc((void **)&c->stat_slab_d, (size_t)grid * 8 * sizeof(unsigned long long)));
-                c->slab_n = need; c->stat_slab_n = grid;
-            }
-            acc.slab = c->slab_d; acc.stat_slab = c->stat_slab_d;
-            if (lds) hipLaunchKernelGGL(k_count_multi4<true>, dim3(grid), dim3(F2Q_V2_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc, c->plan.need);
-            else hipLaunchKernelGGL(k_count_multi4<false>, dim3(grid), dim3(F2Q_V2_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc, c->plan.need);
-            HIPC(c, hipGetLastError());
-            hipLaunchKernelGGL(k_reduce_slabs, dim3(std::max<uint32_t>(1u, (nf_ + 63) / 64), F2Q_RED_SPLIT), dim3(256), 0, c->stream,
-                               c->slab_d, lds ? grid : 0u, nf_, acc.counts, c->stat_slab_d, grid, acc.stats);
-            launches++;
-        } else {
-        const FixedGeom fgeo = fixed_geom(c->run_h);
-        // the library in LDS: uniform 14..21-base library, --m <= 1, and tiles that hold every row under the window
-        const bool use_lt = v2 && lds && !c->no_lt && c->lib_h.lt.ok && c->lib_h.lt.len == (uint32_t)c->run_h.length &&
-                            c->run_h.miss <= 1 && (uint32_t)(fgeo.qw0 + fgeo.nq) <= pb.wq && (uint32_t)(fgeo.bw0 + fgeo.nb) <= pb.wb &&
-                            pb.len != nullptr;
-        // a library beyond one workgroup's LDS, dealt into partitions (or F2Q_PT_PARTS set: that path whatever the size)
-        const bool use_pt = v2 && !c->no_pt && c->lib_h.pt.ok && c->lib_h.pt.len == (uint32_t)c->run_h.length && c->run_h.miss <= 1 &&
-                            (uint32_t)(fgeo.qw0 + fgeo.nq) <= pb.wq && (uint32_t)(fgeo.bw0 + fgeo.nb) <= pb.wb && pb.len != nullptr &&
-                            (c->ix.pt_force_parts > 0 || (!use_lt && (uint64_t)pb.n_tiles * F2Q_TILE >= c->pt_min_reads));
-        if (use_pt) {
-            c->last_path = F2Q_PATH_FIXED_PART;
-            int prc = launch_part(c, pb, acc, launches);
-            if (prc) return prc;
-            launches--;                                  // (the common tail below counts one)
-        } else if (use_lt) {
-            c->last_path = F2Q_PATH_FIXED_LDS;
-            const uint32_t wgs = (pb.n_tiles + F2Q_LT_WAVES - 1) / F2Q_LT_WAVES;
-            const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu);
-            const bool near = c->run_h.miss > 0;
-            const size_t shmem = ((near ? 2u : 1u) * (size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4;
-            const bool spec52 = !c->force_generic && fgeo.nq == 5 && fgeo.nb == 2 && c->run_h.thr >= 33;
-            const bool a20 = spec52 && fgeo.L == 20 && (fgeo.st & 15) == 0;
-            auto kern = near ? (a20 ? k_count_fixed4_lds<5, 2, true, true> : spec52 ? k_count_fixed4_lds<5, 2, true, false> : k_count_fixed4_lds<0, 0, true, false>)
-                             : (a20 ? k_count_fixed4_lds<5, 2, false, true> : spec52 ? k_count_fixed4_lds<5, 2, false, false> : k_count_fixed4_lds<0, 0, false, false>);
-            const uint32_t nf_ = c->lib_h.n_features;
-            const size_t need = (size_t)grid * nf_;
-            if (need > c->slab_n || (size_t)grid > c->stat_slab_n) {
-                if (c->slab_d) (void)hipFree(c->slab_d);
-                if (c->stat_slab_d) (void)hipFree(c->stat_slab_d);
-                c->slab_d = nullptr; c->slab_n = 0; c->stat_slab_d = nullptr; c->stat_slab_n = 0;
-                HIPC(c, hipMalloc((void **)&c->slab_d, std::max<size_t>(need, 1) * sizeof(uint32_t)));
-                HIPC(c, hipMalloc((void **)&c->stat_slab_d, (size_t)grid * 8 * sizeof(unsigned long long)));
-                c->slab_n = need; c->stat_slab_n = grid;
-            }
-            acc.slab = c->slab_d; acc.stat_slab = c->stat_slab_d;
-            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_LT_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
-            HIPC(c, hipGetLastError());
-            hipLaunchKernelGGL(k_reduce_slabs, dim3((nf_ + 63) / 64, F2Q_RED_SPLIT), dim3(256), 0, c->stream,
-                               c->slab_d, grid, nf_, acc.counts, c->stat_slab_d, grid, acc.stats);
-            launches++;
-        } else if (v2) {
-            c->last_path = F2Q_PATH_FIXED_PACKED;
-            const uint32_t wgs = (pb.n_tiles + F2Q_V2_WAVES - 1) / F2Q_V2_WAVES;
-            uint32_t v2_mult = 2u; { const char *e = getenv("F2Q_V2_GRID"); if (e && atoi(e) > 0) v2_mult = (uint32_t)atoi(e); }
-            const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * v2_mult);
-            const size_t shmem = (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 12 + (lds ? (size_t)c->lib_h.n_features * 4 : (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 4);
-            const FixedGeom fg = fixed_geom(c->run_h);
-            const bool spec52 = !c->force_generic && fg.nq == 5 && fg.nb == 2 && c->run_h.thr >= 33;
-            auto kern = lds ? (spec52 ? k_count_fixed4<true, 5, 2> : k_count_fixed4<true, 0, 0>)
-                            : (spec52 ? k_count_fixed4<false, 5, 2> : k_count_fixed4<false, 0, 0>);
-            const uint32_t nf_ = c->lib_h.n_features;
-            const uint32_t n_ranges = lds ? 1u : (nf_ + F2Q_HIST_RANGE - 1) / F2Q_HIST_RANGE;
-            const uint32_t n_parts = lds ? grid : std::max<uint32_t>(1u, (uint32_t)c->n_cu / n_ranges);
-            {
-                // slab rows: one per counting workgroup (LDS histogram) or one per part of k_hist_ranges; stats rows per workgroup
-                const size_t need = (size_t)n_parts * nf_;
-                if (need > c->slab_n || (size_t)grid > c->stat_slab_n) {
-                    if (c->slab_d) (void)hipFree(c->slab_d);
-                    if (c->stat_slab_d) (void)hipFree(c->stat_slab_d);
-                    c->slab_d = nullptr; c->slab_n = 0; c->stat_slab_d = nullptr; c->stat_slab_n = 0;
-                    HIPC(c, hipMalloc((void **)&c->slab_d, std::max<size_t>(need, 1) * sizeof(uint32_t)));
-                    HIPC(c, hipMalloc((void **)&c->stat_slab_d, (size_t)grid * 8 * sizeof(unsigned long long)));
-                    c->slab_n = need; c->stat_slab_n = grid;
-                }
-                acc.slab = c->slab_d;
-                acc.stat_slab = c->stat_slab_d;
-            }
-            if (!lds) {
-                if (pb.n_slots > c->hit_buf_n) {
-                    if (c->hit_buf_d) (void)hipFree(c->hit_buf_d);
-                    c->hit_buf_d = nullptr; c->hit_buf_n = 0;
-                    HIPC(c, hipMalloc((void **)&c->hit_buf_d, pb.n_slots * sizeof(uint32_t)));
-                    c->hit_buf_n = pb.n_slots;
-                }
-                acc.hit_buf = c->hit_buf_d;                          // (the kernel writes every slot: no clearing)
-            }
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_V2_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
-            HIPC(c, hipGetLastError());
-            if (!lds && nf_) {
-                (void)hipFuncSetAttribute((const void *)k_hist_ranges, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(F2Q_HIST_RANGE * 4));
-                hipLaunchKernelGGL(k_hist_ranges, dim3(n_ranges * n_parts), dim3(1024), (size_t)F2Q_HIST_RANGE * 4, c->stream,
-                                   c->hit_buf_d, (uint64_t)pb.n_slots, nf_, n_parts, c->slab_d);
-                HIPC(c, hipGetLastError());
-                launches++;
-            }
-            if (nf_) {
-                hipLaunchKernelGGL(k_reduce_slabs, dim3((nf_ + 63) / 64, F2Q_RED_SPLIT), dim3(256), 0, c->stream,
-                                   c->slab_d, n_parts, nf_, acc.counts, c->stat_slab_d, grid, acc.stats);
-                launches++;
-            }
-        } else {
-            c->last_path = F2Q_PATH_FIXED_V1;
-            const uint32_t grid = std::min<uint32_t>(pb.n_tiles, (uint32_t)c->n_cu * 8u);
-            if (lds) {
-                size_t shmem = std::max<size_t>(4, (size_t)c->lib_h.n_features * 4);
-                hipLaunchKernelGGL(k_count_fixed<true>, dim3(grid), dim3(F2Q_TILE), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
-            } else {
-                hipLaunchKernelGGL(k_count_fixed<false>, dim3(grid), dim3(F2Q_TILE), 0, c->stream, c->run_d, c->lib_d, pb, acc);
-            }
-        }
-        }
-        HIPC(c, hipGetLastError());
-        launches++;
+    int rc = F2Q_OK;
+    if (pb.n_tiles) switch (c->last_path = choose_path(c, pb)) {
+        case F2Q_PATH_PAIRS:        rc = launch_pairs(c, pb, acc, launches); break;
+        case F2Q_PATH_ANCHOR:       rc = launch_anchor(c, pb, acc, launches); break;
+        case F2Q_PATH_ANCHOR_LDS:   rc = launch_anchor_lds(c, pb, acc, launches); break;
+        case F2Q_PATH_EXTRACT:      rc = pb.planar_nw ? launch_anchor(c, pb, acc, launches) : launch_extract_fixed(c, pb, acc, launches); break;
+        case F2Q_PATH_MULTI_LDS:    rc = launch_fixed_lds(c, pb, acc, launches, true); break;
+        case F2Q_PATH_MULTI:        rc = launch_multi(c, pb, acc, launches); break;
+        case F2Q_PATH_FIXED_PART:   rc = launch_part(c, pb, acc, launches); break;
+        case F2Q_PATH_FIXED_LDS:    rc = launch_fixed_lds(c, pb, acc, launches, false); break;
+        case F2Q_PATH_FIXED_PACKED: rc = launch_fixed_packed(c, pb, acc, launches); break;
+        default:                    rc = launch_fixed_v1(c, pb, acc, launches); break;
     }
-    if (rbv.n) {
-        RawBlock rb = rbv;
-        rb.first_index += c->reads_seen;
-        const uint64_t wg = (rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS;
-        uint32_t gmul = 64u; { const char *e = getenv("F2Q_GEN_GRID"); if (e && atoi(e) > 0) gmul = (uint32_t)atoi(e); }
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * gmul);
-        hipLaunchKernelGGL(k_count_general, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
-        HIPC(c, hipGetLastError());
-        launches++;
-        EC_POINT(c, "k_count_general");
-    }
+    if (rc || !rbv.n) return rc;
+    RawBlock rb = rbv;
+    rb.first_index += c->reads_seen;
+    const uint64_t wg = (rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
+    hipLaunchKernelGGL(k_count_general, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
+    HIPC(c, hipGetLastError());
+    launches++;
+    EC_POINT(c, "k_count_general");
     return F2Q_OK;
 }
 
@@ -1003,6 +958,22 @@ static int launch_aux_general(f2q_ctx *c, const f2q_block *b, Accum &acc, uint32
     return F2Q_OK;
 }
 
+// reads the Extract+Count counters into ctr (after the stream's work so far); a table that overflowed fails the call
+static int ec_counters(f2q_ctx *c, unsigned long long ctr[F2Q_CTR_WORDS])
+{
+    HIPC(c, hipMemcpyAsync(ctr, c->ec.ctr, F2Q_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (ctr[2]) return fail(c, F2Q_ENOMEM, "Extract+Count table overflow (internal sizing error, code " + std::to_string(ctr[2]) + ")");
+    return F2Q_OK;
+}
+// an Extract+Count block whose packed tiles take the hot-key kernels: anchored tiles of one pair (not the 161 .. 320-base
+// instantiation) and fixed-window tiles
+static bool ec_hot_path(const f2q_ctx *c, const f2q_block *b)
+{
+    const PackedBlock &pb = b->pb;
+    return pb.n_tiles && !c->no_hot && !c->plan.multi_pair && (!pb.planar_nw || (pb.len != nullptr && pb.planar_nw != 10));
+}
+
 // one launch of the hot-key kernel over a view of the block's anchored tiles (it starts slot_base slots into the
 // block); the tables have room (the caller reserved).  learning: the hot set is not built yet, the kernel runs with an
 // empty one and notes the keys that come up F2Q_HOT_MINCOUNT times.  ctr: the counters after the launch.
@@ -1012,8 +983,6 @@ static int launch_hot(f2q_ctx *c, const PackedBlock &v, uint64_t slot_base, Accu
     int rc = hot_arrays(c);
     if (rc) return rc;
     if (learning) HIPC(c, hipMemsetAsync(c->hot.keys, 0xFF, (size_t)F2Q_HOT_SLOTS * 8, c->stream));   // an empty set
-    const int nw = (int)v.planar_nw, kb = c->plan.kb;
-    const bool sameq = c->run_h.thr_up == c->run_h.thr && c->run_h.thr_down == c->run_h.thr;
     const size_t shmem = (size_t)F2Q_HOT_SLOTS * 12;             // key words + counters
     if (!v.planar_nw) {
         // fixed window: one wave per tile
@@ -1024,33 +993,20 @@ static int launch_hot(f2q_ctx *c, const PackedBlock &v, uint64_t slot_base, Accu
         hipLaunchKernelGGL(kern, dim3(fgrid), dim3(F2Q_FH_THREADS), shmem, c->stream, c->run_d, c->ec, c->hot, v, acc, c->reads_seen,
                            c->defer_d, slot_base, (uint64_t)c->defer_cap);
     } else {
-    const uint32_t groups = (v.n_tiles + F2Q_HOT_GROUPS - 1) / F2Q_HOT_GROUPS;
-    const uint32_t grid = std::min<uint32_t>(groups, (uint32_t)c->n_cu);
-#define F2Q_LAUNCH_HOT2(NW_, KB_, SQ_)                                                                                 \
-    do {                                                                                                               \
-        auto kern = learning ? k_extract_anchor_hot<NW_, KB_, SQ_, true> : k_extract_anchor_hot<NW_, KB_, SQ_, false>; \
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);         \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_HOT_THREADS), shmem, c->stream, c->run_d, c->ec, c->hot, v, acc, \
-                           c->reads_seen, c->defer_d, slot_base, (uint64_t)c->defer_cap);                              \
-    } while (0)
-#define F2Q_LAUNCH_HOT(NW_, KB_) do { if (sameq) F2Q_LAUNCH_HOT2(NW_, KB_, true); else F2Q_LAUNCH_HOT2(NW_, KB_, false); } while (0)
-    if (nw == 3 && kb == 0) F2Q_LAUNCH_HOT(3, 0);
-    else if (nw == 3 && kb == 1) F2Q_LAUNCH_HOT(3, 1);
-    else if (nw == 3) F2Q_LAUNCH_HOT(3, 3);
-    else if (kb == 0) F2Q_LAUNCH_HOT(5, 0);
-    else if (kb == 1) F2Q_LAUNCH_HOT(5, 1);
-    else F2Q_LAUNCH_HOT(5, 3);
-#undef F2Q_LAUNCH_HOT
-#undef F2Q_LAUNCH_HOT2
+        const uint32_t groups = (v.n_tiles + F2Q_HOT_GROUPS - 1) / F2Q_HOT_GROUPS;
+        const uint32_t grid = std::min<uint32_t>(groups, (uint32_t)c->n_cu);
+        anchored_geom(v.planar_nw, c->plan.kb, same_q(c->run_h), [&](auto NW, auto KB, auto SQ) {
+            auto kern = learning ? k_extract_anchor_hot<NW, KB, SQ, true> : k_extract_anchor_hot<NW, KB, SQ, false>;
+            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_HOT_THREADS), shmem, c->stream, c->run_d, c->ec, c->hot, v, acc,
+                               c->reads_seen, c->defer_d, slot_base, (uint64_t)c->defer_cap);
+        });
     }
     HIPC(c, hipGetLastError());
     launches++;
     if (aux_block && (rc = launch_aux_general(c, aux_block, acc, launches))) return rc;
     EC_POINT(c, learning ? "k_extract_anchor_hot (learning)" : "k_extract_anchor_hot");
-    HIPC(c, hipMemcpyAsync(ctr, c->ec.ctr, F2Q_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (ctr[2]) return fail(c, F2Q_ENOMEM, "Extract+Count table overflow (internal sizing error, code " + std::to_string(ctr[2]) + ")");
-    return F2Q_OK;
+    return ec_counters(c, ctr);
 }
 
 // the reads the launches over a block set aside (ctr: the counters as just read): windows the single-word table cannot
@@ -1117,8 +1073,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
             if (v.index) v.index += (size_t)t0 * F2Q_TILE; else v.first_index += (uint64_t)t0 * F2Q_TILE;
             return v;
         };
-        // anchored tiles (one pair) and fixed-window tiles take the hot-key kernels
-        const bool hot_path = b->pb.n_tiles && !c->no_hot && !c->plan.multi_pair && (b->pb.planar_nw ? b->pb.len != nullptr && b->pb.planar_nw != 10 : true);
+        const bool hot_path = ec_hot_path(c, b);
         if (hot_path) {
             // anchored tiles: hot keys in LDS.  The first hot_learn reads of a sample go through the same kernel with an
             // empty hot set (every key takes the table's insert); then the set is built and serves the rest of the sample.
@@ -1127,11 +1082,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
             const uint64_t to_learn = c->hot_valid || c->ec_learned >= c->hot_learn ? 0 : std::min<uint64_t>(n, c->hot_learn - c->ec_learned);
             unsigned long long ctr[F2Q_CTR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
             int rc;
-            if (c->ec.ctr) {
-                HIPC(c, hipMemcpyAsync(ctr, c->ec.ctr, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
-                HIPC(c, hipStreamSynchronize(c->stream));
-                if (ctr[2]) return fail(c, F2Q_ENOMEM, "Extract+Count table overflow (internal sizing error, code " + std::to_string(ctr[2]) + ")");
-            }
+            if (c->ec.ctr && (rc = ec_counters(c, ctr))) return rc;
             // new single-word keys to expect: at the rate the sample has shown once the learning reads are in (a table that
             // fills up all the same only moves reads to the deferred pass), a guess of one key per six reads before that
             auto expect_of = [&](uint64_t reads) {
@@ -1142,12 +1093,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
             const uint64_t raw_bytes = b->raw_key_bytes + b->rb.n * F2Q_MAX_ITER + aside * ((uint64_t)b->pb.rmax + F2Q_MAX_ITER);
             if ((rc = ec_reserve(c, (to_learn ? to_learn + (n - to_learn) / 6 : expect_of(n)) + b->rb.n + aside, b->rb.n + aside, raw_bytes, ctr))) return rc;
             // the list of reads set aside: room for every slot of the block, cleared once per block
-            if (n > c->defer_cap || !c->defer_d) {
-                if (c->defer_d) (void)hipFree(c->defer_d);
-                c->defer_d = nullptr; c->defer_cap = 0;
-                HIPC(c, hipMalloc((void **)&c->defer_d, (size_t)n * sizeof(unsigned long long)));
-                c->defer_cap = n;
-            }
+            if ((rc = grow_buf(c, &c->defer_d, c->defer_cap, n, false))) return rc;
             HIPC(c, hipMemsetAsync(c->ec.ctr + F2Q_CTR_ASIDE, 0, 16, c->stream));
             uint32_t t0 = 0;
             if (to_learn) {
@@ -1219,13 +1165,11 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
         t->kernel_ms = ms; t->reads = b->n_reads; t->general_reads = b->n_general;
         t->fast_reads = b->n_reads - b->n_general; t->launches = launches; t->path = c->last_path;
     }
-    if (c->prm.mode == 1 && b->n_reads && !(b->pb.n_tiles && !c->no_hot && !c->plan.multi_pair && (b->pb.planar_nw ? b->pb.len != nullptr && b->pb.planar_nw != 10 : true))) {
+    if (c->prm.mode == 1 && b->n_reads && !ec_hot_path(c, b)) {
         // (the hot-key path has looked at the counters after its last launch; what its deferred passes could still
         // report is seen by the next call that reads them)
-        unsigned long long ctr[4];
-        HIPC(c, hipMemcpyAsync(ctr, c->ec.ctr, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipStreamSynchronize(c->stream));
-        if (ctr[2]) return fail(c, F2Q_ENOMEM, "Extract+Count table overflow (internal sizing error, code " + std::to_string(ctr[2]) + ")");
+        unsigned long long ctr[F2Q_CTR_WORDS];
+        return ec_counters(c, ctr);
     }
     return F2Q_OK;
 }
