@@ -48,7 +48,7 @@ struct f2q_ctx {
     hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
     std::vector<hipEvent_t> q_ev;          // f2q_count_resident_queued: a pair of events per queued step
     uint32_t q_n = 0;                      // steps queued since the last f2q_queued_times
-    hipStream_t copy_stream = nullptr;   // f2q_count_file: the text of the next piece travels while this one is counted
+    hipStream_t copy_stream = nullptr;   // PieceStream: the text of the next piece travels while this one is counted
     hipEvent_t ev_copy = nullptr;
     RunDev run_h{};
     RunDev *run_d = nullptr;
@@ -1174,6 +1174,27 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
     return F2Q_OK;
 }
 
+static void timing_add(f2q_timing &sum, const f2q_timing &one)
+{
+    sum.kernel_ms += one.kernel_ms; sum.total_ms += one.total_ms; sum.reads += one.reads;
+    sum.fast_reads += one.fast_reads; sum.general_reads += one.general_reads; sum.launches += one.launches;
+    if (one.path) sum.path = one.path;
+}
+
+// the ev_a / ev_b bracket of a counting call: ev_a was recorded on c->stream when the call began; *t = sum, with
+// total_ms the event time from there to now
+static int timing_close(f2q_ctx *c, f2q_timing *t, const f2q_timing &sum)
+{
+    if (!t) return F2Q_OK;
+    hipError_t e = hipEventRecord(c->ev_b, c->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(c->ev_b);
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev_a, c->ev_b);
+    if (e != hipSuccess) return fail(c, F2Q_EHIP, hipGetErrorString(e));
+    *t = sum; t->total_ms = ms;
+    return F2Q_OK;
+}
+
 extern "C" int f2q_count_resident(f2q_ctx *c, const f2q_block *b, f2q_timing *t)
 {
     if (!c || !b) return F2Q_EINVAL;
@@ -1181,13 +1202,7 @@ extern "C" int f2q_count_resident(f2q_ctx *c, const f2q_block *b, f2q_timing *t)
     if (t) { memset(t, 0, sizeof *t); HIPC(c, hipEventRecord(c->ev_a, c->stream)); }
     int rc = launch_block(c, b, t);
     if (rc) return rc;
-    if (t) {
-        HIPC(c, hipEventRecord(c->ev_b, c->stream));
-        HIPC(c, hipEventSynchronize(c->ev_b));
-        float ms = 0; HIPC(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-        t->total_ms = ms;
-    }
-    return F2Q_OK;
+    return t ? timing_close(c, t, *t) : F2Q_OK;
 }
 
 extern "C" int f2q_count_resident_queued(f2q_ctx *c, const f2q_block *b)
@@ -1445,22 +1460,13 @@ extern "C" int f2q_count_block(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, 
         f2q_timing one; memset(&one, 0, sizeof one);
         rc = count_window(c, fastq + pos, take, nullptr, &used, t ? &one : nullptr);
         if (rc) return rc;
-        sum.kernel_ms += one.kernel_ms; sum.reads += one.reads; sum.fast_reads += one.fast_reads;
-        sum.general_reads += one.general_reads; sum.launches += one.launches; if (one.path) sum.path = one.path;
+        timing_add(sum, one);
         if (used == 0) break;                          // no complete record left in this window
         pos += used;
         if (take < ((size_t)1 << 30)) break;           // that was the tail: what is left is a partial record
     }
     if (consumed) *consumed = pos;
-    if (t) {
-        hipError_t e = hipEventRecord(c->ev_b, c->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(c->ev_b);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev_a, c->ev_b);
-        if (e != hipSuccess) return fail(c, F2Q_EHIP, hipGetErrorString(e));
-        *t = sum; t->total_ms = ms;
-    }
-    return F2Q_OK;
+    return timing_close(c, t, sum);
 }
 
 // ---- FASTQ text resident in device memory ------------------------------------------------------------------
@@ -1494,15 +1500,7 @@ extern "C" int f2q_count_text(f2q_ctx *c, f2q_text *txt, size_t *consumed, f2q_t
     int rc = txt->nbytes ? count_window(c, nullptr, txt->nbytes, &pre, &used, t ? &one : nullptr) : F2Q_OK;
     if (rc) return rc;
     if (consumed) *consumed = used;
-    if (t) {
-        hipError_t e = hipEventRecord(c->ev_b, c->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(c->ev_b);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev_a, c->ev_b);
-        if (e != hipSuccess) return fail(c, F2Q_EHIP, hipGetErrorString(e));
-        *t = one; t->total_ms = ms;
-    }
-    return F2Q_OK;
+    return timing_close(c, t, one);
 }
 
 extern "C" void f2q_text_free(f2q_ctx *c, f2q_text *t)
@@ -1550,6 +1548,146 @@ struct PinnedPool {
     }
 };
 static PinnedPool g_pinned;
+
+// One piece of text in a pinned slot, as the reader thread describes it: n bytes at the slot's head room, the text to
+// count starting a bytes into them.  The last piece holds no text; it only ends the stream.
+struct Piece { int slot = -1; size_t n = 0, a = 0; uint64_t max_records = ~0ull, first_read = 0; bool ok = true, last = false; };
+// a piece's text copied ahead to the device, `head` bytes into the buffer
+struct Staged { void *buf = nullptr; size_t cap = 0; int slot = -1; size_t n = 0; };
+
+// free a staged copy once `s`, the last stream to touch it, is done with it
+static void free_staged(f2q_ctx *c, Staged &st, hipStream_t s)
+{
+    if (!st.buf) return;
+    (void)hipStreamSynchronize(s);
+    std::vector<void *> v{st.buf}; free_all(c, v);
+    st = Staged();
+}
+
+// The piece pipeline of f2q_count_file(_shard) and f2q_count_pieces.  Three pinned slots: one being counted, one ready
+// (its text possibly already travelling to the device), one being filled by the reader thread with fill(j, p, pc):
+// piece j's text goes to p, `head` bytes into the slot, and pc describes it.  next() hands the pieces over in order.
+// When staging is allowed, the text of the piece after the one handed over is copied to the device on c->copy_stream
+// while that one is counted; next() makes c->stream wait for that copy and leaves it in `cur`.  The destructor stops
+// and joins the reader and gives back every buffer, so no return path leaves a joinable thread or a held buffer
+// behind; whatever fill uses must outlive the PieceStream.
+struct PieceStream {
+    static constexpr int NSLOT = 3;
+    f2q_ctx *const c;
+    size_t head = 0;
+    bool can_stage = false, force_stage = false;
+    PinBuf buf[NSLOT];
+    std::mutex mu; std::condition_variable cv;
+    std::deque<Piece> ready; bool slot_free[NSLOT] = {true, true, true}; bool stop = false;
+    std::thread reader;
+    Staged staged;                                 // the text of the next piece, on its way to the device
+    Staged cur;                                    // the text of the piece next() handed over, if it was sent ahead
+    double pin_ms = 0, read_ms = 0, wait_ms = 0;   // (F2Q_TRACE) getting the slots, the reader busy, next() waiting for it
+
+    explicit PieceStream(f2q_ctx *ctx) : c(ctx) {}
+    ~PieceStream() { close(); }
+    uint8_t *text(const Piece &pc) const { return buf[pc.slot].p + head; }
+
+    template <class Fill> int start(size_t head_room, size_t slot_bytes, bool stage, Fill fill)
+    {
+        head = head_room; can_stage = stage; force_stage = getenv("F2Q_FORCE_STAGING") != nullptr;
+        const double p0 = now_ms();
+        for (auto &b : buf) if (!g_pinned.acquire(slot_bytes, b)) return fail(c, F2Q_ENOMEM, "cannot allocate the read buffers");
+        pin_ms = now_ms() - p0;
+        if (can_stage && !c->copy_stream) {
+            hipError_t e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming);
+            if (e != hipSuccess) return fail(c, F2Q_EHIP, std::string("copy stream: ") + hipGetErrorString(e));
+        }
+        reader = std::thread([this, fill]() {
+            for (uint64_t j = 0;; j++) {
+                const int slot = (int)(j % NSLOT);
+                { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return slot_free[slot] || stop; }); if (stop) return; slot_free[slot] = false; }
+                Piece pc; pc.slot = slot;
+                const double r0 = now_ms();
+                fill(j, buf[slot].p + head, pc);
+                read_ms += now_ms() - r0;
+                { std::lock_guard<std::mutex> g(mu); ready.push_back(pc); }
+                cv.notify_all();
+                if (pc.last) return;
+            }
+        });
+        return F2Q_OK;
+    }
+
+    Piece next()
+    {
+        Piece pc;
+        { const double w0 = now_ms(); std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !ready.empty(); }); pc = ready.front(); ready.pop_front(); wait_ms += now_ms() - w0; }
+        if (staged.buf && staged.slot == pc.slot && staged.n == pc.n) {
+            cur = staged; staged = Staged();
+            if (hipStreamWaitEvent(c->stream, c->ev_copy, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->copy_stream); }
+        } else free_staged(c, staged, c->copy_stream);
+        if (!pc.last) stage_next();                // the piece after this one, if the reader has it already
+        return pc;
+    }
+
+    // the caller is done with the piece (a staged copy it left in `cur` was not used); with stop_now no more are read
+    void done(const Piece &pc, bool stop_now)
+    {
+        free_staged(c, cur, c->stream);
+        { std::lock_guard<std::mutex> g(mu); slot_free[pc.slot] = true; if (stop_now) stop = true; }
+        cv.notify_all();
+    }
+
+    void close()
+    {
+        free_staged(c, cur, c->stream);
+        free_staged(c, staged, c->copy_stream);
+        { std::lock_guard<std::mutex> g(mu); stop = true; }
+        cv.notify_all();
+        if (reader.joinable()) reader.join();
+        for (auto &b : buf) g_pinned.release(b);
+    }
+
+  private:
+    void stage_next()
+    {
+        if (!can_stage || staged.buf) return;
+        Piece nx;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            if (force_stage) cv.wait(lk, [&] { return !ready.empty(); });      // tests: every piece takes this path
+            if (!ready.empty()) nx = ready.front();
+        }
+        if (nx.slot < 0 || nx.n == 0 || !nx.ok) return;
+        const size_t cap = head + nx.n + 2 * (size_t)F2Q_NL_CHUNK + 64;
+        if (dev_get(c, cap, &staged.buf) != F2Q_OK) { staged = Staged(); return; }   // no memory for it: the piece takes the ordinary path
+        staged.cap = cap; staged.slot = nx.slot; staged.n = nx.n;
+        if (hipMemcpyAsync((uint8_t *)staged.buf + head, buf[nx.slot].p + head, nx.n, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
+            hipEventRecord(c->ev_copy, c->copy_stream) != hipSuccess) {
+            (void)hipGetLastError();
+            free_staged(c, staged, c->copy_stream);
+        }
+    }
+};
+
+// Count text that was sent ahead.  It starts `off` bytes into the staged buffer, where the tail_n host bytes at `tail`
+// (a carried tail) are first put on c->stream in front of the staged bytes; n bytes in all, the last one last_byte.
+// The up to 15 bytes between the 16-byte boundary below the text and the text are filled with 'x': they lengthen the
+// first line, a record's header line, which is never looked at (fast2q.py:324-328 takes lines 2 and 4 only).  Unless
+// that fails, the buffer belongs to the block from here on; *used counts from the start of the text.
+static int count_staged(f2q_ctx *c, Staged &st, size_t off, const uint8_t *tail, size_t tail_n, size_t n, uint8_t last_byte,
+                        uint64_t max_records, size_t *used, f2q_timing *one)
+{
+    const size_t al = off & ~(size_t)15, lead = off - al;
+    uint8_t *d = (uint8_t *)st.buf;
+    hipError_t e = hipSuccess;
+    if (tail_n) e = hipMemcpyAsync(d + off, tail, tail_n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && lead) e = hipMemsetAsync(d + al, 'x', lead, c->stream);
+    if (e != hipSuccess) return fail(c, F2Q_EHIP, hipGetErrorString(e));
+    DevText pre; pre.buf = st.buf; pre.cap = st.cap; pre.text = d + al; pre.last_byte = last_byte;
+    st = Staged();
+    size_t used_dev = 0;
+    const int rc = count_window(c, nullptr, lead + n, &pre, &used_dev, one, max_records);
+    *used = used_dev > lead ? used_dev - lead : 0;
+    return rc;
+}
 
 // reads_counter's file half (fast2q.py:560-578).  A reader thread (f2q_reader.h: parallel pread / parallel BGZF
 // inflate / gzread) fills one pinned buffer while the device frames, packs and counts the other; whole lines only
@@ -1606,96 +1744,28 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
     const size_t HEAD = 64 << 10;                  // room in front of each piece for the carried tail
     if (src.kind == TextSource::PLAIN && src.regular) CH = std::min<size_t>(CH, std::max<size_t>(src.file_size, 4096));
     else if (src.regular) CH = std::min<size_t>(CH, std::max<size_t>(src.file_size * 16, (size_t)4 << 20));
-    const double tr_a = now_ms();
-    // three staging buffers: one being counted, one ready (its text already travelling to the device), one being read
-    constexpr int NSLOT = 3;
-    PinBuf buf[NSLOT];
-    auto drop = [&]() { for (auto &b : buf) g_pinned.release(b); };
-    for (auto &b : buf) if (!g_pinned.acquire(HEAD + CH, b)) { drop(); return fail(c, F2Q_ENOMEM, "cannot allocate the read buffers"); }
-    const double tr_b = now_ms();
-
-    // the second stream is made before the reader thread exists: no early return may leave a joinable thread behind
-    const bool can_stage = world == 1 && !c->host_pack && !getenv("F2Q_NO_STAGING");
-    const bool force_stage = getenv("F2Q_FORCE_STAGING") != nullptr;
-    if (can_stage && !c->copy_stream) {
-        hipError_t e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming);
-        if (e != hipSuccess) { drop(); return fail(c, F2Q_EHIP, std::string("copy stream: ") + hipGetErrorString(e)); }
-    }
-
-    struct Piece { int slot; size_t n; };
-    std::mutex mu; std::condition_variable cv;
-    std::deque<Piece> ready; bool slot_free[NSLOT]; for (bool &f : slot_free) f = true; bool stop = false;
-    double read_ms = 0;
-    std::thread reader([&]() {
-        for (int slot = 0;; slot = (slot + 1) % NSLOT) {
-            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return slot_free[slot] || stop; }); if (stop) return; slot_free[slot] = false; }
-            const double r0 = now_ms();
-            const size_t n = src.read(buf[slot].p + HEAD, CH);
-            read_ms += now_ms() - r0;
-            { std::lock_guard<std::mutex> g(mu); ready.push_back(Piece{slot, n}); }
-            cv.notify_all();
-            if (n == 0) return;
-        }
-    });
-
-    // The text of piece k+1 is copied to the device (second stream) while piece k is framed, packed and counted.  Its
-    // carried tail is only known once piece k is framed, so the piece lands HEAD bytes into its device buffer and the
-    // tail is put in front of it later; the text then starts wherever HEAD - tail falls, and the up to 15 bytes between
-    // the 16-byte boundary below it and the text are filled with 'x': they lengthen the first line, which is a record's
-    // header line and is never looked at (fast2q.py:324-328 takes lines 2 and 4 only).
-    struct Staged { void *buf = nullptr; size_t cap = 0; int slot = -1; size_t n = 0; } staged;
-    auto unstage = [&]() {                         // give up a staged copy (after it has landed)
-        if (!staged.buf) return;
-        (void)hipStreamSynchronize(c->copy_stream);
-        std::vector<void *> v{staged.buf}; free_all(c, v);
-        staged = Staged();
-    };
-    auto stage_next = [&]() {
-        if (!can_stage || staged.buf) return;
-        Piece nx{-1, 0};
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            if (force_stage) cv.wait(lk, [&] { return !ready.empty(); });      // tests: every piece takes this path
-            if (!ready.empty()) nx = ready.front();
-        }
-        if (nx.slot < 0 || nx.n == 0) return;
-        void *d = nullptr;
-        const size_t cap = HEAD + nx.n + 2 * (size_t)F2Q_NL_CHUNK + 64;
-        if (dev_get(c, cap, &d) != F2Q_OK) return;     // no memory for it: the piece takes the ordinary path
-        if (hipMemcpyAsync((uint8_t *)d + HEAD, buf[nx.slot].p + HEAD, nx.n, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
-            hipEventRecord(c->ev_copy, c->copy_stream) != hipSuccess) {
-            (void)hipGetLastError(); (void)hipStreamSynchronize(c->copy_stream);
-            std::vector<void *> v{d}; free_all(c, v);
-            return;
-        }
-        staged.buf = d; staged.cap = cap; staged.slot = nx.slot; staged.n = nx.n;
-    };
-
+    // The text of piece k+1 is copied to the device while piece k is framed, packed and counted.  Its carried tail is
+    // only known once piece k is framed, so the piece lands HEAD bytes into its device buffer and the tail is put in
+    // front of it later (count_staged).
+    PieceStream ps(c);
+    int rc = ps.start(HEAD, HEAD + CH, world == 1 && !c->host_pack && !getenv("F2Q_NO_STAGING"),
+                      [&](uint64_t, uint8_t *p, Piece &pc) { pc.n = src.read(p, CH); pc.last = pc.n == 0; });
+    if (rc) return rc;
     f2q_timing sum; memset(&sum, 0, sizeof sum);
-    int rc = F2Q_OK;
     std::vector<uint8_t> carry, big;
-    double wait_ms = 0;
     uint32_t piece_no = 0;                         // pieces are dealt to the ranks round robin
     for (;;) {
-        Piece pc;
-        { const double w0 = now_ms(); std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !ready.empty(); }); pc = ready.front(); ready.pop_front(); wait_ms += now_ms() - w0; }
-        const bool eof = (pc.n == 0);
-        Staged mine;                               // this piece's text, if it was sent ahead
-        if (staged.buf && staged.slot == pc.slot && staged.n == pc.n) {
-            mine = staged; staged = Staged();
-            if (hipStreamWaitEvent(c->stream, c->ev_copy, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->copy_stream); }
-        } else unstage();
-        if (!eof) stage_next();                    // the piece after this one, if the reader has it already (after the end marker nothing follows)
+        const Piece pc = ps.next();
+        const bool eof = pc.last;
         uint8_t *base; size_t have;
         if (carry.size() <= HEAD) {
-            base = buf[pc.slot].p + HEAD - carry.size();
+            base = ps.text(pc) - carry.size();
             if (!carry.empty()) memcpy(base, carry.data(), carry.size());
             have = carry.size() + pc.n;
         } else {                                   // a tail longer than the head room (very long lines): pageable detour
             big.resize(carry.size() + pc.n);
             memcpy(big.data(), carry.data(), carry.size());
-            if (pc.n) memcpy(big.data() + carry.size(), buf[pc.slot].p + HEAD, pc.n);
+            if (pc.n) memcpy(big.data() + carry.size(), ps.text(pc), pc.n);
             base = big.data(); have = big.size();
         }
         size_t used = 0;
@@ -1705,21 +1775,9 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
             // (at the end of a damaged archive too: readline raised there instead of returning the cut-off line, :405-407)
             if (!eof || src.truncated()) while (cut > 0 && base[cut - 1] != 0x0a) cut--;
             if (cut) {
-                if (mine.buf && carry.size() <= HEAD) {
-                    const size_t c_len = carry.size(), textoff = HEAD - c_len, al = textoff & ~(size_t)15, lead = textoff - al;
-                    uint8_t *d = (uint8_t *)mine.buf;
-                    hipError_t e = hipSuccess;
-                    if (c_len) e = hipMemcpyAsync(d + textoff, carry.data(), c_len, hipMemcpyHostToDevice, c->stream);
-                    if (e == hipSuccess && lead) e = hipMemsetAsync(d + al, 'x', lead, c->stream);
-                    if (e != hipSuccess) { rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); (void)hipStreamSynchronize(c->stream); std::vector<void *> v{mine.buf}; free_all(c, v); }
-                    else {
-                        DevText pre; pre.buf = mine.buf; pre.cap = mine.cap; pre.text = d + al; pre.last_byte = base[cut - 1];
-                        size_t used_dev = 0;
-                        rc = count_window(c, nullptr, lead + cut, &pre, &used_dev, &one);      // the buffer now belongs to the block
-                        used = used_dev > lead ? used_dev - lead : 0;
-                    }
-                    mine = Staged();
-                } else if (piece_no % world == rank) rc = f2q_count_block(c, base, cut, &used, &one);
+                if (ps.cur.buf && carry.size() <= HEAD)
+                    rc = count_staged(c, ps.cur, HEAD - carry.size(), carry.data(), carry.size(), cut, base[cut - 1], ~0ull, &used, &one);
+                else if (piece_no % world == rank) rc = f2q_count_block(c, base, cut, &used, &one);
                 else {                             // another rank's piece: only its framing matters here
                     uint64_t n_rec = 0;
                     used = skip_piece(base, cut, src.n_threads, &n_rec);
@@ -1727,22 +1785,17 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
                 }
                 piece_no++;
             }
-            if (mine.buf) { (void)hipStreamSynchronize(c->stream); std::vector<void *> v{mine.buf}; free_all(c, v); mine = Staged(); }   // not used after all
             if (eof) used = have;                  // trailing partial record is dropped (:392)
-            sum.kernel_ms += one.kernel_ms; sum.total_ms += one.total_ms; sum.reads += one.reads;
-            sum.fast_reads += one.fast_reads; sum.general_reads += one.general_reads; sum.launches += one.launches; if (one.path) sum.path = one.path;
+            timing_add(sum, one);
         }
         if (!rc) { std::vector<uint8_t> rest(base + used, base + have); carry.swap(rest); }
-        { std::lock_guard<std::mutex> g(mu); slot_free[pc.slot] = true; if (rc || eof) stop = true; }
-        cv.notify_all();
+        ps.done(pc, rc || eof);
         if (rc || eof) break;
     }
-    unstage();
-    reader.join();
-    drop();
+    ps.close();
     if (t) *t = sum;
     if (c->trace) fprintf(stderr, "[f2q trace] %s (%s, %d io threads): pinned %.1f ms, reader busy %.1f ms, waited for reader %.1f ms, frame+pack %.1f ms (H2D copy %.1f), count %.1f ms, free %.1f ms\n",
-                          path, src.kind_name(), src.n_threads, tr_b - tr_a, read_ms, wait_ms, c->tr_frame, c->tr_copy, c->tr_count, c->tr_free);
+                          path, src.kind_name(), src.n_threads, ps.pin_ms, ps.read_ms, ps.wait_ms, c->tr_frame, c->tr_copy, c->tr_count, c->tr_free);
     if (rc) return rc;
     if (src.truncated()) return fail(c, F2Q_ETRUNCATED, std::string(path) + " is an incomplete or corrupted gzip file");
     return F2Q_OK;
@@ -1917,132 +1970,62 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
         }
     }
     const size_t HEAD = 64, MARGIN = (size_t)1 << 20;       // a record that starts in the piece ends within the margin behind it
-    constexpr int NSLOT = 3;
-    PinBuf buf[NSLOT];
-    auto drop = [&]() { for (auto &b : buf) g_pinned.release(b); };
-    const size_t cap = HEAD + (size_t)std::max<uint64_t>(pm.max_text, 4096) + MARGIN + (pm.bgzf ? (size_t)1 << 16 : 0);
-    for (auto &b : buf) if (!g_pinned.acquire(cap, b)) { drop(); return fail(c, F2Q_ENOMEM, "cannot allocate the read buffers"); }
-    const bool can_stage = !c->host_pack && !getenv("F2Q_NO_STAGING");
-    if (can_stage && !c->copy_stream) {
-        hipError_t e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming);
-        if (e != hipSuccess) { drop(); return fail(c, F2Q_EHIP, std::string("copy stream: ") + hipGetErrorString(e)); }
-    }
-    struct Piece { int slot; size_t n, a; uint64_t max_rec, first_read; bool ok; };
-    std::mutex mu; std::condition_variable cv;
-    std::deque<Piece> ready; bool slot_free[NSLOT]; for (bool &f : slot_free) f = true; bool stop = false;
-    std::thread reader([&]() {
-        int slot = 0;
-        for (size_t j = 0; j <= jobs.size(); j++, slot = (slot + 1) % NSLOT) {
-            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return slot_free[slot] || stop; }); if (stop) return; slot_free[slot] = false; }
-            Piece pc{slot, 0, 0, 0, 0, true};
-            if (j < jobs.size()) {
-                const Job &jb = jobs[j];
-                PieceSpan sp = piece_span(src.file_size, piece_bytes, jb.k);
-                uint64_t want = std::min<uint64_t>(sp.size + MARGIN, src.file_size - sp.base);
-                uint8_t *p = buf[slot].p + HEAD;
-                size_t n = 0;
-                if (!pm.bgzf) { n = src.read_at(sp.base, p, (size_t)want); pc.ok = n == want; }
-                else {
-                    // the run of members, then members behind it until the last record is whole (4 newlines) or the margin is full
-                    sp.base = 0; sp.size = pm.text[jb.k];
-                    pc.ok = src.seek_bgzf(pm.c_off[jb.k]);
-                    while (pc.ok && n < sp.size) { const size_t g = src.read(p + n, (size_t)(sp.size - n)); if (!g) pc.ok = false; n += g; }
-                    size_t seen = 0, o = n;
-                    bool more = true;
-                    while (pc.ok && more && seen < 4 && n < sp.size + MARGIN) {
-                        const size_t g = src.read(p + n, (size_t)std::min<uint64_t>((uint64_t)1 << 16, sp.size + MARGIN - n));
-                        if (!g) { more = false; if (src.truncated()) pc.ok = false; break; }
-                        n += g;
-                        while (seen < 4 && o < n) { const uint8_t *q = (const uint8_t *)memchr(p + o, 0x0a, n - o); if (!q) { o = n; break; } o = (size_t)(q - p) + 1; seen++; }
-                    }
-                    // (for the check below: "the file goes on behind what was read" <=> the margin filled up without 4 newlines)
-                    want = n; sp.base = 0;
-                    const bool file_goes_on = more && seen < 4;
-                    if (file_goes_on) pc.ok = false;
-                }
-                // the first record start: the line after the one cut by the piece's start, then `skip_lines` more
-                size_t a = 0;
-                uint64_t skip = jb.skip_lines + (jb.at_line_start ? 0 : 1);
-                while (skip && a < n) { const uint8_t *q = (const uint8_t *)memchr(p + a, 0x0a, n - a); if (!q) { a = n; break; } a = (size_t)(q - p) + 1; skip--; }
-                // the margin must hold the rest of the last record (4 more newlines, or the end of the file)
-                if (!pm.bgzf && sp.base + want < src.file_size) {
-                    size_t seen = 0, o = (size_t)sp.size;
-                    while (seen < 4 && o < n) { const uint8_t *q = (const uint8_t *)memchr(p + o, 0x0a, n - o); if (!q) break; o = (size_t)(q - p) + 1; seen++; }
-                    if (seen < 4) pc.ok = false;           // lines too long for the margin: the caller falls back
-                }
-                pc.n = n; pc.a = a; pc.max_rec = jb.n_records; pc.first_read = jb.first_read;
+    PieceStream ps(c);
+    const size_t slot_bytes = HEAD + (size_t)std::max<uint64_t>(pm.max_text, 4096) + MARGIN + (pm.bgzf ? (size_t)1 << 16 : 0);
+    int rc = ps.start(HEAD, slot_bytes, !c->host_pack && !getenv("F2Q_NO_STAGING"), [&](uint64_t j, uint8_t *p, Piece &pc) {
+        if (j == jobs.size()) { pc.last = true; return; }
+        const Job &jb = jobs[j];
+        PieceSpan sp = piece_span(src.file_size, piece_bytes, jb.k);
+        uint64_t want = std::min<uint64_t>(sp.size + MARGIN, src.file_size - sp.base);
+        size_t n = 0;
+        if (!pm.bgzf) { n = src.read_at(sp.base, p, (size_t)want); pc.ok = n == want; }
+        else {
+            // the run of members, then members behind it until the last record is whole (4 newlines) or the margin is full
+            sp.base = 0; sp.size = pm.text[jb.k];
+            pc.ok = src.seek_bgzf(pm.c_off[jb.k]);
+            while (pc.ok && n < sp.size) { const size_t g = src.read(p + n, (size_t)(sp.size - n)); if (!g) pc.ok = false; n += g; }
+            size_t seen = 0, o = n;
+            bool more = true;
+            while (pc.ok && more && seen < 4 && n < sp.size + MARGIN) {
+                const size_t g = src.read(p + n, (size_t)std::min<uint64_t>((uint64_t)1 << 16, sp.size + MARGIN - n));
+                if (!g) { more = false; if (src.truncated()) pc.ok = false; break; }
+                n += g;
+                while (seen < 4 && o < n) { const uint8_t *q = (const uint8_t *)memchr(p + o, 0x0a, n - o); if (!q) { o = n; break; } o = (size_t)(q - p) + 1; seen++; }
             }
-            { std::lock_guard<std::mutex> g(mu); ready.push_back(pc); }
-            cv.notify_all();
+            // (for the check below: "the file goes on behind what was read" <=> the margin filled up without 4 newlines)
+            want = n; sp.base = 0;
+            const bool file_goes_on = more && seen < 4;
+            if (file_goes_on) pc.ok = false;
         }
+        // the first record start: the line after the one cut by the piece's start, then `skip_lines` more
+        size_t a = 0;
+        uint64_t skip = jb.skip_lines + (jb.at_line_start ? 0 : 1);
+        while (skip && a < n) { const uint8_t *q = (const uint8_t *)memchr(p + a, 0x0a, n - a); if (!q) { a = n; break; } a = (size_t)(q - p) + 1; skip--; }
+        // the margin must hold the rest of the last record (4 more newlines, or the end of the file)
+        if (!pm.bgzf && sp.base + want < src.file_size) {
+            size_t seen = 0, o = (size_t)sp.size;
+            while (seen < 4 && o < n) { const uint8_t *q = (const uint8_t *)memchr(p + o, 0x0a, n - o); if (!q) break; o = (size_t)(q - p) + 1; seen++; }
+            if (seen < 4) pc.ok = false;           // lines too long for the margin: the caller falls back
+        }
+        pc.n = n; pc.a = a; pc.max_records = jb.n_records; pc.first_read = jb.first_read;
     });
-    struct Staged { void *buf = nullptr; size_t cap = 0; int slot = -1; size_t n = 0; } staged;
-    auto unstage = [&]() {
-        if (!staged.buf) return;
-        (void)hipStreamSynchronize(c->copy_stream);
-        std::vector<void *> v{staged.buf}; free_all(c, v);
-        staged = Staged();
-    };
-    auto stage_next = [&]() {
-        if (!can_stage || staged.buf) return;
-        Piece nx{-1, 0, 0, 0, 0, true};
-        { std::unique_lock<std::mutex> lk(mu); if (!ready.empty()) nx = ready.front(); }
-        if (nx.slot < 0 || nx.n == 0 || !nx.ok) return;
-        void *d = nullptr;
-        const size_t dcap = HEAD + nx.n + 2 * (size_t)F2Q_NL_CHUNK + 64;
-        if (dev_get(c, dcap, &d) != F2Q_OK) return;
-        if (hipMemcpyAsync((uint8_t *)d + HEAD, buf[nx.slot].p + HEAD, nx.n, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
-            hipEventRecord(c->ev_copy, c->copy_stream) != hipSuccess) {
-            (void)hipGetLastError(); (void)hipStreamSynchronize(c->copy_stream);
-            std::vector<void *> v{d}; free_all(c, v);
-            return;
-        }
-        staged.buf = d; staged.cap = dcap; staged.slot = nx.slot; staged.n = nx.n;
-    };
+    if (rc) return rc;
     f2q_timing sum; memset(&sum, 0, sizeof sum);
-    int rc = F2Q_OK;
-    for (size_t j = 0; j <= jobs.size(); j++) {
-        Piece pc;
-        { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !ready.empty(); }); pc = ready.front(); ready.pop_front(); }
-        Staged mine;
-        if (staged.buf && staged.slot == pc.slot && staged.n == pc.n) {
-            mine = staged; staged = Staged();
-            if (hipStreamWaitEvent(c->stream, c->ev_copy, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->copy_stream); }
-        } else unstage();
-        if (j < jobs.size()) stage_next();
+    for (;;) {
+        const Piece pc = ps.next();
         if (!pc.ok) rc = fail(c, F2Q_EUNSUPPORTED, "a line longer than the piece margin (or a short read): count this file unsharded");
-        if (!rc && j < jobs.size() && pc.n > pc.a) {
+        if (!rc && !pc.last && pc.n > pc.a) {
             f2q_timing one; memset(&one, 0, sizeof one);
             size_t used = 0;
             c->reads_seen = pc.first_read;
-            uint8_t *base = buf[pc.slot].p + HEAD + pc.a;
-            if (mine.buf) {
-                // the text starts `a` bytes into the staged copy; the bytes between the 16-byte boundary below it and the
-                // text lengthen the first line, a header line, which is never looked at (fast2q.py:324-328)
-                const size_t textoff = HEAD + pc.a, al = textoff & ~(size_t)15, lead = textoff - al;
-                uint8_t *d = (uint8_t *)mine.buf;
-                hipError_t e = lead ? hipMemsetAsync(d + al, 'x', lead, c->stream) : hipSuccess;
-                if (e != hipSuccess) { rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
-                else {
-                    DevText pre; pre.buf = mine.buf; pre.cap = mine.cap; pre.text = d + al; pre.last_byte = base[pc.n - pc.a - 1];
-                    rc = count_window(c, nullptr, lead + (pc.n - pc.a), &pre, &used, &one, pc.max_rec);   // the buffer now belongs to the block
-                    mine = Staged();
-                }
-            } else rc = count_window(c, base, pc.n - pc.a, nullptr, &used, &one, pc.max_rec);
-            sum.kernel_ms += one.kernel_ms; sum.total_ms += one.total_ms; sum.reads += one.reads;
-            sum.fast_reads += one.fast_reads; sum.general_reads += one.general_reads; sum.launches += one.launches; if (one.path) sum.path = one.path;
+            uint8_t *base = ps.text(pc) + pc.a;
+            if (ps.cur.buf) rc = count_staged(c, ps.cur, HEAD + pc.a, nullptr, 0, pc.n - pc.a, base[pc.n - pc.a - 1], pc.max_records, &used, &one);
+            else rc = count_window(c, base, pc.n - pc.a, nullptr, &used, &one, pc.max_records);
+            timing_add(sum, one);
         }
-        if (mine.buf) { (void)hipStreamSynchronize(c->stream); std::vector<void *> v{mine.buf}; free_all(c, v); }
-        { std::lock_guard<std::mutex> g(mu); slot_free[pc.slot] = true; if (rc) stop = true; }
-        cv.notify_all();
-        if (rc) break;
+        ps.done(pc, rc || pc.last);
+        if (rc || pc.last) break;
     }
-    unstage();
-    { std::lock_guard<std::mutex> g(mu); stop = true; }
-    cv.notify_all();
-    reader.join();
-    drop();
     if (t) *t = sum;
     return rc;
 }

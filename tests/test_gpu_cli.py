@@ -142,11 +142,16 @@ def test_count_file_shard_sums_to_the_whole(tmp_path, monkeypatch, kind, world):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world,piece,block", [(2, 1 << 16, 20000), (3, 200000, 0xFF00), (4, 4096, 3000), (1, 1 << 20, 0xFF00)])
-def test_count_pieces_of_a_bgzf_file(tmp_path, world, piece, block):
+# (explicit ids: the as_it_comes cases keep the ids they had before the staging parameter)
+@pytest.mark.parametrize("world,piece,block,staging", [
+    pytest.param(w, p, b, s, id=f"{w}-{p}-{b}" + ("" if s == "as_it_comes" else f"-{s}"))
+    for w, p, b, s in [(2, 1 << 16, 20000, "as_it_comes"), (3, 200000, 0xFF00, "as_it_comes"), (4, 4096, 3000, "as_it_comes"),
+                       (1, 1 << 20, 0xFF00, "as_it_comes"), (2, 1 << 16, 20000, "every_piece"), (1, 1 << 20, 0xFF00, "every_piece")]])
+def test_count_pieces_of_a_bgzf_file(tmp_path, monkeypatch, world, piece, block, staging):
     """the same protocol on a BGZF file: a piece is a run of whole members (their text sizes come from the trailers), each
     rank inflates only its own runs -- once for the census, once to count -- plus the members behind a run that finish its
     last record.  Empty members inside the file, a partial last record, ordinary gzip refused."""
+    if staging == "every_piece": monkeypatch.setenv("F2Q_FORCE_STAGING", "1")
     sharding = importlib.import_module("2fast2q_amd.sharding")
     guides = synth.make_library(150, 20, 5)
     fq = sprinkle_symbols(synth.make_fastq(synth.Spec(seed=34, n_reads=7000, read_len=101), guides), 3, rate=0.004)
@@ -187,13 +192,19 @@ def test_count_pieces_of_a_bgzf_file(tmp_path, world, piece, block):
         assert c.file_pieces(str(mixed), piece) == (0, False)
 
 
-@pytest.mark.parametrize("world", [1, 2, 3, 5])
-@pytest.mark.parametrize("piece", [4096, 50000, 1 << 20])
-def test_count_pieces_without_foreign_bytes(tmp_path, world, piece):
+# (explicit ids: the as_it_comes cases keep the ids they had before the staging parameter)
+@pytest.mark.parametrize("world,piece,staging", [
+    pytest.param(w, p, s, id=f"{p}-{w}" + ("" if s == "as_it_comes" else f"-{s}"))
+    for p in (4096, 50000, 1 << 20) for w in (1, 2, 3, 5) for s in ("as_it_comes", "every_piece", "never")])
+def test_count_pieces_without_foreign_bytes(tmp_path, monkeypatch, world, piece, staging):
     """f2q_file_pieces / f2q_census_pieces / f2q_count_pieces: every rank counts the newlines of its own pieces, the
     census vectors are summed (here: in this process; in a run: one all-reduce), and each rank frames and counts the
     records that start in its pieces.  The rank results add up to the oracle's on a file with CRLF lines, lines that
     straddle pieces, a partial last record -- for Counter mode and for Extract+Count (keys merged by first read)."""
+    # the text of the next piece may travel to the device ahead of time: forced on, its first record start lands at
+    # every alignment in the staged copy; "never" is the plain path
+    if staging == "every_piece": monkeypatch.setenv("F2Q_FORCE_STAGING", "1")
+    if staging == "never": monkeypatch.setenv("F2Q_NO_STAGING", "1")
     sharding = importlib.import_module("2fast2q_amd.sharding")
     guides = synth.make_library(150, 20, 5)
     fq = sprinkle_symbols(synth.make_fastq(synth.Spec(seed=33, n_reads=9000, read_len=101), guides), 3, rate=0.004)
