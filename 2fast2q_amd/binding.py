@@ -19,7 +19,7 @@ EXPORTS = (
     "f2q_count_file", "f2q_count_file_shard", "f2q_file_pieces", "f2q_census_pieces", "f2q_count_pieces", "f2q_synth_create", "f2q_block_from_fastq", "f2q_count_resident", "f2q_count_resident_queued", "f2q_queued_times", "f2q_block_info",
     "f2q_block_free", "f2q_synth_fastq", "f2q_synth_library", "f2q_reset_counts", "f2q_read_counts",
     "f2q_counts_device_ptr", "f2q_stream", "f2q_ec_size", "f2q_ec_fetch", "f2q_set_read_base", "f2q_synth_guides",
-    "f2q_text_upload", "f2q_count_text", "f2q_text_free",
+    "f2q_text_upload", "f2q_count_text", "f2q_text_free", "f2q_text_from_bgzf", "f2q_text_read",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
@@ -138,6 +138,8 @@ def load(path=None):
     L.f2q_text_upload.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
     L.f2q_count_text.argtypes = [vp, vp, C.POINTER(C.c_size_t), C.POINTER(Timing)]
     L.f2q_text_free.argtypes = [vp, vp]; L.f2q_text_free.restype = None
+    L.f2q_text_from_bgzf.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
+    L.f2q_text_read.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.f2q_count_file_shard.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(Timing)]
     L.f2q_file_pieces.argtypes = [C.c_char_p, C.c_uint64, u64p, C.POINTER(C.c_int)]
     L.f2q_census_pieces.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, u64p, C.c_uint64]
@@ -189,6 +191,14 @@ class DeviceText:
         if self._h:
             self._c._L.f2q_text_free(self._c._h, self._h)
             self._h = None
+
+    def read(self):
+        """the text's bytes, copied back to the host"""
+        n = C.c_size_t(0)
+        self._c._check(self._c._L.f2q_text_read(self._c._h, self._h, None, 0, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        self._c._check(self._c._L.f2q_text_read(self._c._h, self._h, C.cast(buf, C.c_void_p), n.value, C.byref(n)))
+        return buf.raw[:n.value]
 
 
 class Block:
@@ -289,6 +299,17 @@ class Counter:
         h = C.c_void_p()
         self._check(self._L.f2q_text_upload(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data), C.byref(h)))
         return DeviceText(self, h)
+
+    def text_from_bgzf(self, data):
+        """inflate an in-memory BGZF buffer on the device -> (DeviceText, truncated); truncated: a member is damaged and
+        the text holds the members before it"""
+        data = bytes(data)
+        h = C.c_void_p()
+        rc = self._L.f2q_text_from_bgzf(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data), C.byref(h))
+        if rc == F2Q_ETRUNCATED and h.value:
+            return DeviceText(self, h), True
+        self._check(rc)
+        return DeviceText(self, h), False
 
     def count_text(self, text, want_timing=False):
         """frame, pack and count FASTQ text that already sits in device memory; returns bytes consumed (and timing)"""

@@ -28,6 +28,7 @@ using namespace f2q;
 #include "f2q_count_kernels.h"
 #include "f2q_part_kernels.h"
 #include "f2q_aux_kernels.h"
+#include "f2q_inflate_kernels.h"
 
 // ===============================================================================================
 // host side
@@ -1511,6 +1512,103 @@ extern "C" void f2q_text_free(f2q_ctx *c, f2q_text *t)
     delete t;
 }
 
+extern "C" int f2q_text_read(f2q_ctx *c, const f2q_text *t, uint8_t *dst, size_t cap, size_t *nbytes)
+{
+    if (!c || !t || !nbytes) return F2Q_EINVAL;
+    *nbytes = t->nbytes;
+    if (!dst) return F2Q_OK;
+    if (cap < t->nbytes) return fail(c, F2Q_EINVAL, "f2q_text_read: the buffer is smaller than the text");
+    HIPC(c, hipSetDevice(c->device));
+    if (t->nbytes) HIPC(c, hipMemcpyAsync(dst, t->buf, t->nbytes, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return F2Q_OK;
+}
+
+// ---- BGZF members inflated on the device (k_inflate_bgzf) ----------------------------------------------------------
+// the member table of n members whose compressed bytes lie in d_in (in_cap bytes, table included if it is there):
+// inflate into d_text (text_cap bytes) on c->stream and bring the n result words back.  The first member whose status
+// is not OK is *first_bad (n: none).
+static int inflate_members(f2q_ctx *c, const uint8_t *d_in, uint64_t in_cap, const BgzfMember *d_mem, uint32_t n, uint8_t *d_text,
+                           uint64_t text_cap, std::vector<BgzfResult> &res, uint32_t *first_bad)
+{
+    res.assign(n, BgzfResult{});
+    *first_bad = n;
+    if (n == 0) return F2Q_OK;
+    std::vector<void *> tmp;
+    BgzfResult *d_res;
+    int rc = dev_alloc(c, n, &d_res, tmp, 0xFF);
+    if (rc) return rc;
+    // LDS holds two workgroups per CU; each walks its share of the members
+    const uint32_t grid = std::min<uint32_t>(n, (uint32_t)c->n_cu * 2u);
+    hipLaunchKernelGGL(k_inflate_bgzf, dim3(grid), dim3(64), 0, c->stream, d_in, in_cap, d_mem, n, d_text, text_cap, d_res);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_res, (size_t)n * sizeof(BgzfResult), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    free_all(c, tmp);
+    if (e != hipSuccess) return fail(c, F2Q_EHIP, std::string("k_inflate_bgzf: ") + hipGetErrorString(e));
+    for (uint32_t i = 0; i < n; i++) if (res[i].status != F2Q_INF_OK) { *first_bad = i; break; }
+    return F2Q_OK;
+}
+
+// offset of the first byte after the last '\n' of members [0, n) (0: none), and the last byte of their text
+static void members_tail(const std::vector<BgzfMember> &ms, const std::vector<BgzfResult> &res, uint32_t n, uint64_t &cut, int &last_byte)
+{
+    cut = 0; last_byte = -1;
+    for (uint32_t i = n; i-- > 0;) {
+        if (last_byte < 0 && ms[i].isize) last_byte = (int)res[i].last_byte;
+        if (res[i].last_nl) { cut = ms[i].out_off + res[i].last_nl; break; }
+    }
+    for (uint32_t i = n; last_byte < 0 && i-- > 0;) if (ms[i].isize) last_byte = (int)res[i].last_byte;
+}
+
+extern "C" int f2q_text_from_bgzf(f2q_ctx *c, const uint8_t *bgzf, size_t nbytes, f2q_text **out)
+{
+    if (!c || !out || (!bgzf && nbytes)) return F2Q_EINVAL;
+    *out = nullptr;
+    // the member table (a damaged header ends it: the members before it are what the text holds)
+    std::vector<BgzfMember> ms;
+    uint64_t text = 0;
+    bool bad = false;
+    for (size_t pos = 0; pos < nbytes;) {
+        uint32_t bsize, hdr;
+        if (!TextSource::bgzf_member(bgzf + pos, nbytes - pos, bsize, hdr) || bsize > nbytes - pos)
+            return fail(c, F2Q_EUNSUPPORTED, "f2q_text_from_bgzf: the buffer is not a run of whole BGZF members");
+        if (bsize < hdr + 8) { bad = true; break; }
+        const uint8_t *t = bgzf + pos + bsize - 8;
+        BgzfMember m{};
+        m.in_off = pos + hdr; m.in_len = bsize - hdr - 8; m.out_off = (uint32_t)text;
+        m.crc = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
+        m.isize = t[4] | (t[5] << 8) | (t[6] << 16) | ((uint32_t)t[7] << 24);
+        if (m.isize > F2Q_INF_OUT_BYTES) return fail(c, F2Q_EUNSUPPORTED, "f2q_text_from_bgzf: a member holds more than 64 KiB of text");
+        text += m.isize;
+        if (text > ((uint64_t)1 << 30)) return fail(c, F2Q_EINVAL, "f2q_text_from_bgzf: at most 1 GiB of text (the device framing indexes a text with 32 bits)");
+        ms.push_back(m);
+        pos += bsize;
+    }
+    HIPC(c, hipSetDevice(c->device));
+    std::vector<void *> tmp;
+    uint8_t *d_in; BgzfMember *d_mem;
+    int rc = dev_alloc(c, nbytes + 64, &d_in, tmp);
+    if (!rc) rc = dev_upload(c, ms.data(), ms.size(), &d_mem, tmp);
+    if (!rc && nbytes) { hipError_t e = hipMemcpyAsync(d_in, bgzf, nbytes, hipMemcpyHostToDevice, c->stream); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
+    f2q_text *t = new f2q_text();
+    const size_t n_chunks = ((size_t)text + F2Q_NL_CHUNK - 1) / F2Q_NL_CHUNK;
+    t->cap = n_chunks * F2Q_NL_CHUNK + 16;
+    if (!rc) { hipError_t e = hipMalloc(&t->buf, t->cap); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    std::vector<BgzfResult> res;
+    uint32_t fb = 0;
+    if (!rc) rc = inflate_members(c, d_in, nbytes + 64, d_mem, (uint32_t)ms.size(), (uint8_t *)t->buf, text, res, &fb);
+    free_all(c, tmp);
+    if (rc) { if (t->buf) (void)hipFree(t->buf); delete t; return rc; }
+    t->nbytes = fb < ms.size() ? ms[fb].out_off : text;
+    uint64_t cut; int lb;
+    members_tail(ms, res, fb, cut, lb);
+    t->last = lb < 0 ? 0 : (uint8_t)lb;
+    *out = t;
+    if (bad || fb < ms.size()) return fail(c, F2Q_ETRUNCATED, "f2q_text_from_bgzf: a damaged member; the text ends before it");
+    return F2Q_OK;
+}
+
 // ---- file streaming -------------------------------------------------------------------------------
 // Page-locked staging buffers are expensive to create (tens of ms per 256 MiB) and every file needs two, so
 // they are kept in a small process-wide pool between files (and between contexts: --cp runs several at once).
@@ -1733,6 +1831,161 @@ static size_t skip_piece(const uint8_t *p, size_t n, int threads, uint64_t *n_re
     return n;
 }
 
+// Count `n` bytes of text that start `off` bytes into the device buffer buf (cap bytes); the caller keeps the buffer.
+// As in count_staged, the bytes between the 16-byte boundary below the text and the text become 'x'.
+static int count_dev_text(f2q_ctx *c, uint8_t *buf, size_t cap, size_t off, size_t n, uint8_t last_byte, size_t *used, f2q_timing *one)
+{
+    const size_t al = off & ~(size_t)15, lead = off - al;
+    if (lead) HIPC(c, hipMemsetAsync(buf + al, 'x', lead, c->stream));
+    DevText pre; pre.buf = buf; pre.cap = cap; pre.text = buf + al; pre.last_byte = last_byte; pre.borrowed = true;
+    size_t used_dev = 0;
+    const int rc = count_window(c, nullptr, lead + n, &pre, &used_dev, one);
+    *used = used_dev > lead ? used_dev - lead : 0;
+    return rc;
+}
+
+// f2q_count_file on a BGZF file with F2Q_DEVICE_INFLATE=1 (count_file_impl decides).  Pieces are runs of whole members
+// with at most CH bytes of text, as piece_map cuts them; the reader thread only preads each run's compressed bytes into
+// a pinned slot behind its member table, and PieceStream sends both to the device ahead.  k_inflate_bgzf writes the
+// text behind the head room of a device text buffer; the carried tail (the partial record piece k leaves over) is
+// copied device to device in front of it, the head room growing for a tail longer than 64 KiB.  The members before the
+// first damaged one are counted, whole lines only, and nothing after it (read_bgzf's verdict).
+static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, const std::vector<uint64_t> &off, const std::vector<uint32_t> &isz,
+                             size_t CH, f2q_timing *t)
+{
+    const size_t HEAD = 64 << 10, MAX_WINDOW = (size_t)1 << 30;
+    CH = std::min<size_t>(CH, (size_t)512 << 20);
+    // the pieces: text <= CH, member table + compressed bytes <= PB (a run of empty members takes little text)
+    const size_t PB = std::max<size_t>(CH, (size_t)1 << 20);
+    struct Run { size_t m0, m1; uint64_t text, bytes; };
+    std::vector<Run> runs;
+    for (size_t i = 0; i < off.size(); i++) {
+        const uint64_t bs = (i + 1 < off.size() ? off[i + 1] : src.file_size) - off[i];
+        if (runs.empty() || runs.back().text + isz[i] > CH || runs.back().bytes + bs + sizeof(BgzfMember) * (runs.back().m1 - runs.back().m0 + 1) + 16 > PB)
+            runs.push_back(Run{i, i, 0, 0});
+        Run &r = runs.back();
+        r.m1 = i + 1; r.text += isz[i]; r.bytes += bs;
+    }
+    // what the reader leaves for each slot: the member table (also at the head of the slot) and a damaged header
+    struct SlotInfo { std::vector<BgzfMember> ms; uint64_t text = 0; bool bad = false, io = false; };
+    SlotInfo info[PieceStream::NSLOT];
+    auto fill = [&](uint64_t j, uint8_t *p, Piece &pc) {
+        if (j >= runs.size()) { pc.last = true; return; }
+        const Run &r = runs[j];
+        SlotInfo &si = info[pc.slot];
+        si = SlotInfo();
+        const size_t nm = r.m1 - r.m0, T = (nm * sizeof(BgzfMember) + 15) & ~(size_t)15;
+        uint8_t *z = p + T;
+        // the run's compressed bytes, in slices of at least 4 MiB read by up to F2Q_IO_THREADS threads
+        const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)src.n_threads, r.bytes / ((size_t)4 << 20)));
+        std::atomic<bool> short_read{false};
+        auto slice = [&](int k) {
+            const size_t a = r.bytes * (size_t)k / (size_t)nt, b = r.bytes * (size_t)(k + 1) / (size_t)nt;
+            for (size_t o = a; o < b;) { ssize_t g = pread(src.fd, z + o, b - o, (off_t)(off[r.m0] + o)); if (g <= 0) { short_read = true; return; } o += (size_t)g; }
+        };
+        std::vector<std::thread> th;
+        for (int k = 1; k < nt; k++) th.emplace_back(slice, k);
+        slice(0);
+        for (auto &x : th) x.join();
+        if (short_read) { si.io = true; pc.n = 0; return; }
+        for (size_t i = r.m0; i < r.m1; i++) {
+            const size_t at = (size_t)(off[i] - off[r.m0]);
+            const uint32_t want = (uint32_t)((i + 1 < off.size() ? off[i + 1] : src.file_size) - off[i]);
+            uint32_t bsize = 0, hdr = 0;
+            if (!TextSource::bgzf_member(z + at, r.bytes - at, bsize, hdr) || bsize != want || bsize < hdr + 8) { si.bad = true; break; }
+            const uint8_t *tl = z + at + bsize - 8;
+            BgzfMember m{};
+            m.in_off = T + at + hdr; m.in_len = bsize - hdr - 8; m.out_off = (uint32_t)si.text;
+            m.crc = tl[0] | (tl[1] << 8) | (tl[2] << 16) | ((uint32_t)tl[3] << 24);
+            m.isize = isz[i];
+            si.ms.push_back(m); si.text += m.isize;
+        }
+        if (!si.ms.empty()) memcpy(p, si.ms.data(), si.ms.size() * sizeof(BgzfMember));
+        pc.n = T + r.bytes;
+    };
+    PieceStream ps(c);
+    int rc = ps.start(0, PB + 64, !getenv("F2Q_NO_STAGING"), fill);
+    if (rc) return rc;
+    f2q_timing sum; memset(&sum, 0, sizeof sum);
+    double inflate_ms = 0;
+    uint8_t *prev = nullptr; size_t prev_cap = 0;   // the text buffer of the last piece; its tail [carry_at, carry_at + carry_n) is carried
+    size_t carry_at = 0, carry_n = 0;
+    uint8_t carry_last = 0;
+    bool truncated = false;
+    std::vector<void *> hold;                        // prev, for free_all
+    auto release_prev = [&]() { if (prev) { hold.assign(1, prev); free_all(c, hold); prev = nullptr; } };
+    for (;;) {
+        const Piece pc = ps.next();
+        f2q_timing one; memset(&one, 0, sizeof one);
+        if (pc.last) {                               // the last partial record, counted in place (:392)
+            size_t used = 0;
+            if (carry_n) rc = count_dev_text(c, prev, prev_cap, carry_at, carry_n, carry_last, &used, &one);
+            timing_add(sum, one);
+            ps.done(pc, true);
+            break;
+        }
+        const SlotInfo &si = info[pc.slot];
+        if (si.io) { rc = fail(c, F2Q_EIO, std::string("short read of ") + path); ps.done(pc, true); break; }
+        const uint32_t nm = (uint32_t)si.ms.size();
+        const size_t hr = std::max(HEAD, (carry_n + 15) & ~(size_t)15);
+        const size_t cap = hr + (size_t)si.text + 2 * (size_t)F2Q_NL_CHUNK + 64;
+        if (carry_n + si.text > MAX_WINDOW - (size_t)F2Q_NL_CHUNK) { rc = fail(c, F2Q_EINVAL, std::string(path) + ": a line longer than the device window"); ps.done(pc, true); break; }
+        const double i0 = now_ms();
+        void *tb = nullptr, *zb = nullptr;
+        rc = dev_get(c, cap, &tb);
+        std::vector<void *> scratch;
+        const uint8_t *d_in = (const uint8_t *)ps.cur.buf;
+        uint64_t in_cap = ps.cur.cap;
+        if (!rc && !d_in) {                          // not sent ahead: copy it now
+            rc = dev_get(c, pc.n + 64, &zb);
+            if (!rc) { scratch.push_back(zb); d_in = (const uint8_t *)zb; in_cap = pc.n + 64; }
+            if (!rc) { hipError_t e = hipMemcpyAsync(zb, ps.text(pc), pc.n, hipMemcpyHostToDevice, c->stream); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
+        }
+        if (!rc && carry_n) {
+            hipError_t e = hipMemcpyAsync((uint8_t *)tb + hr - carry_n, prev + carry_at, carry_n, hipMemcpyDeviceToDevice, c->stream);
+            if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e));
+        }
+        std::vector<BgzfResult> res;
+        uint32_t fb = nm;
+        if (!rc) rc = inflate_members(c, d_in, in_cap, (const BgzfMember *)d_in, nm, (uint8_t *)tb + hr, si.text, res, &fb);
+        free_all(c, scratch);
+        inflate_ms += now_ms() - i0;
+        release_prev();
+        if (tb) { prev = (uint8_t *)tb; prev_cap = cap; }
+        if (rc) { ps.done(pc, true); break; }
+        const bool bad = si.bad || fb < nm;
+        const uint64_t text_n = fb < nm ? si.ms[fb].out_off : si.text;
+        uint64_t nl; int lb;
+        members_tail(si.ms, res, fb, nl, lb);
+        if (lb >= 0) carry_last = (uint8_t)lb;
+        const size_t start = hr - carry_n, have = carry_n + (size_t)text_n;
+        size_t used = 0;
+        if (nl) {                                    // whole lines only: a line is never split between blocks
+            // the framing zeroes the bytes behind the window: the partial line there is kept aside and put back
+            const size_t cut = carry_n + (size_t)nl, rest = have - cut;
+            void *aside = nullptr;
+            if (rest) rc = dev_get(c, rest, &aside);
+            if (!rc && rest) { hipError_t e = hipMemcpyAsync(aside, prev + start + cut, rest, hipMemcpyDeviceToDevice, c->stream); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
+            if (!rc) rc = count_dev_text(c, prev, prev_cap, start, cut, 0x0a, &used, &one);
+            if (!rc && rest) { hipError_t e = hipMemcpyAsync(prev + start + cut, aside, rest, hipMemcpyDeviceToDevice, c->stream); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
+            if (aside) { hold.assign(1, aside); free_all(c, hold); }
+            timing_add(sum, one);
+        }
+        carry_at = start + used; carry_n = have - used;
+        if (bad) truncated = true;
+        ps.done(pc, rc || bad);
+        if (rc || bad) break;
+    }
+    ps.close();
+    release_prev();
+    if (t) *t = sum;
+    if (c->trace) fprintf(stderr, "[f2q trace] %s (bgzf-device, %d io threads): pinned %.1f ms, reader busy %.1f ms, waited for reader %.1f ms, inflate %.1f ms, frame+pack %.1f ms (H2D copy %.1f), count %.1f ms, free %.1f ms\n",
+                          path, src.n_threads, ps.pin_ms, ps.read_ms, ps.wait_ms, inflate_ms, c->tr_frame, c->tr_copy, c->tr_count, c->tr_free);
+    if (rc) return rc;
+    if (truncated) return fail(c, F2Q_ETRUNCATED, std::string(path) + " is an incomplete or corrupted gzip file");
+    return F2Q_OK;
+}
+
 static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t world, f2q_timing *t)
 {
     if (!c || !path || world == 0 || rank >= world) return F2Q_EINVAL;
@@ -1744,6 +1997,13 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
     const size_t HEAD = 64 << 10;                  // room in front of each piece for the carried tail
     if (src.kind == TextSource::PLAIN && src.regular) CH = std::min<size_t>(CH, std::max<size_t>(src.file_size, 4096));
     else if (src.regular) CH = std::min<size_t>(CH, std::max<size_t>(src.file_size * 16, (size_t)4 << 20));
+    // F2Q_DEVICE_INFLATE=1: a BGZF file of members of at most 64 KiB of text each is inflated on the device
+    const char *dinf = getenv("F2Q_DEVICE_INFLATE");
+    if (dinf && dinf[0] == '1' && world == 1 && !getenv("F2Q_HOST_PACK") && src.kind == TextSource::BGZF && src.regular) {
+        std::vector<uint64_t> off; std::vector<uint32_t> isz;
+        if (src.bgzf_index(off, isz) && std::all_of(isz.begin(), isz.end(), [](uint32_t s) { return s <= F2Q_INF_OUT_BYTES; }))
+            return count_bgzf_device(c, path, src, off, isz, CH, t);
+    }
     // The text of piece k+1 is copied to the device while piece k is framed, packed and counted.  Its carried tail is
     // only known once piece k is framed, so the piece lands HEAD bytes into its device buffer and the tail is put in
     // front of it later (count_staged).

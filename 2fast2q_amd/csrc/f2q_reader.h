@@ -160,6 +160,16 @@ struct TextSource {
     {
         off.clear(); isz.clear();
         if (kind != BGZF || !regular) return false;
+        if (bmap) {                                         // mapped: only the pages of the headers and trailers are touched
+            for (size_t pos = 0; pos < bmap_len;) {
+                uint32_t bsize;
+                if (!bgzf_header(bmap + pos, bmap_len - pos, bsize) || bsize > bmap_len - pos || pos + bsize < 4) return false;
+                const uint8_t *t = bmap + pos + bsize - 4;
+                off.push_back(pos); isz.push_back(t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24));
+                pos += bsize;
+            }
+            return true;
+        }
         const size_t CH = (size_t)8 << 20;
         std::vector<uint8_t> b(CH + 65536 + 64);
         uint64_t pos = 0;                                   // compressed offset of the next member
@@ -180,6 +190,13 @@ struct TextSource {
             if (o == 0) return false;
             pos += o;
         }
+        return true;
+    }
+    // a BGZF member header at h (avail bytes): bsize = the whole member's bytes, hdr = the header bytes before the deflate payload
+    static bool bgzf_member(const uint8_t *h, size_t avail, uint32_t &bsize, uint32_t &hdr)
+    {
+        if (!bgzf_header(h, avail, bsize)) return false;
+        hdr = 12u + (h[10] | ((uint32_t)h[11] << 8));
         return true;
     }
 

@@ -147,11 +147,21 @@ typedef struct f2q_text f2q_text;
 int f2q_text_upload(f2q_ctx *ctx, const uint8_t *fastq, size_t nbytes, f2q_text **out);
 int f2q_count_text(f2q_ctx *ctx, f2q_text *text, size_t *consumed, f2q_timing *t);
 void f2q_text_free(f2q_ctx *ctx, f2q_text *text);
+/* An in-memory BGZF buffer (bgzip / BCL Convert output) inflated on the device into a device-resident text that
+ * f2q_count_text counts: one workgroup per member (k_inflate_bgzf), CRC-32 and ISIZE checked as gzip does.  Replaces
+ * the reference's gzip.open + line iteration (fast2q.py:566-578) for such a buffer.  F2Q_EUNSUPPORTED: the buffer is not
+ * a run of whole BGZF members of at most 64 KiB of text each; F2Q_EINVAL: more than 1 GiB of text.  F2Q_ETRUNCATED: a
+ * member is damaged; *out is still set and holds the text of the members before it. */
+int f2q_text_from_bgzf(f2q_ctx *ctx, const uint8_t *bgzf, size_t nbytes, f2q_text **out);
+/* A device text back to the host: *nbytes = its size; with dst != NULL (cap >= *nbytes) the bytes too. */
+int f2q_text_read(f2q_ctx *ctx, const f2q_text *text, uint8_t *dst, size_t cap, size_t *nbytes);
 /* reads_counter's file half (fast2q.py:560-578): plain or .gz FASTQ by path (gzip by content; blocked gzip --
  * BGZF -- is inflated member-parallel).  The file is streamed in pieces by a reader thread while the device
  * frames, packs and counts.  F2Q_ETRUNCATED: the archive is cut off or damaged; every complete line before the damage has
  * been counted, as the reference does (its parser keeps what it counted when readline raises, fast2q.py:405-407, and
- * reads_counter returns those partial counts with a warning; the cut-off last line is never seen).  The harness too. */
+ * reads_counter returns those partial counts with a warning; the cut-off last line is never seen).  The harness too.
+ * F2Q_DEVICE_INFLATE=1 (off by default): a BGZF regular file whose members each hold at most 64 KiB of text is inflated
+ * on the device (k_inflate_bgzf), only its compressed bytes cross PCIe; same counts, same verdict on damage. */
 int f2q_count_file(f2q_ctx *ctx, const char *path, f2q_timing *t);
 /* The same file counted by `world` processes, one per GPU (replaces the chunk pool of
  * single_file_reads_binner, fast2q.py:447-512): every rank streams the whole file -- the 4-line framing is
