@@ -20,11 +20,13 @@ EXPORTS = (
     "f2q_block_free", "f2q_synth_fastq", "f2q_synth_library", "f2q_reset_counts", "f2q_read_counts",
     "f2q_counts_device_ptr", "f2q_stream", "f2q_ec_size", "f2q_ec_fetch", "f2q_set_read_base", "f2q_synth_guides",
     "f2q_text_upload", "f2q_count_text", "f2q_text_free", "f2q_text_from_bgzf", "f2q_text_read",
+    "f2q_set_mate2", "f2q_count_block_paired", "f2q_block_from_fastq_paired", "f2q_count_file_paired",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
-          -8: "EUNSUPPORTED"}
+          -8: "EUNSUPPORTED", -9: "EPAIRING"}
 F2Q_ETRUNCATED = -6
+F2Q_EPAIRING = -9
 
 
 class F2QError(RuntimeError):
@@ -144,6 +146,10 @@ def load(path=None):
     L.f2q_file_pieces.argtypes = [C.c_char_p, C.c_uint64, u64p, C.POINTER(C.c_int)]
     L.f2q_census_pieces.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, u64p, C.c_uint64]
     L.f2q_count_pieces.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, u64p, C.c_uint64, C.POINTER(Timing)]
+    L.f2q_set_mate2.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.c_int32]
+    L.f2q_count_block_paired.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(Timing)]
+    L.f2q_block_from_fastq_paired.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
+    L.f2q_count_file_paired.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(Timing)]
     L.f2q_synth_create.argtypes = [vp, C.POINTER(Synth), C.POINTER(vp)]
     L.f2q_block_from_fastq.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
     L.f2q_count_resident.argtypes = [vp, vp, C.POINTER(Timing)]
@@ -229,9 +235,12 @@ class Counter:
 
     ``features``: ordered list of sequences as features_loader leaves them
     (upper-case, blanks removed, unique); row i of the count vector is feature i.
+
+    ``start2`` ("b[,b...]" or a list) makes it a paired context (f2q_set_mate2): ``start`` names the windows in mate 1,
+    ``start2`` those in mate 2, ``rc2`` takes mate 2 reverse-complemented; such a context counts with the *_paired calls.
     """
 
-    def __init__(self, features=None, lib_path=None, **params):
+    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -241,6 +250,9 @@ class Counter:
             raise F2QError(rc, (self._L.f2q_last_error(None) or b"").decode())
         self._h = h
         self.n_features = 0
+        self.paired = False
+        if start2 is not None:
+            self.set_mate2(start2, rc2)
         if features is not None:
             self.set_features(features)
 
@@ -275,6 +287,44 @@ class Counter:
         blob = b"".join(enc)
         self._check(self._L.f2q_set_features(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_uint32)), len(enc)))
         self.n_features = len(enc)
+
+    def set_mate2(self, start2, rc2=False):
+        """windows of mate 2 (paired-end samples); before set_features"""
+        st = [int(x) for x in (start2 if isinstance(start2, (list, tuple)) else str(start2).split(","))]
+        arr = (C.c_int32 * max(len(st), 1))(*st)
+        self._check(self._L.f2q_set_mate2(self._h, arr, len(st), 1 if rc2 else 0))
+        self.paired = True
+
+    # -- counting: paired-end --
+    @staticmethod
+    def _ptr(data):
+        data = data if isinstance(data, bytes) else bytes(data)
+        return data, C.cast(C.c_char_p(data), C.c_void_p)
+
+    def count_block_paired(self, data1, data2, want_timing=False):
+        """fastq_parser over two FASTQ buffers in lockstep; returns (bytes consumed of each) (and timing)"""
+        d1, p1 = self._ptr(data1)
+        d2, p2 = self._ptr(data2)
+        u1, u2, t = C.c_size_t(0), C.c_size_t(0), Timing()
+        self._check(self._L.f2q_count_block_paired(self._h, p1, len(d1), p2, len(d2), C.byref(u1), C.byref(u2), C.byref(t)))
+        return ((u1.value, u2.value), t.as_dict()) if want_timing else (u1.value, u2.value)
+
+    def block_from_fastq_paired(self, data1, data2):
+        d1, p1 = self._ptr(data1)
+        d2, p2 = self._ptr(data2)
+        h = C.c_void_p()
+        self._check(self._L.f2q_block_from_fastq_paired(self._h, p1, len(d1), p2, len(d2), C.byref(h)))
+        return Block(self, h)
+
+    def count_file_paired(self, path1, path2):
+        """Counts the two files of a paired sample.  Returns (timing dict, truncated flag); F2QError with code
+        F2Q_EPAIRING when one file holds records beyond the other's last (the common pairs are counted)."""
+        t = Timing()
+        rc = self._L.f2q_count_file_paired(self._h, os.fsencode(path1), os.fsencode(path2), C.byref(t))
+        if rc == F2Q_ETRUNCATED:
+            return t.as_dict(), True
+        self._check(rc)
+        return t.as_dict(), False
 
     # -- counting --
     def count_block(self, data, want_timing=False):

@@ -1867,6 +1867,7 @@ struct RawBlock {
     const unsigned long long *off;         // offset of the sequence line
     const unsigned long long *qoff;        // offset of the quality line, or nullptr: it follows the sequence
     const uint32_t *len, *qlen, *index;    // index: position inside the block (nullptr: == record id)
+    const uint32_t *len1, *qlen1;          // paired-end blocks: the records are merged pairs, mate 1's share of len / qlen (else nullptr)
 };
 
 // One read per lane, byte-exact routine.  The routine walks the record byte by byte with dependent loads, so each lane
@@ -1886,6 +1887,8 @@ __device__ __forceinline__ void stage_line(uint32_t *dst, gbytes raw, unsigned l
     uint8_t *db = reinterpret_cast<uint8_t *>(dst);
     for (uint32_t k = 4u * full; k < mis + (uint32_t)n; k++) db[k] = raw[off - mis + k];      // <= 3 bytes, never past the line
 }
+// PAIRED: the records are merged pairs (RawBlock::len1 / qlen1 set); the single-end instantiation never looks at them
+template <bool PAIRED>
 __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_general(const RunDev *__restrict__ runp,
                                                                     const LibDev *__restrict__ libp, EcDev ec, RawBlock rb,
                                                                     Accum acc)
@@ -1902,15 +1905,16 @@ __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_general(const RunDev 
         const int r = (int)gp(rb.len)[i], qn = (int)gp(rb.qlen)[i];
         const unsigned long long qo = rb.qoff ? gp(rb.qoff)[i] : so + (unsigned long long)r;
         const unsigned long long gi = rb.first_index + (rb.index ? gp(rb.index)[i] : i);
+        const int r1 = PAIRED ? (int)gp(rb.len1)[i] : 0, qn1 = PAIRED ? (int)gp(rb.qlen1)[i] : 0;
         const uint32_t ms = (uint32_t)so & 3u, mq = (uint32_t)qo & 3u;
         if (r >= 0 && qn >= 0 && ms + (uint32_t)r <= 4u * F2Q_GEN_WORDS && mq + (uint32_t)qn <= 4u * F2Q_GEN_WORDS) {
             stage_line(mine, raw, so, r);
             stage_line(mine + F2Q_GEN_WORDS, raw, qo, qn);
             const uint8_t *sl = reinterpret_cast<const uint8_t *>(mine) + ms;
             const uint8_t *ql = reinterpret_cast<const uint8_t *>(mine + F2Q_GEN_WORDS) + mq;
-            general_read<const uint8_t *, true>(run, lib, ec, acc, sl, r, ql, qn, gi, st, &n_new);
+            general_read<const uint8_t *, true, PAIRED>(run, lib, ec, acc, sl, r, ql, qn, gi, st, &n_new, r1, qn1);
         } else {
-            general_read<gbytes, true>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, &n_new);
+            general_read<gbytes, true, PAIRED>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, &n_new, r1, qn1);
         }
     }
     if (run.mode == 1) ec64_report_new(ec, n_new);

@@ -65,7 +65,8 @@ struct RunDev {
     uint64_t up_codes, down_codes;     // symbol j = (codes >> 2j) & 3  -- one scalar load, no per-symbol memory access
     uint32_t up_pos[4], down_pos[4];   // per symbol c: bit j set iff anchor symbol j == c
     // several --us/--ds pairs, every anchor ACGT-only and 1..32 long: the same masks per pair (k_count_anchor_pairs)
-    int32_t pairs_packed, pad2_;
+    int32_t pairs_packed;
+    int32_t n_mate1;                   // paired-end runs (f2q_set_mate2): windows [0, n_mate1) lie in mate 1, the others in mate 2; 0: single-end
     uint32_t mp_up_pos[F2Q_DEV_MAX_ITER][4], mp_down_pos[F2Q_DEV_MAX_ITER][4];
 };
 
@@ -930,10 +931,13 @@ F2Q_HD void ec_count_key(const EcDev &ec, const KV &kv, unsigned long long read_
 // general path: one read given as raw bytes.  st[] = the 5 reference counters (thread-local).
 // ---------------------------------------------------------------------------------------------
 // WORDS: see gk_exact (true where this routine is the main road: k_count_general, the host twin)
-template <class P, bool WORDS = false>
+// PAIRED: the record is a merged pair, seq = mate 1 (r1 bytes) then mate 2 as the run takes it, qual likewise (qn1 bytes
+// of mate 1 first); a fixed window is sliced inside its own mate, so it clips at the end of THAT mate (:354 per mate)
+template <class P, bool WORDS = false, bool PAIRED = false>
 F2Q_HD void general_read(const RunDev &run, const LibDev &lib, const EcDev &ec, const Accum &acc,
                          P seq, int r, P qual, int qn,
-                         unsigned long long read_index, unsigned long long st[5], uint32_t *n_new = nullptr)
+                         unsigned long long read_index, unsigned long long st[5], uint32_t *n_new = nullptr,
+                         int r1 = 0, int qn1 = 0)
 {
     KeyViewT<P> kv; kv.seq = seq; kv.nseg = 0; kv.len = 0;
     bool all_failed = true;
@@ -945,8 +949,15 @@ F2Q_HD void general_read(const RunDev &run, const LibDev &lib, const EcDev &ec, 
             if (end < start) continue;                                           // :343-345
         }
         int a, b, qa, qb;
+        if (PAIRED) {
+            const bool m2 = i >= run.n_mate1;
+            py_slice(m2 ? r - r1 : r1, start, end, a, b);
+            py_slice(m2 ? qn - qn1 : qn1, start, end, qa, qb);
+            if (m2) { a += r1; b += r1; qa += qn1; qb += qn1; }
+        } else {
         py_slice(r, start, end, a, b);                                           // :354
         py_slice(qn, start, end, qa, qb);                                        // :355
+        }
         if (qual_range_fails(qual, qa, qb, run.thr)) continue;                   // :357-360
         all_failed = false;
         kv.a[kv.nseg] = a; kv.b[kv.nseg] = b; kv.nseg++;
@@ -2033,6 +2044,10 @@ struct PackPlan {
     // window of n_win * win_len bases; need = n_win * win_len, from = 0.  A read that ends inside a window is not packed.
     int n_win = 0, win_len = 0, win_end = 0;       // win_end: every window lies inside [0, win_end) of the read
     int win_start[F2Q_MW_MAX] = {0, 0, 0, 0};
+    // paired-end runs: windows [0, n_win1) are taken from mate 1 (win_end bounds them), the others from mate 2 (win_end2),
+    // which is read from its end and complemented when rc2 is set.  Single-end: n_win1 == n_win, nothing comes from a mate 2.
+    bool rc2 = false;
+    int n_win1 = 0, win_end2 = 0;
     bool inband_n = false;         // non-ACGT symbols travel as flag bits (all-ACGT library only)
     bool n_only = false;           // ... but only the symbol 'N' (Extract+Count: the key spells the symbol, a flag reads 'N'; fixed windows: 'n' too, upper-cased)
     bool fast_anchor = false;      // --us/--ds with ACGT anchors: packed bit-plane path
@@ -2042,15 +2057,57 @@ struct PackPlan {
 
 template <class P>
 struct RecT { P seq; P qual; uint32_t len, qlen; };
-// read position of stored position s (fixed-offset tiles)
-F2Q_HD uint32_t pack_src(const PackPlan &pl, uint32_t s) { return pl.n_win ? (uint32_t)pl.win_start[s / (uint32_t)pl.win_len] + s % (uint32_t)pl.win_len : s; }
+// read position of stored position s (fixed-offset tiles); F2Q_SRC_MATE2 set: a position in mate 2
+#define F2Q_SRC_MATE2 0x80000000u
+F2Q_HD uint32_t pack_src(const PackPlan &pl, uint32_t s)
+{
+    if (!pl.n_win) return s;
+    const uint32_t w = s / (uint32_t)pl.win_len;
+    return ((uint32_t)pl.win_start[w] + s % (uint32_t)pl.win_len) | (w >= (uint32_t)pl.n_win1 ? F2Q_SRC_MATE2 : 0u);
+}
 
-// Can this read go through a packed fast path?  The planes cannot carry a quality line of another length or
+// A pair of mates behind the same two members: seq[at] / qual[at] take a pack_src position.  Mate 2 is seen as the run
+// takes it: with `rev` from its end, with `comp` (the sequence line) complemented byte by byte.
+F2Q_HD uint8_t comp8(uint8_t c)
+{
+    switch (c) {
+        case 'A': return 'T'; case 'T': return 'A'; case 'C': return 'G'; case 'G': return 'C';
+        case 'a': return 't'; case 't': return 'a'; case 'c': return 'g'; case 'g': return 'c';
+        default: return c;
+    }
+}
+template <class P>
+struct MateBytes {
+    P m1, m2; uint32_t n2; bool rev, comp;
+    F2Q_HD uint8_t operator[](uint32_t at) const
+    {
+        if (!(at & F2Q_SRC_MATE2)) return m1[at];
+        const uint32_t p = at & ~F2Q_SRC_MATE2;
+        const uint8_t c = m2[rev ? n2 - 1u - p : p];
+        return comp ? comp8(c) : c;
+    }
+};
+template <class P>
+struct PairRecT { MateBytes<P> seq, qual; uint32_t len, qlen, len2, qlen2; };      // len / qlen: mate 1
+template <class P>
+F2Q_HD PairRecT<P> pair_rec(bool rc2, P s1, P q1, uint32_t len1, uint32_t qlen1, P s2, P q2, uint32_t len2, uint32_t qlen2)
+{
+    PairRecT<P> r;
+    r.seq.m1 = s1; r.seq.m2 = s2; r.seq.n2 = len2; r.seq.rev = rc2; r.seq.comp = rc2;
+    r.qual.m1 = q1; r.qual.m2 = q2; r.qual.n2 = qlen2; r.qual.rev = rc2; r.qual.comp = false;
+    r.len = len1; r.qlen = qlen1; r.len2 = len2; r.qlen2 = qlen2;
+    return r;
+}
+// mate 2 of a pair: its quality line as long as its sequence, every window inside it
+template <class P> F2Q_HD bool mate2_fits(const PackPlan &, const RecT<P> &) { return true; }
+template <class P> F2Q_HD bool mate2_fits(const PackPlan &pl, const PairRecT<P> &r) { return r.qlen2 == r.len2 && r.len2 >= (uint32_t)pl.win_end2; }
+
+// Can this read (RecT) or pair (PairRecT) go through a packed fast path?  The planes cannot carry a quality line of another length or
 // quality bytes >= 128 (bit 7 is the flag bit and the Phred SWAR test relies on 7-bit bytes); non-ACGT symbols
 // only as flag bits (all-ACGT library); anchored runs carry lower-case bases as marked bases (F2Q_LEN_CASE), but not
 // next to non-ACGT symbols in the same read.
-template <class P>
-F2Q_HD bool read_is_clean(const PackPlan &pl, const RecT<P> &r)
+template <class R>
+F2Q_HD bool read_is_clean(const PackPlan &pl, const R &r)
 {
     if (pl.fast_anchor) {
         if (r.qlen != r.len || r.len > F2Q_ANCHOR_MAXLEN) return false;
@@ -2066,7 +2123,7 @@ F2Q_HD bool read_is_clean(const PackPlan &pl, const RecT<P> &r)
         return !(lower && odd);                            // one kind of mark per read: both kinds take the byte-exact routine
     }
     if (!pl.fast_fixed) return false;
-    if (r.qlen != r.len) return false;
+    if (r.qlen != r.len || !mate2_fits(pl, r)) return false;
     if (pl.n_win && r.len < (uint32_t)pl.win_end) return false;              // a window the read ends in: the byte-exact routine clips it
     const uint32_t b = pl.n_win ? (uint32_t)pl.need : (r.len < (uint32_t)pl.need ? r.len : (uint32_t)pl.need);
     uint32_t nmask = 0;
@@ -2085,8 +2142,8 @@ F2Q_HD bool read_is_clean(const PackPlan &pl, const RecT<P> &r)
 }
 
 // number of bases of the read that are stored
-template <class P>
-F2Q_HD uint32_t packed_len(const PackPlan &pl, const RecT<P> &r)
+template <class R>
+F2Q_HD uint32_t packed_len(const PackPlan &pl, const R &r)
 {
     return pl.fast_anchor ? r.len : pl.n_win ? (uint32_t)pl.need : (r.len < (uint32_t)pl.need ? r.len : (uint32_t)pl.need);
 }
@@ -2100,8 +2157,8 @@ F2Q_HD void tile_geometry(const PackPlan &pl, uint32_t rmax_in, uint32_t &rmax, 
 }
 
 // one clean read -> its words (sink.base(w, v), sink.qual(w, v), sink.len(v))
-template <class P, class Sink>
-F2Q_HD void pack_read(const PackPlan &pl, const RecT<P> &r, uint32_t planar_nw, Sink &sink)
+template <class R, class Sink>
+F2Q_HD void pack_read(const PackPlan &pl, const R &r, uint32_t planar_nw, Sink &sink)
 {
     const uint32_t l = packed_len(pl, r);
     const uint32_t from = pl.fast_anchor ? 0u : (uint32_t)pl.from;

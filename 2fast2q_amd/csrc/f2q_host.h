@@ -519,8 +519,17 @@ inline PackPlan make_plan(const RunDev &run)
             pl.n_win = run.n_iter; pl.win_len = run.length; pl.win_end = hi + run.length;       // only the windows are stored, back to back
             for (int i = 0; i < run.n_iter; i++) pl.win_start[i] = run.start[i];
             pl.from = 0; pl.need = run.n_iter * run.length;
+            pl.n_win1 = pl.n_win;
+            if (run.n_mate1 > 0) {                       // paired-end: each mate bounds its own windows
+                pl.n_win1 = run.n_mate1; pl.win_end = 0; pl.win_end2 = 0;
+                for (int i = 0; i < run.n_iter; i++) {
+                    int &e = i < run.n_mate1 ? pl.win_end : pl.win_end2;
+                    if (run.start[i] + run.length > e) e = run.start[i] + run.length;
+                }
+            }
         }
     }
+    // (rc2 is set by the owner of the plan: it is no run parameter of the kernels)
     pl.fast_anchor = !run.fixed && run.n_iter == 1 && run.anchors_packed && run.msu >= 0 && run.msd >= 0 &&
                      run.msu <= 7 && run.msd <= 7 && run.length >= 0 && run.length <= F2Q_ANCHOR_MAXLEN;
     // several pairs: every pair searched on the same planes, the parts joined with ':' (fast2q.py:333-363)
@@ -546,6 +555,7 @@ struct HostPacked {
     std::vector<uint8_t> raw;                  // seq bytes then qual bytes per record
     std::vector<unsigned long long> g_off;     // per record: offset of seq in raw (qual follows at +len)
     std::vector<uint32_t> g_len, g_qlen, g_index;
+    std::vector<uint32_t> g_len1, g_qlen1;     // paired-end: the record is a merged pair, these are mate 1's share of g_len / g_qlen
 };
 
 struct HostSink {
@@ -591,6 +601,59 @@ inline void pack_records(const PackPlan &pl, const std::vector<Rec> &recs, HostP
     }
 }
 
+// mate 2 as the run takes it: the line reversed, the sequence line complemented too (rc2), else as read
+inline void append_mate2(std::vector<uint8_t> &dst, const uint8_t *p, uint32_t n, bool rev, bool comp)
+{
+    if (!rev) { dst.insert(dst.end(), p, p + n); return; }
+    for (uint32_t k = 0; k < n; k++) { const uint8_t c = p[n - 1u - k]; dst.push_back(comp ? comp8(c) : c); }
+}
+
+// Paired-end twin of pack_records: record i of r1 pairs with record i of r2 (the shorter list decides).  A clean pair
+// becomes one slot of a compact tile, exactly the slot the merged read would get; every other pair becomes the merged
+// raw record mate 1 + mate 2 (sequence, then quality) with mate 1's lengths beside it (general_read<.., PAIRED>).
+inline void pack_pairs(const PackPlan &pl, const std::vector<Rec> &r1, const std::vector<Rec> &r2, HostPacked &hp)
+{
+    hp = HostPacked();
+    const size_t n = r1.size() < r2.size() ? r1.size() : r2.size();
+    auto rec_of = [&](size_t i) {
+        return pair_rec<const uint8_t *>(pl.rc2, r1[i].seq, r1[i].qual, r1[i].len, r1[i].qlen, r2[i].seq, r2[i].qual, r2[i].len, r2[i].qlen);
+    };
+    std::vector<uint32_t> clean; clean.reserve(n);
+    uint32_t rmax = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const PairRecT<const uint8_t *> r = rec_of(i);
+        if (read_is_clean(pl, r)) {
+            clean.push_back(i);
+            const uint32_t l = packed_len(pl, r);
+            if (l > rmax) rmax = l;
+        } else {
+            hp.g_off.push_back(hp.raw.size());
+            hp.g_len.push_back(r.len + r.len2); hp.g_qlen.push_back(r.qlen + r.qlen2); hp.g_index.push_back(i);
+            hp.g_len1.push_back(r.len); hp.g_qlen1.push_back(r.qlen);
+            hp.raw.insert(hp.raw.end(), r1[i].seq, r1[i].seq + r.len);
+            append_mate2(hp.raw, r2[i].seq, r.len2, pl.rc2, pl.rc2);
+            hp.raw.insert(hp.raw.end(), r1[i].qual, r1[i].qual + r.qlen);
+            append_mate2(hp.raw, r2[i].qual, r.qlen2, pl.rc2, false);
+        }
+    }
+    hp.raw.resize(hp.raw.size() + 8, 0);
+    hp.n_clean = clean.size();
+    if (clean.empty()) return;
+    hp.c_index.assign(((clean.size() + F2Q_TILE - 1) / F2Q_TILE) * F2Q_TILE, 0);
+    for (size_t s = 0; s < clean.size(); s++) hp.c_index[s] = clean[s];
+    tile_geometry(pl, rmax, hp.rmax, hp.planar_nw, hp.wb, hp.wq);
+    hp.n_tiles = (uint32_t)((clean.size() + F2Q_TILE - 1) / F2Q_TILE);
+    hp.bases.assign((size_t)hp.n_tiles * hp.wb * F2Q_TILE, 0);
+    hp.qual.assign((size_t)hp.n_tiles * hp.wq * F2Q_TILE, 0);
+    hp.len.assign((size_t)hp.n_tiles * F2Q_TILE, (uint16_t)F2Q_LEN_SKIP);
+    for (size_t s = 0; s < clean.size(); s++) {
+        const size_t tile = s / F2Q_TILE, lane = s % F2Q_TILE;
+        HostSink sink{hp.bases.data() + tile * hp.wb * F2Q_TILE + lane, hp.qual.data() + tile * hp.wq * F2Q_TILE + lane,
+                      hp.len.data() + tile * F2Q_TILE + lane};
+        pack_read(pl, rec_of(clean[s]), hp.planar_nw, sink);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // run set-up (reads_counter :536-558, initializer :1112-1129)
 // ---------------------------------------------------------------------------------------------
@@ -602,7 +665,8 @@ inline int phred_threshold(int ph)
 }
 
 // f2q_params -> RunDev; returns an F2Q_E* code and a message
-inline int fill_run(const f2q_params &p, RunDev &r, std::string &err)
+// n_mate1 > 0: a paired-end run, the first n_mate1 --st values are windows of mate 1, the others of mate 2 (f2q_set_mate2)
+inline int fill_run(const f2q_params &p, RunDev &r, std::string &err, int n_mate1 = 0)
 {
     memset(&r, 0, sizeof r);
     r.mode = p.mode; r.miss = p.miss < 0 ? 0 : p.miss; r.length = p.length;
@@ -610,7 +674,7 @@ inline int fill_run(const f2q_params &p, RunDev &r, std::string &err)
     r.msu = p.miss_search_up; r.msd = p.miss_search_down;
     if (p.n_upstream == 0 && p.n_downstream == 0) {               // fast2q.py:538-541
         if (p.n_start < 1 || p.n_start > F2Q_MAX_ITER) { err = "n_start must be 1..16"; return F2Q_EINVAL; }
-        r.fixed = 1; r.n_iter = p.n_start;
+        r.fixed = 1; r.n_iter = p.n_start; r.n_mate1 = n_mate1;
         for (int i = 0; i < p.n_start; i++) r.start[i] = p.start[i];
         r.compact = make_plan(r).multi ? 1 : 0;                   // the packed tiles of a multi-window run hold the windows only
         return F2Q_OK;

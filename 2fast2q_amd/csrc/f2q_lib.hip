@@ -28,6 +28,7 @@ using namespace f2q;
 #include "f2q_count_kernels.h"
 #include "f2q_part_kernels.h"
 #include "f2q_aux_kernels.h"
+#include "f2q_pair_kernels.h"
 #include "f2q_inflate_kernels.h"
 
 // ===============================================================================================
@@ -54,6 +55,8 @@ struct f2q_ctx {
     RunDev run_h{};
     RunDev *run_d = nullptr;
     PackPlan plan{};
+    int n_mate1 = 0;                     // f2q_set_mate2: a paired context, windows [0, n_mate1) of the run lie in mate 1
+    bool rc2 = false;                    // ... and mate 2 is taken reverse-complemented
     // library
     bool have_lib = false;
     HostIndex ix;
@@ -220,9 +223,10 @@ static int setup_run(f2q_ctx *c)
     for (int i = 0; i < p.n_upstream && i < F2Q_MAX_ITER; i++) p.upstream[i] = c->up_s[i].c_str();
     for (int i = 0; i < p.n_downstream && i < F2Q_MAX_ITER; i++) p.downstream[i] = c->down_s[i].c_str();
     std::string err;
-    int rc = fill_run(p, c->run_h, err);
+    int rc = fill_run(p, c->run_h, err, c->n_mate1);
     if (rc) return fail(c, rc, err);
     c->plan = make_plan(c->run_h);
+    c->plan.rc2 = c->rc2;
     if (c->force_general) { c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi_pair = false; }
     return F2Q_OK;
 }
@@ -399,6 +403,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     HIPC(c, hipSetDevice(c->device));
     for (uint32_t i = 0; i < n; i++) if (offs[i + 1] < offs[i]) return fail(c, F2Q_EINVAL, "offsets must be non-decreasing");
     c->plan = make_plan(c->run_h);                   // the library decides below whether the packed paths apply
+    c->plan.rc2 = c->rc2;
     if (c->force_general) { c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false; }
     int packed_len = c->plan.fast_fixed ? c->run_h.length : 0;
     if (c->plan.fast_anchor) {
@@ -912,7 +917,8 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
     rb.first_index += c->reads_seen;
     const uint64_t wg = (rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
-    hipLaunchKernelGGL(k_count_general, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
+    if (rb.len1) hipLaunchKernelGGL(k_count_general<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
+    else hipLaunchKernelGGL(k_count_general<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     HIPC(c, hipGetLastError());
     launches++;
     EC_POINT(c, "k_count_general");
@@ -952,7 +958,7 @@ static int launch_aux_general(f2q_ctx *c, const f2q_block *b, Accum &acc, uint32
     RawBlock rb = b->rb;
     rb.first_index += c->reads_seen;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS, (uint64_t)c->n_cu * 32u);
-    hipLaunchKernelGGL(k_count_general, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->aux_stream, c->run_d, c->lib_d, c->ec, rb, acc);
+    hipLaunchKernelGGL(k_count_general<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->aux_stream, c->run_d, c->lib_d, c->ec, rb, acc);
     HIPC(c, hipGetLastError());
     launches++;
     c->aux_busy = true;
@@ -1139,6 +1145,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
             v.n = std::min<uint64_t>(step, b->rb.n - r0);
             v.off += r0; v.len += r0; v.qlen += r0;
             if (v.qoff) v.qoff += r0;
+            if (v.len1) { v.len1 += r0; v.qlen1 += r0; }
             if (v.index) v.index += r0; else v.first_index += r0;
             // no key is longer than its record's bytes + separators (block-wide bound: the arena is never cleared)
             int rc = ec_reserve(c, v.n, v.n, b->raw_key_bytes + v.n * F2Q_MAX_ITER);
@@ -1250,12 +1257,11 @@ extern "C" int f2q_block_info(const f2q_block *b, uint64_t *n_reads, uint64_t *n
     return F2Q_OK;
 }
 
-static int block_from_records(f2q_ctx *c, const std::vector<Rec> &recs, f2q_block **out)
+// host-packed tiles and raw records -> a resident block of n_reads reads (or pairs)
+static int block_from_packed(f2q_ctx *c, const HostPacked &hp, uint64_t n_reads, f2q_block **out)
 {
-    HostPacked hp;
-    pack_records(c->plan, recs, hp);
     f2q_block *b = new f2q_block();
-    b->n_reads = recs.size(); b->n_general = hp.g_len.size();
+    b->n_reads = n_reads; b->n_general = hp.g_len.size();
     int rc = F2Q_OK;
     do {
         if (hp.n_tiles) {
@@ -1279,6 +1285,12 @@ static int block_from_records(f2q_ctx *c, const std::vector<Rec> &recs, f2q_bloc
             if ((rc = dev_upload(c, hp.g_qlen.data(), hp.g_qlen.size(), &dqlen, b->allocs))) break;
             if ((rc = dev_upload(c, hp.g_index.data(), hp.g_index.size(), &dix, b->allocs))) break;
             b->rb.n = hp.g_len.size(); b->rb.raw = dr; b->rb.off = doff; b->rb.len = dlen; b->rb.qlen = dqlen; b->rb.index = dix;
+            if (!hp.g_len1.empty()) {                    // merged pairs
+                uint32_t *dl1, *dq1;
+                if ((rc = dev_upload(c, hp.g_len1.data(), hp.g_len1.size(), &dl1, b->allocs))) break;
+                if ((rc = dev_upload(c, hp.g_qlen1.data(), hp.g_qlen1.size(), &dq1, b->allocs))) break;
+                b->rb.len1 = dl1; b->rb.qlen1 = dq1;
+            }
             b->dev_bytes += hp.raw.size() + hp.g_len.size() * 20;
             b->raw_key_bytes = hp.raw.size();
         }
@@ -1288,6 +1300,13 @@ static int block_from_records(f2q_ctx *c, const std::vector<Rec> &recs, f2q_bloc
     if (rc) { free_all(c, b->allocs); delete b; return rc; }
     *out = b;
     return F2Q_OK;
+}
+
+static int block_from_records(f2q_ctx *c, const std::vector<Rec> &recs, f2q_block **out)
+{
+    HostPacked hp;
+    pack_records(c->plan, recs, hp);
+    return block_from_packed(c, hp, recs.size(), out);
 }
 
 
@@ -1312,6 +1331,43 @@ static int exclusive_scan(f2q_ctx *c, const uint32_t *in, uint32_t *out, uint32_
 // 16-byte aligned start of the FASTQ bytes inside it, with room for the census padding behind them
 struct DevText { void *buf = nullptr; size_t cap = 0; uint8_t *text = nullptr; uint8_t last_byte = 0; bool borrowed = false; };   // borrowed: the caller keeps the allocation (f2q_text)
 
+// One text on the device, framed: its line starts (k_nl_count -> scan -> k_line_starts).  The text is copied from `fastq`
+// into an allocation pushed to `text_owner`, or is already (on its way) in device memory (`pre`).  ft.sentinel is the source of
+// an asynchronous 4-byte copy: ft must outlive the next wait on the stream.
+struct FramedText { uint8_t *text = nullptr; uint32_t *ls = nullptr; uint32_t n_chunks = 0, n_newlines = 0, sentinel = 0; uint64_t n_lines = 0; };
+static int frame_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, const DevText *pre, std::vector<void *> &text_owner,
+                             std::vector<void *> &tmp, FramedText &ft)
+{
+    int rc;
+    ft.n_chunks = (uint32_t)((nbytes + F2Q_NL_CHUNK - 1) / F2Q_NL_CHUNK);
+    const uint32_t n_chunks = ft.n_chunks;
+    const size_t padded = (size_t)n_chunks * F2Q_NL_CHUNK + 16;
+    uint32_t *d_cc, *d_cp;
+    if (pre) {
+        ft.text = pre->text;
+        if ((size_t)(ft.text - (uint8_t *)pre->buf) + padded > pre->cap) return fail(c, F2Q_EINVAL, "staged text buffer too small");
+    } else if ((rc = dev_alloc(c, padded, &ft.text, text_owner))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_chunks + 1, &d_cc, tmp, 0))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_chunks + 1, &d_cp, tmp))) return rc;
+    HIPC(c, hipMemsetAsync(ft.text + nbytes, 0, padded - nbytes, c->stream));
+    const double tc0 = now_ms();
+    if (!pre) HIPC(c, hipMemcpyAsync(ft.text, fastq, nbytes, hipMemcpyHostToDevice, c->stream));
+    if (c->trace) { HIPC(c, hipStreamSynchronize(c->stream)); c->tr_copy += now_ms() - tc0; }
+    hipLaunchKernelGGL(k_nl_count, dim3(n_chunks), dim3(256), 0, c->stream, ft.text, (uint64_t)nbytes, d_cc);
+    HIPC(c, hipGetLastError());
+    if ((rc = exclusive_scan(c, d_cc, d_cp, (uint32_t)n_chunks + 1u, tmp))) return rc;
+    HIPC(c, hipMemcpyAsync(&ft.n_newlines, d_cp + n_chunks, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    const bool open_tail = nbytes > 0 && (pre ? pre->last_byte : fastq[nbytes - 1]) != '\n';
+    ft.n_lines = (uint64_t)ft.n_newlines + (open_tail ? 1 : 0);
+    if ((rc = dev_alloc(c, (size_t)ft.n_newlines + 2, &ft.ls, tmp))) return rc;
+    hipLaunchKernelGGL(k_line_starts, dim3(n_chunks), dim3(256), 0, c->stream, ft.text, (uint64_t)nbytes, d_cp, ft.ls);
+    HIPC(c, hipGetLastError());
+    ft.sentinel = (uint32_t)nbytes + 1u;
+    HIPC(c, hipMemcpyAsync(ft.ls + ft.n_newlines + 1, &ft.sentinel, 4, hipMemcpyHostToDevice, c->stream));
+    return F2Q_OK;
+}
+
 static int block_from_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, size_t *consumed, f2q_block **out,
                                   const DevText *pre = nullptr, uint64_t max_records = ~0ull)
 {
@@ -1322,35 +1378,12 @@ static int block_from_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbyte
     std::vector<void *> tmp;                         // scratch freed before returning
     int rc = F2Q_OK;
     auto bail = [&](int code) { free_all(c, tmp); free_all(c, b->allocs); delete b; return code; };
-    const uint32_t n_chunks = (uint32_t)((nbytes + F2Q_NL_CHUNK - 1) / F2Q_NL_CHUNK);
-    const size_t padded = (size_t)n_chunks * F2Q_NL_CHUNK + 16;
-    uint8_t *d_text; uint32_t *d_cc, *d_cp;
-    if (pre) {
-        d_text = pre->text;
-        if ((size_t)(d_text - (uint8_t *)pre->buf) + padded > pre->cap) { fail(c, F2Q_EINVAL, "staged text buffer too small"); return bail(F2Q_EINVAL); }
-    } else if ((rc = dev_alloc(c, padded, &d_text, b->allocs))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_chunks + 1, &d_cc, tmp, 0))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_chunks + 1, &d_cp, tmp))) return bail(rc);
+    FramedText ft;
+    if ((rc = frame_text_device(c, fastq, nbytes, pre, b->allocs, tmp, ft))) return bail(rc);
+    uint8_t *const d_text = ft.text; uint32_t *const d_ls = ft.ls;
+    const uint32_t n_newlines = ft.n_newlines;
+    const uint32_t n_rec = (uint32_t)std::min<uint64_t>(ft.n_lines / 4, max_records);   // (a piece of a sharded file owns only the records that start in it)
 #define ING(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(c, F2Q_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); return bail(F2Q_EHIP); } } while (0)
-    ING(hipMemsetAsync(d_text + nbytes, 0, padded - nbytes, c->stream));
-    const double tc0 = now_ms();
-    if (!pre) ING(hipMemcpyAsync(d_text, fastq, nbytes, hipMemcpyHostToDevice, c->stream));
-    if (c->trace) { ING(hipStreamSynchronize(c->stream)); c->tr_copy += now_ms() - tc0; }
-    hipLaunchKernelGGL(k_nl_count, dim3(n_chunks), dim3(256), 0, c->stream, d_text, (uint64_t)nbytes, d_cc);
-    ING(hipGetLastError());
-    if ((rc = exclusive_scan(c, d_cc, d_cp, (uint32_t)n_chunks + 1u, tmp))) return bail(rc);
-    uint32_t n_newlines = 0;
-    ING(hipMemcpyAsync(&n_newlines, d_cp + n_chunks, 4, hipMemcpyDeviceToHost, c->stream));
-    ING(hipStreamSynchronize(c->stream));
-    const bool open_tail = nbytes > 0 && (pre ? pre->last_byte : fastq[nbytes - 1]) != '\n';
-    const uint64_t n_lines = (uint64_t)n_newlines + (open_tail ? 1 : 0);
-    const uint32_t n_rec = (uint32_t)std::min<uint64_t>(n_lines / 4, max_records);   // (a piece of a sharded file owns only the records that start in it)
-    uint32_t *d_ls;
-    if ((rc = dev_alloc(c, (size_t)n_newlines + 2, &d_ls, tmp))) return bail(rc);
-    hipLaunchKernelGGL(k_line_starts, dim3(n_chunks), dim3(256), 0, c->stream, d_text, (uint64_t)nbytes, d_cp, d_ls);
-    ING(hipGetLastError());
-    const uint32_t sentinel = (uint32_t)nbytes + 1u;
-    ING(hipMemcpyAsync(d_ls + n_newlines + 1, &sentinel, 4, hipMemcpyHostToDevice, c->stream));
     b->n_reads = n_rec;
     if (n_rec == 0) { ING(hipStreamSynchronize(c->stream)); free_all(c, tmp); *out = b; return F2Q_OK; }
     // bytes consumed: the start of line 4*n_rec, or everything when the last record's last line is unterminated
@@ -1414,6 +1447,7 @@ static int block_from_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbyte
 extern "C" int f2q_block_from_fastq(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, f2q_block **out)
 {
     if (!c || !out || (!fastq && nbytes)) return F2Q_EINVAL;
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
     HIPC(c, hipSetDevice(c->device));
     if (!c->host_pack && nbytes < ((size_t)1 << 31)) { size_t used; return block_from_text_device(c, fastq, nbytes, &used, out); }
     std::vector<Rec> recs;
@@ -1448,6 +1482,7 @@ static int count_window(f2q_ctx *c, const uint8_t *fastq, size_t take, const Dev
 extern "C" int f2q_count_block(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, size_t *consumed, f2q_timing *t)
 {
     if (!c || (!fastq && nbytes)) return F2Q_EINVAL;
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
     HIPC(c, hipSetDevice(c->device));
     if (t) { memset(t, 0, sizeof *t); HIPC(c, hipEventRecord(c->ev_a, c->stream)); }
     if (consumed) *consumed = 0;
@@ -1467,6 +1502,175 @@ extern "C" int f2q_count_block(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, 
         if (take < ((size_t)1 << 30)) break;           // that was the tail: what is left is a partial record
     }
     if (consumed) *consumed = pos;
+    return timing_close(c, t, sum);
+}
+
+// ---- paired-end samples: feature parts taken from both mates -------------------------------------------------------
+extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2, int32_t revcomp)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->have_lib || c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_mate2 comes once, after f2q_create and before f2q_set_features");
+    if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
+    if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
+    for (int i = 0; i < n_start2; i++) if (start2[i] < 0) return fail(c, F2Q_EINVAL, "a mate-2 window starts before the mate");
+    const f2q_params keep = c->prm;
+    HIPC(c, hipSetDevice(c->device));
+    c->n_mate1 = c->prm.n_start; c->rc2 = revcomp != 0;
+    for (int i = 0; i < n_start2; i++) c->prm.start[c->prm.n_start + i] = start2[i];
+    c->prm.n_start += n_start2;
+    int rc = setup_run(c);
+    if (rc) { c->prm = keep; c->n_mate1 = 0; c->rc2 = false; (void)setup_run(c); return rc; }
+    HIPC(c, hipMemcpyAsync(c->run_d, &c->run_h, sizeof(RunDev), hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return F2Q_OK;
+}
+
+// Two FASTQ texts (each below 1 GiB: 32-bit offsets) -> a resident block of min(records1, records2) pairs; framing and
+// packing done by the device (k_nl_count .. k_pack_paired).  *used1 / *used2 = bytes up to the end of the last record used.
+static int block_from_pairs_device(f2q_ctx *c, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, size_t *used1, size_t *used2,
+                                   f2q_block **out)
+{
+    *out = nullptr; *used1 = *used2 = 0;
+    f2q_block *b = new f2q_block();
+    if (n1 == 0 || n2 == 0) { *out = b; return F2Q_OK; }
+    std::vector<void *> tmp;                         // scratch freed before returning (the texts too: raw records are copies)
+    int rc = F2Q_OK;
+    auto bail = [&](int code) { (void)hipStreamSynchronize(c->stream); free_all(c, tmp); free_all(c, b->allocs); delete b; return code; };
+#define ING(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(c, F2Q_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); return bail(F2Q_EHIP); } } while (0)
+    FramedText t1, t2;
+    if ((rc = frame_text_device(c, fq1, n1, nullptr, tmp, tmp, t1))) return bail(rc);
+    if ((rc = frame_text_device(c, fq2, n2, nullptr, tmp, tmp, t2))) return bail(rc);
+    const uint32_t n_rec = (uint32_t)std::min<uint64_t>(t1.n_lines / 4, t2.n_lines / 4);
+    b->n_reads = n_rec;
+    if (n_rec == 0) { ING(hipStreamSynchronize(c->stream)); free_all(c, tmp); *out = b; return F2Q_OK; }
+    uint32_t cons1 = (uint32_t)n1, cons2 = (uint32_t)n2;
+    if ((uint64_t)4 * n_rec <= t1.n_newlines) ING(hipMemcpyAsync(&cons1, t1.ls + (size_t)4 * n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((uint64_t)4 * n_rec <= t2.n_newlines) ING(hipMemcpyAsync(&cons2, t2.ls + (size_t)4 * n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    PairIngestDev ing{};
+    ing.text1 = t1.text; ing.text2 = t2.text; ing.ls1 = t1.ls; ing.ls2 = t2.ls; ing.n_pairs = n_rec;
+    uint32_t *d_before, *d_raw_before;
+    for (uint32_t **p : {&ing.off1, &ing.len1, &ing.qoff1, &ing.qlen1, &ing.off2, &ing.len2, &ing.qoff2, &ing.qlen2})
+        if ((rc = dev_alloc(c, (size_t)n_rec, p, tmp))) return bail(rc);
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &ing.clean, tmp, 0))) return bail(rc);
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &ing.raw_bytes, tmp, 0))) return bail(rc);
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_before, tmp))) return bail(rc);
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_raw_before, tmp))) return bail(rc);
+    if ((rc = dev_alloc(c, (size_t)4, &ing.meta, tmp, 0))) return bail(rc);
+    const unsigned igrid = (unsigned)((n_rec + F2Q_ING_THREADS - 1u) / F2Q_ING_THREADS);
+    hipLaunchKernelGGL(k_classify_paired, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan);
+    ING(hipGetLastError());
+    if ((rc = exclusive_scan(c, ing.clean, d_before, n_rec + 1u, tmp))) return bail(rc);
+    if ((rc = exclusive_scan(c, ing.raw_bytes, d_raw_before, n_rec + 1u, tmp))) return bail(rc);
+    uint32_t n_clean = 0, rmax_in = 0, raw_total = 0;
+    ING(hipMemcpyAsync(&n_clean, d_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    ING(hipMemcpyAsync(&raw_total, d_raw_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    ING(hipMemcpyAsync(&rmax_in, ing.meta, 4, hipMemcpyDeviceToHost, c->stream));
+    ING(hipStreamSynchronize(c->stream));
+    *used1 = cons1; *used2 = cons2;
+    const uint32_t n_dirty = n_rec - n_clean;
+    PairPackOut o{};
+    if (n_clean) {
+        uint32_t rmax, nw, wb, wq;
+        tile_geometry(c->plan, rmax_in, rmax, nw, wb, wq);
+        const uint32_t n_tiles = (n_clean + F2Q_TILE - 1) / F2Q_TILE;
+        if ((rc = dev_alloc(c, (size_t)n_tiles * wb * F2Q_TILE, &o.bases, b->allocs, 0))) return bail(rc);
+        if ((rc = dev_alloc(c, (size_t)n_tiles * wq * F2Q_TILE, &o.qual, b->allocs, 0))) return bail(rc);
+        if ((rc = dev_alloc(c, (size_t)n_tiles * F2Q_TILE, &o.len, b->allocs, 0xFF))) return bail(rc);
+        if (c->prm.mode == 1 && (rc = dev_alloc(c, (size_t)n_tiles * F2Q_TILE, &o.c_index, b->allocs, 0))) return bail(rc);
+        o.wb = wb; o.wq = wq;
+        b->pb.n_slots = (uint64_t)n_tiles * F2Q_TILE; b->pb.n_tiles = n_tiles; b->pb.wb = wb; b->pb.wq = wq; b->pb.rmax = rmax;
+        b->pb.planar_nw = nw; b->pb.bases = o.bases; b->pb.qual = o.qual; b->pb.len = o.len; b->pb.index = o.c_index;
+        b->dev_bytes += (uint64_t)n_tiles * F2Q_TILE * ((wb + wq) * 4 + 2);
+    }
+    if (n_dirty) {
+        if ((rc = dev_alloc(c, (size_t)raw_total + 16, &o.raw, b->allocs, 0))) return bail(rc);
+        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_off, b->allocs))) return bail(rc);
+        for (uint32_t **p : {&o.g_len, &o.g_qlen, &o.g_len1, &o.g_qlen1, &o.g_index})
+            if ((rc = dev_alloc(c, (size_t)n_dirty, p, b->allocs))) return bail(rc);
+        b->rb.n = n_dirty; b->rb.raw = o.raw; b->rb.off = o.g_off; b->rb.len = o.g_len; b->rb.qlen = o.g_qlen;
+        b->rb.len1 = o.g_len1; b->rb.qlen1 = o.g_qlen1; b->rb.index = o.g_index;
+        b->dev_bytes += (uint64_t)raw_total + (uint64_t)n_dirty * 28;
+        b->raw_key_bytes = raw_total;                // no key is longer than its merged record
+    }
+    b->n_general = n_dirty;
+    hipLaunchKernelGGL(k_pack_paired, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan, d_before, d_raw_before, o);
+    ING(hipGetLastError());
+    ING(hipStreamSynchronize(c->stream));             // scratch dies with this frame
+#undef ING
+    free_all(c, tmp);
+    *out = b;
+    return F2Q_OK;
+}
+
+// byte offset behind line `n_lines` of buf (the whole buffer when it holds fewer newlines)
+static size_t after_lines(const uint8_t *buf, size_t nbytes, uint64_t n_lines)
+{
+    size_t pos = 0;
+    for (uint64_t k = 0; k < n_lines && pos < nbytes; k++) {
+        const uint8_t *nl = (const uint8_t *)memchr(buf + pos, '\n', nbytes - pos);
+        pos = nl ? (size_t)(nl - buf) + 1 : nbytes;
+    }
+    return pos;
+}
+
+// a window of each text (each below 1 GiB) -> a block of pairs; the host twin under F2Q_HOST_PACK=1
+static int pair_block(f2q_ctx *c, const uint8_t *fq1, size_t n1, const uint8_t *fq2, size_t n2, size_t *used1, size_t *used2, f2q_block **out)
+{
+    if (!c->host_pack) return block_from_pairs_device(c, fq1, n1, fq2, n2, used1, used2, out);
+    std::vector<Rec> r1, r2;
+    frame_fastq(fq1, n1, r1); frame_fastq(fq2, n2, r2);
+    const size_t n = std::min(r1.size(), r2.size());
+    r1.resize(n); r2.resize(n);
+    *used1 = after_lines(fq1, n1, 4 * (uint64_t)n); *used2 = after_lines(fq2, n2, 4 * (uint64_t)n);
+    HostPacked hp;
+    pack_pairs(c->plan, r1, r2, hp);
+    return block_from_packed(c, hp, n, out);
+}
+
+static const size_t F2Q_PAIR_WINDOW = (size_t)1 << 30;      // most text of one mate per block (32-bit offsets on the device)
+
+extern "C" int f2q_block_from_fastq_paired(f2q_ctx *c, const uint8_t *fastq1, size_t n1, const uint8_t *fastq2, size_t n2, f2q_block **out)
+{
+    if (!c || !out || (!fastq1 && n1) || (!fastq2 && n2)) return F2Q_EINVAL;
+    if (!c->n_mate1) return fail(c, F2Q_ESTATE, "not a paired context: call f2q_set_mate2 first");
+    if (n1 >= F2Q_PAIR_WINDOW || n2 >= F2Q_PAIR_WINDOW) return fail(c, F2Q_EINVAL, "a resident block of pairs holds less than 1 GiB of text per mate");
+    HIPC(c, hipSetDevice(c->device));
+    size_t u1, u2;
+    return pair_block(c, fastq1, n1, fastq2, n2, &u1, &u2, out);
+}
+
+extern "C" int f2q_count_block_paired(f2q_ctx *c, const uint8_t *fastq1, size_t n1, const uint8_t *fastq2, size_t n2,
+                                      size_t *consumed1, size_t *consumed2, f2q_timing *t)
+{
+    if (!c || (!fastq1 && n1) || (!fastq2 && n2)) return F2Q_EINVAL;
+    if (!c->n_mate1) return fail(c, F2Q_ESTATE, "not a paired context: call f2q_set_mate2 first");
+    HIPC(c, hipSetDevice(c->device));
+    if (t) { memset(t, 0, sizeof *t); HIPC(c, hipEventRecord(c->ev_a, c->stream)); }
+    if (consumed1) *consumed1 = 0;
+    if (consumed2) *consumed2 = 0;
+    size_t p1 = 0, p2 = 0;
+    f2q_timing sum; memset(&sum, 0, sizeof sum);
+    while (p1 < n1 && p2 < n2) {
+        const size_t take1 = std::min(n1 - p1, F2Q_PAIR_WINDOW - 1), take2 = std::min(n2 - p2, F2Q_PAIR_WINDOW - 1);
+        // a window that is not the text's tail ends with a whole line: an open last line would count as a line
+        size_t w1 = take1, w2 = take2;
+        if (p1 + w1 < n1) while (w1 > 0 && fastq1[p1 + w1 - 1] != '\n') w1--;
+        if (p2 + w2 < n2) while (w2 > 0 && fastq2[p2 + w2 - 1] != '\n') w2--;
+        f2q_block *b = nullptr; size_t u1 = 0, u2 = 0;
+        int rc = pair_block(c, fastq1 + p1, w1, fastq2 + p2, w2, &u1, &u2, &b);
+        if (rc) return rc;
+        f2q_timing one; memset(&one, 0, sizeof one);
+        if (b && b->n_reads) rc = launch_block(c, b, t ? &one : nullptr);
+        const bool none = !b || b->n_reads == 0;
+        if (b) f2q_block_free(c, b);
+        if (rc) return rc;
+        timing_add(sum, one);
+        if (none) break;                               // no complete pair left in these windows
+        p1 += u1; p2 += u2;
+        if (p1 + (w1 - u1) >= n1 && p2 + (w2 - u2) >= n2) break;     // both windows reached their text's end
+    }
+    if (consumed1) *consumed1 = p1;
+    if (consumed2) *consumed2 = p2;
     return timing_close(c, t, sum);
 }
 
@@ -1492,6 +1696,7 @@ extern "C" int f2q_text_upload(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, 
 extern "C" int f2q_count_text(f2q_ctx *c, f2q_text *txt, size_t *consumed, f2q_timing *t)
 {
     if (!c || !txt) return F2Q_EINVAL;
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
     HIPC(c, hipSetDevice(c->device));
     if (t) { memset(t, 0, sizeof *t); HIPC(c, hipEventRecord(c->ev_a, c->stream)); }
     if (consumed) *consumed = 0;
@@ -1989,6 +2194,7 @@ static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, cons
 static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t world, f2q_timing *t)
 {
     if (!c || !path || world == 0 || rank >= world) return F2Q_EINVAL;
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
     HIPC(c, hipSetDevice(c->device));
     size_t CH = (size_t)256 << 20;                 // bytes of text per piece; F2Q_FILE_CHUNK overrides (tests)
     { const char *e = getenv("F2Q_FILE_CHUNK"); if (e && atol(e) >= 4096) CH = (size_t)atol(e); }
@@ -2068,6 +2274,88 @@ extern "C" int f2q_count_file(f2q_ctx *c, const char *path, f2q_timing *t) { ret
 extern "C" int f2q_count_file_shard(f2q_ctx *c, const char *path, uint32_t rank, uint32_t world, f2q_timing *t)
 {
     return count_file_impl(c, path, rank, world, t);
+}
+
+// ---- a paired-end sample by path: two files streamed in lockstep ----------------------------------------------------
+// One piece of each file per round (F2Q_FILE_CHUNK bytes of text; a file whose carried tail already holds a piece's worth
+// waits for the other), cut at whole lines, counted with the paired block call; what a round did not use is carried to
+// the next.  The reads are synchronous and the buffers pageable: no thread, no pinned memory to give back on any return.
+struct MateStream {
+    TextSource src; std::vector<uint8_t> buf; size_t at = 0; bool eof = false;      // buf[at ..): text not used yet
+    const uint8_t *data() const { return buf.data() + at; }
+    size_t size() const { return buf.size() - at; }
+    void fill(size_t chunk)
+    {
+        if (at) { buf.erase(buf.begin(), buf.begin() + (ptrdiff_t)at); at = 0; }    // once per read, not once per round
+        const size_t have = buf.size();
+        buf.resize(have + chunk);
+        const size_t got = src.read(buf.data() + have, chunk);
+        buf.resize(have + got);
+        if (got == 0) eof = true;
+    }
+    // the bytes a block may see: whole lines only, except at the sound end of the data (a damaged archive's cut-off last
+    // line is never seen, as readline raises there instead of returning it, fast2q.py:405-407)
+    size_t whole() const
+    {
+        size_t cut = size();
+        if (!eof || src.truncated()) while (cut > 0 && data()[cut - 1] != 0x0a) cut--;
+        return cut;
+    }
+    // does it hold a complete record?  four lines, the last one possibly open at the sound end of the data
+    bool has_record() const
+    {
+        const size_t n = whole();
+        size_t pos = 0; int lines = 0;
+        while (pos < n && lines < 4) {
+            const uint8_t *nl = (const uint8_t *)memchr(data() + pos, 0x0a, n - pos);
+            lines++;
+            pos = nl ? (size_t)(nl - data()) + 1 : n;
+        }
+        return lines == 4;
+    }
+};
+
+extern "C" int f2q_count_file_paired(f2q_ctx *c, const char *path1, const char *path2, f2q_timing *t)
+{
+    if (!c || !path1 || !path2) return F2Q_EINVAL;
+    if (!c->n_mate1) return fail(c, F2Q_ESTATE, "not a paired context: call f2q_set_mate2 first");
+    HIPC(c, hipSetDevice(c->device));
+    size_t CH = (size_t)64 << 20;                  // bytes of text per piece and file; F2Q_FILE_CHUNK overrides (tests)
+    { const char *e = getenv("F2Q_FILE_CHUNK"); if (e && atol(e) >= 4096) CH = (size_t)atol(e); }
+    CH = std::min(CH, F2Q_PAIR_WINDOW / 4);
+    MateStream m[2];
+    { std::string err; if (m[0].src.open(path1, err) != 0) return fail(c, F2Q_EIO, err); }
+    { std::string err; if (m[1].src.open(path2, err) != 0) return fail(c, F2Q_EIO, err); }
+    if (c->trace) fprintf(stderr, "[f2q trace] paired: %s (%s) + %s (%s), pieces of %zu bytes\n", path1, m[0].src.kind_name(), path2, m[1].src.kind_name(), CH);
+    f2q_timing sum; memset(&sum, 0, sizeof sum);
+    int rc = F2Q_OK;
+    bool stuck = false;                            // the last round used nothing: both files read on whatever they carry
+    for (;;) {
+        for (int k = 0; k < 2; k++) if (!m[k].eof && (stuck || m[k].size() < CH)) m[k].fill(CH);
+        size_t used[2] = {0, 0};
+        const size_t w0 = m[0].whole(), w1 = m[1].whole();
+        if (w0 && w1) {
+            f2q_timing one; memset(&one, 0, sizeof one);
+            if ((rc = f2q_count_block_paired(c, m[0].data(), w0, m[1].data(), w1, &used[0], &used[1], &one))) break;
+            timing_add(sum, one);
+        }
+        for (int k = 0; k < 2; k++) m[k].at += used[k];
+        stuck = used[0] == 0 && used[1] == 0;
+        // done when one file has ended and holds no further record: the other can complete no pair any more
+        const bool end0 = m[0].eof && !m[0].has_record(), end1 = m[1].eof && !m[1].has_record();
+        if (!end0 && !end1) continue;
+        // does the other hold a complete record beyond the last pair?  (read on only as far as that takes)
+        const int o = end0 ? 1 : 0;
+        bool extra = !(end0 && end1) && m[o].has_record();
+        while (!(end0 && end1) && !extra && !m[o].eof) { m[o].fill(CH); extra = m[o].has_record(); }
+        if (t) *t = sum;
+        for (int k = 0; k < 2; k++)
+            if (m[k].src.truncated()) return fail(c, F2Q_ETRUNCATED, m[k].src.path + " is an incomplete or corrupted gzip file");
+        if (extra) return fail(c, F2Q_EPAIRING, std::string(end0 ? path2 : path1) + " holds records beyond the last record of its mate file");
+        return F2Q_OK;
+    }
+    if (t) *t = sum;
+    return rc;
 }
 
 // ---- one plain file counted by several processes without anybody reading foreign bytes ------------------------------
@@ -2202,6 +2490,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
                                 const uint64_t *census, uint64_t n_pieces, f2q_timing *t)
 {
     if (!c || !path || !census || world == 0 || rank >= world || !piece_bytes_ok(piece_bytes)) return F2Q_EINVAL;
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
     HIPC(c, hipSetDevice(c->device));
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }
@@ -2398,6 +2687,7 @@ extern "C" int f2q_synth_create(f2q_ctx *c, const f2q_synth *s, f2q_block **out)
 {
     if (!c || !s || !out) return F2Q_EINVAL;
     HIPC(c, hipSetDevice(c->device));
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
     SynthDev d; int rc = synth_to_dev(c, s, d);
     if (rc) return rc;
     const int R = d.read_len;

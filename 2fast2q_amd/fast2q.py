@@ -25,6 +25,7 @@ import csv
 import datetime
 import glob
 import os
+import re
 import sys
 import threading
 import time
@@ -101,6 +102,9 @@ def features_loader(guides):
 
 
 def _counter_kwargs(param):
+    if param.get('paired'):                         # a paired context: the windows of mate 2 and its direction (f2q_set_mate2)
+        plain = {k: v for k, v in param.items() if k != 'paired'}
+        return dict(_counter_kwargs(plain), start2=param['start2'], rc2=bool(param.get('rc2')))
     return dict(mode=param['Running Mode'], miss=param['miss'], phred=param['phred'], length=param['length'],
                 start=param['start'], upstream=param['upstream'], downstream=param['downstream'],
                 miss_search_up=param['miss_search_up'], miss_search_down=param['miss_search_down'],
@@ -156,9 +160,49 @@ def close_contexts():
 atexit.register(close_contexts)
 
 
+_EXTENSIONS = re.compile(r"(\.(fastq|fq|gz|bgz))+$", re.IGNORECASE)
+
+
+def mate_token(path):
+    """(key, mate) of a paired-end file name: mate is 1 or 2, key the name with the mate token masked, equal for the two
+    files of a sample; (None, 0) for a name that carries no token.  The token is the last _R1 / _R2 that is followed by
+    '_', '.' or the end of the stem (Illumina: x_S1_L001_R1_001.fastq.gz), else _1 / _2 directly before the extension(s)."""
+    name = os.path.basename(path)
+    stem = _EXTENSIONS.sub("", name)
+    found = list(re.finditer(r"_R([12])(?=_|\.|$)", stem))
+    if found:
+        m = found[-1]
+        return name[:m.start(1)] + "*" + name[m.end(1):], int(m.group(1))
+    m = re.search(r"_([12])$", stem)
+    if m:
+        return name[:m.start(1)] + "*" + name[m.end(1):], int(m.group(1))
+    return None, 0
+
+
+def pair_files(files):
+    """[(R1 path, R2 path)] of a --pe run, in the order of the R1 files; ValueError names a file without its mate"""
+    mates = {}
+    for path in files:
+        key, mate = mate_token(path)
+        if not mate:
+            raise ValueError(f"{path} carries no _R1/_R2 (or _1/_2) token: with --pe every file of --s needs its mate")
+        if (os.path.dirname(path), key, mate) in mates:
+            raise ValueError(f"{path} and {mates[(os.path.dirname(path), key, mate)]} claim the same mate of one sample")
+        mates[(os.path.dirname(path), key, mate)] = path
+    pairs = []
+    for path in files:
+        key, mate = mate_token(path)
+        other = mates.get((os.path.dirname(path), key, 3 - mate))
+        if other is None:
+            raise ValueError(f"{path} has no mate file (--pe pairs _R1 with _R2, or _1 with _2)")
+        if mate == 1:
+            pairs.append((path, other))
+    return pairs
+
+
 def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
     """Counts one FASTQ(.gz) file (:514-582).  Returns (features, reads_stats, local_read_stats) -- the reference's
-    contract.  A cut-off or damaged .gz gives the counts of every complete record before the damage plus the
+    contract.  A paired-end run (param['paired']) counts `raw` together with its mate file param['mates'][raw].  A cut-off or damaged .gz gives the counts of every complete record before the damage plus the
     reference's warning (its parser keeps what it counted when readline raises, :405-407).  `features` is updated in
     place: Counter mode adds to Features.counts, Extract+Count mode adds the de-novo keys in first-occurrence order."""
     if (param['upstream'] is not None) and (param['downstream'] is not None):
@@ -173,7 +217,19 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
     ctx = _context_for(seqs, _counter_kwargs(param))
     try:
         world = sharding.world()
-        if world.size > 1:
+        if param.get('paired'):
+            if world.size > 1:
+                raise RuntimeError("--pe: paired files are not shared out over several ranks; run one process")
+            try:
+                _, truncated = ctx.count_file_paired(raw, param['mates'][raw])
+            except binding.F2QError as exc:
+                if exc.code != binding.F2Q_EPAIRING:
+                    raise
+                truncated = False                   # the common pairs are counted
+                colourful_errors("WARNING", f"{exc}. Only the pairs both files hold were counted.")
+            counts, stats = ctx.read_counts()
+            ec_rows = None if counter_mode else ctx.ec_results()
+        elif world.size > 1:
             truncated = sharding.count_file_sharded(ctx, raw, world)
             counts, stats, ec_rows = sharding.reduce_results(ctx, world)
         else:
@@ -300,6 +356,8 @@ def initializer(cmd):
         print(f" Finding features with the folowing length: {param['length']}bp")
     if (param['upstream'] is None) and (param['downstream'] is None):
         print(f" Read alignment start position: {param['start']}")
+    if param.get('paired'):
+        print(f" Paired-end: mate 2 start position: {param['start2']}" + (" (mate 2 reverse-complemented)" if param['rc2'] else ""))
     print(f" All data will be saved into {param['directory']}")
     print("\n ---- ")
     param["cpu"] = param["cpu"] if isinstance(param["cpu"], int) and param["cpu"] > 0 else (os.cpu_count() or 1)
@@ -361,12 +419,18 @@ def input_parser(argv=None):
     ap.add_argument("--fs", nargs='?', const=False, help="File Split mode (accepted for compatibility; ignored)")
     ap.add_argument("--k", nargs='?', const=False, help="If enabled, keeps all temporary files (default is disabled)")
     ap.add_argument("--gpu", help="HIP device ordinal (default: LOCAL_RANK or 0)")
+    ap.add_argument("--pe", nargs='?', const=True, help="Paired-end: the files of --s are paired by name (_R1/_R2, else _1/_2); --st names the feature parts in mate 1, --st2 those in mate 2")
+    ap.add_argument("--st2", help="With --pe: the start position(s) of the feature part(s) within mate 2")
+    ap.add_argument("--rc2", nargs='?', const=True, help="With --pe: mate 2 is reverse-complemented before its parts are taken")
     args = ap.parse_args(argv)
     if args.v is not None:
         print(f"\nVersion: {version}\n")
         sys.exit()
     if args.c is None:
         return None
+    if args.pe is not None and args.t is not None:
+        colourful_errors("FATAL", "--pe cannot be combined with -t: the test mode runs on one packaged single-end sample.")
+        sys.exit(2)
     p = {"cmd": True, "big_file_split": args.fs is not None}
     p['used_cmd'] = " ".join(f"--{k}" if isinstance(v, bool) and v else f"--{k} {v}"
                              for k, v in vars(args).items() if v is not None)
@@ -392,6 +456,17 @@ def input_parser(argv=None):
     p['cpu'] = int(args.cp) if args.cp is not None else False
     if args.gpu is not None:
         p['device'] = int(args.gpu)
+    if args.pe is not None:
+        if args.us is not None or args.ds is not None:
+            colourful_errors("FATAL", "--pe takes fixed positions only (--st / --st2): it cannot be combined with --us / --ds.")
+            sys.exit(2)
+        if args.st2 is None:
+            colourful_errors("FATAL", "--pe needs --st2: the start position(s) of the feature part(s) within mate 2.")
+            sys.exit(2)
+        p['paired'], p['start2'], p['rc2'] = True, args.st2, args.rc2 is not None
+    elif args.st2 is not None or args.rc2 is not None:
+        colourful_errors("FATAL", f"{'--st2' if args.st2 is not None else '--rc2'} only has a meaning with --pe.")
+        sys.exit(2)
     for value, key in paths:                                   # :1178-1191
         if value is None:
             p[key] = os.getcwd()
@@ -414,6 +489,17 @@ def file_sizer_split(param):
         param["sequencing_files"] = {"len_files": 1, "preprocess_files": [param["seq_files"]], "files": [param["seq_files"]]}
         return param
     files = [p[0] for p in path_parser(param["seq_files"], ["*.gz", "*.fastq"])]
+    if param.get('paired'):                                      # one sample per pair, named after its R1 file
+        if sharding.world().size > 1:
+            colourful_errors("FATAL", "--pe: paired files are not shared out over several ranks; run one process.")
+            sys.exit(2)
+        try:
+            pairs = pair_files(files)
+        except ValueError as exc:
+            colourful_errors("FATAL", str(exc))
+            sys.exit(2)
+        param['mates'] = dict(pairs)
+        files = [r1 for r1, _ in pairs]
     param["sequencing_files"] = {"len_files": len(files), "preprocess_files": files[:1], "files": files}
     return param
 
@@ -490,6 +576,9 @@ def run_headers(param):
               f"#Mismatches in the downstream search sequence: {param['miss_search_down']}",
               f"#Minimal Phred-score in the upstream search sequence: {param['qual_up']}",
               f"#Minimal Phred-score in the downstream search sequence: {param['qual_down']}"]
+    if param.get('paired'):
+        lines += [f"#Paired-end, feature start position in mate 2: {param['start2']}",
+                  f"#Mate 2 reverse-complemented: {'yes' if param['rc2'] else 'no'}"]
     return lines
 
 

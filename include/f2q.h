@@ -40,7 +40,9 @@ enum {
     F2Q_ETRUNCATED = -6,         /* corrupted or truncated gzip stream (partial counts kept,
                                     as fast2q.py:405-407,580-582)                             */
     F2Q_ESTATE = -7,             /* call order (e.g. counting before f2q_set_features)        */
-    F2Q_EUNSUPPORTED = -8        /* input outside what the device path implements             */
+    F2Q_EUNSUPPORTED = -8,       /* input outside what the device path implements             */
+    F2Q_EPAIRING = -9            /* paired files: one holds complete records beyond the other's
+                                    last (the common pairs stay counted)                      */
 };
 
 /* index into the stats vector == the keys of local_read_stats (fast2q.py:310-316) */
@@ -189,6 +191,39 @@ int f2q_file_pieces(const char *path, uint64_t piece_bytes, uint64_t *n_pieces, 
 int f2q_census_pieces(const char *path, uint32_t rank, uint32_t world, uint64_t piece_bytes, uint64_t *census, uint64_t n_pieces);
 int f2q_count_pieces(f2q_ctx *ctx, const char *path, uint32_t rank, uint32_t world, uint64_t piece_bytes,
                      const uint64_t *census, uint64_t n_pieces, f2q_timing *t);
+
+/* ---- paired-end samples ---------------------------------------------------------------------
+ * The reference reads one file per sample; a dual-guide or barcode-plus-guide screen sequenced paired-end has part A at
+ * a fixed place in R1 and part B at a fixed place in R2.  A paired context counts such a sample as the reference counts
+ * ONE read with n_start + n_start2 windows (fast2q.py:349-367,382-393): record i of the first text pairs with record i of
+ * the second (header lines are not compared; the reference never looks at them, :324-328); the parts are the context's
+ * --st windows of mate 1, then the start2 windows of mate 2, each upper(seq[s:s+l]) of its own mate with Python-slice
+ * clipping at the end of THAT mate (:354), each tested against --ph on its own quality slice (:355-360), failed parts
+ * left out, the rest joined with ':' (:362); Counter mode matches the key with --m (:364-367), Extract+Count takes it as
+ * a key (:382-387); the five counters as for one read, F2Q_READS counting pairs (:389-393).  With revcomp != 0 mate 2 is
+ * taken reverse-complemented: its sequence reversed and complemented byte by byte (A<->T, C<->G, a<->t, c<->g, any other
+ * byte unchanged), its quality line reversed.
+ *
+ * f2q_set_mate2 makes a fixed-offset context (no --us/--ds) a paired context: after f2q_create and before
+ * f2q_set_features, which builds the joined-key index (F2Q_ESTATE afterwards or when called twice); F2Q_EINVAL for an
+ * anchored context, n_start2 < 1, a negative start or n_start + n_start2 > F2Q_MAX_ITER.  From then on f2q_count_block,
+ * f2q_block_from_fastq, f2q_count_text, f2q_count_file*, f2q_count_pieces and f2q_synth_create return F2Q_ESTATE on the
+ * context, and the *_paired calls return F2Q_ESTATE on any other context. */
+int f2q_set_mate2(f2q_ctx *ctx, const int32_t *start2, int32_t n_start2, int32_t revcomp);
+/* fastq_parser (fast2q.py:324-393) over two in-memory FASTQ buffers in lockstep: counts min(records1, records2) pairs;
+ * *consumed1 / *consumed2 (optional) = per text, the bytes up to the end of the last record used, so a caller can stream
+ * two files in blocks.  rstrip() framing per text, a trailing partial record ignored, as f2q_count_block. */
+int f2q_count_block_paired(f2q_ctx *ctx, const uint8_t *fastq1, size_t n1, const uint8_t *fastq2, size_t n2,
+                           size_t *consumed1, size_t *consumed2, f2q_timing *t);
+/* The same pairs packed into a device-resident block for f2q_count_resident / f2q_count_resident_queued (below): a clean
+ * pair takes the tile slot the merged read would take, so the counting kernels run as they are (fast2q.py:349-367 over
+ * the pair).  Less than 1 GiB of text per mate. */
+int f2q_block_from_fastq_paired(f2q_ctx *ctx, const uint8_t *fastq1, size_t n1, const uint8_t *fastq2, size_t n2, f2q_block **out);
+/* reads_counter's file half (fast2q.py:560-578) for the two files of a paired sample: each path plain, gzip or BGZF by
+ * content (the two need not be alike), streamed in lockstep in pieces of F2Q_FILE_CHUNK bytes of text.  F2Q_EPAIRING:
+ * one file holds complete records beyond the other's last; the common pairs stay counted.  F2Q_ETRUNCATED: an archive
+ * is cut off or damaged; the pairs completed before the damage stay counted (as :405-407,580-582 keep what was counted). */
+int f2q_count_file_paired(f2q_ctx *ctx, const char *path1, const char *path2, f2q_timing *t);
 
 /* Device-resident blocks: the roofline entry points.  f2q_synth_create generates the §8(d)
  * reads on the device straight into the packed tile layout; f2q_block_from_fastq packs a host
