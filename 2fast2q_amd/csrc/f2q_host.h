@@ -565,6 +565,29 @@ struct HostSink {
     void len(uint32_t v) { *lp = (uint16_t)v; }
 };
 
+// What both packers end with: the raw records are closed, and the clean reads (`clean`: their positions inside the block,
+// rmax the longest of their packed lengths, rec_of(i) read i as pack_read takes it) fill the slots of compact tiles.
+template <class RecOf>
+inline void pack_clean(const PackPlan &pl, const std::vector<uint32_t> &clean, uint32_t rmax, RecOf rec_of, HostPacked &hp)
+{
+    hp.raw.resize(hp.raw.size() + 8, 0);
+    hp.n_clean = clean.size();
+    if (clean.empty()) return;
+    hp.c_index.assign(((clean.size() + F2Q_TILE - 1) / F2Q_TILE) * F2Q_TILE, 0);
+    for (size_t s = 0; s < clean.size(); s++) hp.c_index[s] = clean[s];
+    tile_geometry(pl, rmax, hp.rmax, hp.planar_nw, hp.wb, hp.wq);
+    hp.n_tiles = (uint32_t)((clean.size() + F2Q_TILE - 1) / F2Q_TILE);
+    hp.bases.assign((size_t)hp.n_tiles * hp.wb * F2Q_TILE, 0);
+    hp.qual.assign((size_t)hp.n_tiles * hp.wq * F2Q_TILE, 0);
+    hp.len.assign((size_t)hp.n_tiles * F2Q_TILE, (uint16_t)F2Q_LEN_SKIP);
+    for (size_t s = 0; s < clean.size(); s++) {
+        const size_t tile = s / F2Q_TILE, lane = s % F2Q_TILE;
+        HostSink sink{hp.bases.data() + tile * hp.wb * F2Q_TILE + lane, hp.qual.data() + tile * hp.wq * F2Q_TILE + lane,
+                      hp.len.data() + tile * F2Q_TILE + lane};
+        pack_read(pl, rec_of(clean[s]), hp.planar_nw, sink);
+    }
+}
+
 inline void pack_records(const PackPlan &pl, const std::vector<Rec> &recs, HostPacked &hp)
 {
     hp = HostPacked();
@@ -583,22 +606,7 @@ inline void pack_records(const PackPlan &pl, const std::vector<Rec> &recs, HostP
             hp.raw.insert(hp.raw.end(), r.qual, r.qual + r.qlen);
         }
     }
-    hp.raw.resize(hp.raw.size() + 8, 0);
-    hp.n_clean = clean.size();
-    if (clean.empty()) return;
-    hp.c_index.assign(((clean.size() + F2Q_TILE - 1) / F2Q_TILE) * F2Q_TILE, 0);
-    for (size_t s = 0; s < clean.size(); s++) hp.c_index[s] = clean[s];
-    tile_geometry(pl, rmax, hp.rmax, hp.planar_nw, hp.wb, hp.wq);
-    hp.n_tiles = (uint32_t)((clean.size() + F2Q_TILE - 1) / F2Q_TILE);
-    hp.bases.assign((size_t)hp.n_tiles * hp.wb * F2Q_TILE, 0);
-    hp.qual.assign((size_t)hp.n_tiles * hp.wq * F2Q_TILE, 0);
-    hp.len.assign((size_t)hp.n_tiles * F2Q_TILE, (uint16_t)F2Q_LEN_SKIP);
-    for (size_t s = 0; s < clean.size(); s++) {
-        const size_t tile = s / F2Q_TILE, lane = s % F2Q_TILE;
-        HostSink sink{hp.bases.data() + tile * hp.wb * F2Q_TILE + lane, hp.qual.data() + tile * hp.wq * F2Q_TILE + lane,
-                      hp.len.data() + tile * F2Q_TILE + lane};
-        pack_read(pl, recs[clean[s]], hp.planar_nw, sink);
-    }
+    pack_clean(pl, clean, rmax, [&](uint32_t i) -> const Rec & { return recs[i]; }, hp);
 }
 
 // mate 2 as the run takes it: the line reversed, the sequence line complemented too (rc2), else as read
@@ -636,22 +644,7 @@ inline void pack_pairs(const PackPlan &pl, const std::vector<Rec> &r1, const std
             append_mate2(hp.raw, r2[i].qual, r.qlen2, pl.rc2, false);
         }
     }
-    hp.raw.resize(hp.raw.size() + 8, 0);
-    hp.n_clean = clean.size();
-    if (clean.empty()) return;
-    hp.c_index.assign(((clean.size() + F2Q_TILE - 1) / F2Q_TILE) * F2Q_TILE, 0);
-    for (size_t s = 0; s < clean.size(); s++) hp.c_index[s] = clean[s];
-    tile_geometry(pl, rmax, hp.rmax, hp.planar_nw, hp.wb, hp.wq);
-    hp.n_tiles = (uint32_t)((clean.size() + F2Q_TILE - 1) / F2Q_TILE);
-    hp.bases.assign((size_t)hp.n_tiles * hp.wb * F2Q_TILE, 0);
-    hp.qual.assign((size_t)hp.n_tiles * hp.wq * F2Q_TILE, 0);
-    hp.len.assign((size_t)hp.n_tiles * F2Q_TILE, (uint16_t)F2Q_LEN_SKIP);
-    for (size_t s = 0; s < clean.size(); s++) {
-        const size_t tile = s / F2Q_TILE, lane = s % F2Q_TILE;
-        HostSink sink{hp.bases.data() + tile * hp.wb * F2Q_TILE + lane, hp.qual.data() + tile * hp.wq * F2Q_TILE + lane,
-                      hp.len.data() + tile * F2Q_TILE + lane};
-        pack_read(pl, rec_of(clean[s]), hp.planar_nw, sink);
-    }
+    pack_clean(pl, clean, rmax, rec_of, hp);
 }
 
 // ---------------------------------------------------------------------------------------------

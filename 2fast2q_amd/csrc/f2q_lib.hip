@@ -13,6 +13,7 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <unordered_map>
 #include <mutex>
 #include <thread>
@@ -203,6 +204,19 @@ static void free_all(f2q_ctx *c, std::vector<void *> &v)
     }
     v.clear();
 }
+// device allocations that go back when the scope ends, on every return path: free_all waits for the stream first
+struct DevScope {
+    f2q_ctx *const c; std::vector<void *> v;
+    explicit DevScope(f2q_ctx *ctx, void *p = nullptr) : c(ctx) { if (p) v.push_back(p); }
+    ~DevScope() { free_all(c, v); }
+    DevScope(const DevScope &) = delete;
+};
+static int hip_rc(f2q_ctx *c, hipError_t e) { return e == hipSuccess ? F2Q_OK : fail(c, F2Q_EHIP, hipGetErrorString(e)); }
+// the calls for single reads refuse a paired context, and the other way round
+static int single_only(f2q_ctx *c) { return c->n_mate1 ? fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls") : F2Q_OK; }
+static int paired_only(f2q_ctx *c) { return c->n_mate1 ? F2Q_OK : fail(c, F2Q_ESTATE, "not a paired context: call f2q_set_mate2 first"); }
+// bytes of text per piece of a streamed file; F2Q_FILE_CHUNK overrides (tests)
+static size_t file_chunk_bytes(size_t dflt) { const char *e = getenv("F2Q_FILE_CHUNK"); return e && atol(e) >= 4096 ? (size_t)atol(e) : dflt; }
 
 extern "C" int f2q_version(void) { return F2Q_ABI_VERSION; }
 
@@ -1368,86 +1382,97 @@ static int frame_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, co
     return F2Q_OK;
 }
 
+// *cons = bytes of a framed text up to the end of its record n_rec - 1: the start of line 4 * n_rec, or everything when
+// that record's last line is unterminated.  Queued on the stream: *cons holds it after the next wait.
+static int consumed_offset(f2q_ctx *c, const FramedText &ft, size_t nbytes, uint32_t n_rec, uint32_t *cons)
+{
+    *cons = (uint32_t)nbytes;
+    if ((uint64_t)4 * n_rec <= ft.n_newlines) HIPC(c, hipMemcpyAsync(cons, ft.ls + (size_t)4 * n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    return F2Q_OK;
+}
+
+// The compact tiles of a block's n_clean clean reads, rmax_in the longest of their packed lengths: the planes are
+// allocated into `own`, described in b->pb and handed to the packing kernel in o (PackOut or PairPackOut).
+template <class Out>
+static int alloc_tile_planes(f2q_ctx *c, f2q_block *b, std::vector<void *> &own, uint32_t n_clean, uint32_t rmax_in, Out &o)
+{
+    if (!n_clean) return F2Q_OK;
+    int rc;
+    uint32_t rmax, nw, wb, wq;
+    tile_geometry(c->plan, rmax_in, rmax, nw, wb, wq);
+    const uint32_t n_tiles = (n_clean + F2Q_TILE - 1) / F2Q_TILE;
+    if ((rc = dev_alloc(c, (size_t)n_tiles * wb * F2Q_TILE, &o.bases, own, 0))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_tiles * wq * F2Q_TILE, &o.qual, own, 0))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_tiles * F2Q_TILE, &o.len, own, 0xFF))) return rc;
+    if (c->prm.mode == 1 && (rc = dev_alloc(c, (size_t)n_tiles * F2Q_TILE, &o.c_index, own, 0))) return rc;
+    o.wb = wb; o.wq = wq;
+    b->pb.n_slots = (uint64_t)n_tiles * F2Q_TILE; b->pb.n_tiles = n_tiles; b->pb.wb = wb; b->pb.wq = wq; b->pb.rmax = rmax;
+    b->pb.planar_nw = nw; b->pb.bases = o.bases; b->pb.qual = o.qual; b->pb.len = o.len; b->pb.index = o.c_index;
+    b->dev_bytes += (uint64_t)n_tiles * F2Q_TILE * ((wb + wq) * 4 + 2);
+    return F2Q_OK;
+}
+
+// Both device ingest drivers keep their scratch in `tmp` and what the block will own in `own` until they hand the block
+// out: any return before that waits for the stream and frees both.
 static int block_from_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, size_t *consumed, f2q_block **out,
                                   const DevText *pre = nullptr, uint64_t max_records = ~0ull)
 {
     *out = nullptr; *consumed = 0;
-    f2q_block *b = new f2q_block();
-    if (pre && !pre->borrowed) b->allocs.push_back(pre->buf);
-    if (nbytes == 0) { if (pre) free_all(c, b->allocs); *out = b; return F2Q_OK; }    // an empty buffer is an empty block
-    std::vector<void *> tmp;                         // scratch freed before returning
-    int rc = F2Q_OK;
-    auto bail = [&](int code) { free_all(c, tmp); free_all(c, b->allocs); delete b; return code; };
-    FramedText ft;
-    if ((rc = frame_text_device(c, fastq, nbytes, pre, b->allocs, tmp, ft))) return bail(rc);
-    uint8_t *const d_text = ft.text; uint32_t *const d_ls = ft.ls;
-    const uint32_t n_newlines = ft.n_newlines;
+    FramedText ft;                                   // (outlives the scopes' wait for the stream: ft.sentinel)
+    std::unique_ptr<f2q_block> b(new f2q_block());
+    DevScope tmp(c), own(c);
+    if (pre && !pre->borrowed) own.v.push_back(pre->buf);
+    if (nbytes == 0) { *out = b.release(); return F2Q_OK; }    // an empty buffer is an empty block
+    int rc;
+    if ((rc = frame_text_device(c, fastq, nbytes, pre, own.v, tmp.v, ft))) return rc;
     const uint32_t n_rec = (uint32_t)std::min<uint64_t>(ft.n_lines / 4, max_records);   // (a piece of a sharded file owns only the records that start in it)
-#define ING(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(c, F2Q_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); return bail(F2Q_EHIP); } } while (0)
     b->n_reads = n_rec;
-    if (n_rec == 0) { ING(hipStreamSynchronize(c->stream)); free_all(c, tmp); *out = b; return F2Q_OK; }
-    // bytes consumed: the start of line 4*n_rec, or everything when the last record's last line is unterminated
-    uint32_t cons32 = (uint32_t)nbytes;
-    if ((uint64_t)4 * n_rec <= n_newlines) ING(hipMemcpyAsync(&cons32, d_ls + (size_t)4 * n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_rec == 0) { HIPC(c, hipStreamSynchronize(c->stream)); b->allocs.swap(own.v); *out = b.release(); return F2Q_OK; }
+    uint32_t cons32;
+    if ((rc = consumed_offset(c, ft, nbytes, n_rec, &cons32))) return rc;
     IngestDev ing{};
-    ing.text = d_text; ing.line_start = d_ls; ing.n_records = n_rec;
+    ing.text = ft.text; ing.line_start = ft.ls; ing.n_records = n_rec;
     uint32_t *d_before;
-    if ((rc = dev_alloc(c, (size_t)n_rec, &ing.r_off, tmp))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec, &ing.r_len, tmp))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec, &ing.r_qoff, tmp))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec, &ing.r_qlen, tmp))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &ing.clean, tmp, 0))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_before, tmp))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)4, &ing.meta, tmp, 0))) return bail(rc);
+    for (uint32_t **p : {&ing.r_off, &ing.r_len, &ing.r_qoff, &ing.r_qlen})
+        if ((rc = dev_alloc(c, (size_t)n_rec, p, tmp.v))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &ing.clean, tmp.v, 0))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_before, tmp.v))) return rc;
+    if ((rc = dev_alloc(c, (size_t)4, &ing.meta, tmp.v, 0))) return rc;
     const unsigned igrid = (unsigned)((n_rec + F2Q_ING_THREADS - 1u) / F2Q_ING_THREADS);
     hipLaunchKernelGGL(k_classify, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan);
-    ING(hipGetLastError());
-    if ((rc = exclusive_scan(c, ing.clean, d_before, n_rec + 1u, tmp))) return bail(rc);
+    HIPC(c, hipGetLastError());
+    if ((rc = exclusive_scan(c, ing.clean, d_before, n_rec + 1u, tmp.v))) return rc;
     uint32_t n_clean = 0, rmax_in = 0;
-    ING(hipMemcpyAsync(&n_clean, d_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
-    ING(hipMemcpyAsync(&rmax_in, ing.meta, 4, hipMemcpyDeviceToHost, c->stream));
-    ING(hipStreamSynchronize(c->stream));
+    HIPC(c, hipMemcpyAsync(&n_clean, d_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&rmax_in, ing.meta, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
     *consumed = cons32;
     const uint32_t n_dirty = n_rec - n_clean;
     PackOut o{};
-    if (n_clean) {
-        uint32_t rmax, nw, wb, wq;
-        tile_geometry(c->plan, rmax_in, rmax, nw, wb, wq);
-        const uint32_t n_tiles = (n_clean + F2Q_TILE - 1) / F2Q_TILE;
-        if ((rc = dev_alloc(c, (size_t)n_tiles * wb * F2Q_TILE, &o.bases, b->allocs, 0))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_tiles * wq * F2Q_TILE, &o.qual, b->allocs, 0))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_tiles * F2Q_TILE, &o.len, b->allocs, 0xFF))) return bail(rc);
-        if (c->prm.mode == 1 && (rc = dev_alloc(c, (size_t)n_tiles * F2Q_TILE, &o.c_index, b->allocs, 0))) return bail(rc);
-        o.wb = wb; o.wq = wq; o.planar_nw = nw;
-        b->pb.n_slots = (uint64_t)n_tiles * F2Q_TILE; b->pb.n_tiles = n_tiles; b->pb.wb = wb; b->pb.wq = wq; b->pb.rmax = rmax;
-        b->pb.planar_nw = nw; b->pb.bases = o.bases; b->pb.qual = o.qual; b->pb.len = o.len; b->pb.index = o.c_index;
-        b->dev_bytes += (uint64_t)n_tiles * F2Q_TILE * ((wb + wq) * 4 + 2);
-    }
+    if ((rc = alloc_tile_planes(c, b.get(), own.v, n_clean, rmax_in, o))) return rc;
+    o.planar_nw = b->pb.planar_nw;
     if (n_dirty) {
-        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_off, b->allocs))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_qoff, b->allocs))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_len, b->allocs))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_qlen, b->allocs))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_index, b->allocs))) return bail(rc);
-        b->rb.n = n_dirty; b->rb.raw = d_text; b->rb.off = o.g_off; b->rb.qoff = o.g_qoff; b->rb.len = o.g_len;
+        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_off, own.v))) return rc;
+        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_qoff, own.v))) return rc;
+        for (uint32_t **p : {&o.g_len, &o.g_qlen, &o.g_index})
+            if ((rc = dev_alloc(c, (size_t)n_dirty, p, own.v))) return rc;
+        b->rb.n = n_dirty; b->rb.raw = ft.text; b->rb.off = o.g_off; b->rb.qoff = o.g_qoff; b->rb.len = o.g_len;
         b->rb.qlen = o.g_qlen; b->rb.index = o.g_index;
         b->dev_bytes += nbytes;
         b->raw_key_bytes = nbytes;                    // the records point into the text: no key is longer than its record
     }
     b->n_general = n_dirty;
     hipLaunchKernelGGL(k_pack, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan, d_before, o);
-    ING(hipGetLastError());
-    ING(hipStreamSynchronize(c->stream));             // scratch dies with this frame
-#undef ING
-    free_all(c, tmp);
-    *out = b;
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));         // scratch dies with this frame
+    b->allocs.swap(own.v); *out = b.release();
     return F2Q_OK;
 }
 
 extern "C" int f2q_block_from_fastq(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, f2q_block **out)
 {
     if (!c || !out || (!fastq && nbytes)) return F2Q_EINVAL;
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
+    if (int rc = single_only(c)) return rc;
     HIPC(c, hipSetDevice(c->device));
     if (!c->host_pack && nbytes < ((size_t)1 << 31)) { size_t used; return block_from_text_device(c, fastq, nbytes, &used, out); }
     std::vector<Rec> recs;
@@ -1482,7 +1507,7 @@ static int count_window(f2q_ctx *c, const uint8_t *fastq, size_t take, const Dev
 extern "C" int f2q_count_block(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, size_t *consumed, f2q_timing *t)
 {
     if (!c || (!fastq && nbytes)) return F2Q_EINVAL;
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
+    if (int rc = single_only(c)) return rc;
     HIPC(c, hipSetDevice(c->device));
     if (t) { memset(t, 0, sizeof *t); HIPC(c, hipEventRecord(c->ev_a, c->stream)); }
     if (consumed) *consumed = 0;
@@ -1531,62 +1556,48 @@ static int block_from_pairs_device(f2q_ctx *c, const uint8_t *fq1, size_t n1, co
                                    f2q_block **out)
 {
     *out = nullptr; *used1 = *used2 = 0;
-    f2q_block *b = new f2q_block();
-    if (n1 == 0 || n2 == 0) { *out = b; return F2Q_OK; }
-    std::vector<void *> tmp;                         // scratch freed before returning (the texts too: raw records are copies)
-    int rc = F2Q_OK;
-    auto bail = [&](int code) { (void)hipStreamSynchronize(c->stream); free_all(c, tmp); free_all(c, b->allocs); delete b; return code; };
-#define ING(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(c, F2Q_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); return bail(F2Q_EHIP); } } while (0)
     FramedText t1, t2;
-    if ((rc = frame_text_device(c, fq1, n1, nullptr, tmp, tmp, t1))) return bail(rc);
-    if ((rc = frame_text_device(c, fq2, n2, nullptr, tmp, tmp, t2))) return bail(rc);
+    std::unique_ptr<f2q_block> b(new f2q_block());
+    if (n1 == 0 || n2 == 0) { *out = b.release(); return F2Q_OK; }
+    DevScope tmp(c), own(c);                         // (the texts are scratch too: raw records are copies)
+    int rc;
+    if ((rc = frame_text_device(c, fq1, n1, nullptr, tmp.v, tmp.v, t1))) return rc;
+    if ((rc = frame_text_device(c, fq2, n2, nullptr, tmp.v, tmp.v, t2))) return rc;
     const uint32_t n_rec = (uint32_t)std::min<uint64_t>(t1.n_lines / 4, t2.n_lines / 4);
     b->n_reads = n_rec;
-    if (n_rec == 0) { ING(hipStreamSynchronize(c->stream)); free_all(c, tmp); *out = b; return F2Q_OK; }
-    uint32_t cons1 = (uint32_t)n1, cons2 = (uint32_t)n2;
-    if ((uint64_t)4 * n_rec <= t1.n_newlines) ING(hipMemcpyAsync(&cons1, t1.ls + (size_t)4 * n_rec, 4, hipMemcpyDeviceToHost, c->stream));
-    if ((uint64_t)4 * n_rec <= t2.n_newlines) ING(hipMemcpyAsync(&cons2, t2.ls + (size_t)4 * n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_rec == 0) { HIPC(c, hipStreamSynchronize(c->stream)); *out = b.release(); return F2Q_OK; }
+    uint32_t cons1, cons2;
+    if ((rc = consumed_offset(c, t1, n1, n_rec, &cons1))) return rc;
+    if ((rc = consumed_offset(c, t2, n2, n_rec, &cons2))) return rc;
     PairIngestDev ing{};
     ing.text1 = t1.text; ing.text2 = t2.text; ing.ls1 = t1.ls; ing.ls2 = t2.ls; ing.n_pairs = n_rec;
     uint32_t *d_before, *d_raw_before;
     for (uint32_t **p : {&ing.off1, &ing.len1, &ing.qoff1, &ing.qlen1, &ing.off2, &ing.len2, &ing.qoff2, &ing.qlen2})
-        if ((rc = dev_alloc(c, (size_t)n_rec, p, tmp))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &ing.clean, tmp, 0))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &ing.raw_bytes, tmp, 0))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_before, tmp))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_raw_before, tmp))) return bail(rc);
-    if ((rc = dev_alloc(c, (size_t)4, &ing.meta, tmp, 0))) return bail(rc);
+        if ((rc = dev_alloc(c, (size_t)n_rec, p, tmp.v))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &ing.clean, tmp.v, 0))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &ing.raw_bytes, tmp.v, 0))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_before, tmp.v))) return rc;
+    if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_raw_before, tmp.v))) return rc;
+    if ((rc = dev_alloc(c, (size_t)4, &ing.meta, tmp.v, 0))) return rc;
     const unsigned igrid = (unsigned)((n_rec + F2Q_ING_THREADS - 1u) / F2Q_ING_THREADS);
     hipLaunchKernelGGL(k_classify_paired, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan);
-    ING(hipGetLastError());
-    if ((rc = exclusive_scan(c, ing.clean, d_before, n_rec + 1u, tmp))) return bail(rc);
-    if ((rc = exclusive_scan(c, ing.raw_bytes, d_raw_before, n_rec + 1u, tmp))) return bail(rc);
+    HIPC(c, hipGetLastError());
+    if ((rc = exclusive_scan(c, ing.clean, d_before, n_rec + 1u, tmp.v))) return rc;
+    if ((rc = exclusive_scan(c, ing.raw_bytes, d_raw_before, n_rec + 1u, tmp.v))) return rc;
     uint32_t n_clean = 0, rmax_in = 0, raw_total = 0;
-    ING(hipMemcpyAsync(&n_clean, d_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
-    ING(hipMemcpyAsync(&raw_total, d_raw_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
-    ING(hipMemcpyAsync(&rmax_in, ing.meta, 4, hipMemcpyDeviceToHost, c->stream));
-    ING(hipStreamSynchronize(c->stream));
+    HIPC(c, hipMemcpyAsync(&n_clean, d_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&raw_total, d_raw_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(&rmax_in, ing.meta, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
     *used1 = cons1; *used2 = cons2;
     const uint32_t n_dirty = n_rec - n_clean;
     PairPackOut o{};
-    if (n_clean) {
-        uint32_t rmax, nw, wb, wq;
-        tile_geometry(c->plan, rmax_in, rmax, nw, wb, wq);
-        const uint32_t n_tiles = (n_clean + F2Q_TILE - 1) / F2Q_TILE;
-        if ((rc = dev_alloc(c, (size_t)n_tiles * wb * F2Q_TILE, &o.bases, b->allocs, 0))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_tiles * wq * F2Q_TILE, &o.qual, b->allocs, 0))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_tiles * F2Q_TILE, &o.len, b->allocs, 0xFF))) return bail(rc);
-        if (c->prm.mode == 1 && (rc = dev_alloc(c, (size_t)n_tiles * F2Q_TILE, &o.c_index, b->allocs, 0))) return bail(rc);
-        o.wb = wb; o.wq = wq;
-        b->pb.n_slots = (uint64_t)n_tiles * F2Q_TILE; b->pb.n_tiles = n_tiles; b->pb.wb = wb; b->pb.wq = wq; b->pb.rmax = rmax;
-        b->pb.planar_nw = nw; b->pb.bases = o.bases; b->pb.qual = o.qual; b->pb.len = o.len; b->pb.index = o.c_index;
-        b->dev_bytes += (uint64_t)n_tiles * F2Q_TILE * ((wb + wq) * 4 + 2);
-    }
+    if ((rc = alloc_tile_planes(c, b.get(), own.v, n_clean, rmax_in, o))) return rc;
     if (n_dirty) {
-        if ((rc = dev_alloc(c, (size_t)raw_total + 16, &o.raw, b->allocs, 0))) return bail(rc);
-        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_off, b->allocs))) return bail(rc);
+        if ((rc = dev_alloc(c, (size_t)raw_total + 16, &o.raw, own.v, 0))) return rc;
+        if ((rc = dev_alloc(c, (size_t)n_dirty, &o.g_off, own.v))) return rc;
         for (uint32_t **p : {&o.g_len, &o.g_qlen, &o.g_len1, &o.g_qlen1, &o.g_index})
-            if ((rc = dev_alloc(c, (size_t)n_dirty, p, b->allocs))) return bail(rc);
+            if ((rc = dev_alloc(c, (size_t)n_dirty, p, own.v))) return rc;
         b->rb.n = n_dirty; b->rb.raw = o.raw; b->rb.off = o.g_off; b->rb.len = o.g_len; b->rb.qlen = o.g_qlen;
         b->rb.len1 = o.g_len1; b->rb.qlen1 = o.g_qlen1; b->rb.index = o.g_index;
         b->dev_bytes += (uint64_t)raw_total + (uint64_t)n_dirty * 28;
@@ -1594,23 +1605,24 @@ static int block_from_pairs_device(f2q_ctx *c, const uint8_t *fq1, size_t n1, co
     }
     b->n_general = n_dirty;
     hipLaunchKernelGGL(k_pack_paired, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan, d_before, d_raw_before, o);
-    ING(hipGetLastError());
-    ING(hipStreamSynchronize(c->stream));             // scratch dies with this frame
-#undef ING
-    free_all(c, tmp);
-    *out = b;
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipStreamSynchronize(c->stream));         // scratch dies with this frame
+    b->allocs.swap(own.v); *out = b.release();
     return F2Q_OK;
 }
 
-// byte offset behind line `n_lines` of buf (the whole buffer when it holds fewer newlines)
-static size_t after_lines(const uint8_t *buf, size_t nbytes, uint64_t n_lines)
+// steps over up to k newlines of buf[pos, n): how many it saw, and the offset behind the last of them (n when the text
+// ends before the k-th)
+struct LineStep { size_t pos; uint64_t seen; };
+static LineStep skip_lines(const uint8_t *buf, size_t n, size_t pos, uint64_t k)
 {
-    size_t pos = 0;
-    for (uint64_t k = 0; k < n_lines && pos < nbytes; k++) {
-        const uint8_t *nl = (const uint8_t *)memchr(buf + pos, '\n', nbytes - pos);
-        pos = nl ? (size_t)(nl - buf) + 1 : nbytes;
+    uint64_t seen = 0;
+    while (seen < k && pos < n) {
+        const uint8_t *nl = (const uint8_t *)memchr(buf + pos, '\n', n - pos);
+        if (!nl) { pos = n; break; }
+        pos = (size_t)(nl - buf) + 1; seen++;
     }
-    return pos;
+    return LineStep{pos, seen};
 }
 
 // a window of each text (each below 1 GiB) -> a block of pairs; the host twin under F2Q_HOST_PACK=1
@@ -1621,7 +1633,7 @@ static int pair_block(f2q_ctx *c, const uint8_t *fq1, size_t n1, const uint8_t *
     frame_fastq(fq1, n1, r1); frame_fastq(fq2, n2, r2);
     const size_t n = std::min(r1.size(), r2.size());
     r1.resize(n); r2.resize(n);
-    *used1 = after_lines(fq1, n1, 4 * (uint64_t)n); *used2 = after_lines(fq2, n2, 4 * (uint64_t)n);
+    *used1 = skip_lines(fq1, n1, 0, 4 * (uint64_t)n).pos; *used2 = skip_lines(fq2, n2, 0, 4 * (uint64_t)n).pos;
     HostPacked hp;
     pack_pairs(c->plan, r1, r2, hp);
     return block_from_packed(c, hp, n, out);
@@ -1632,7 +1644,7 @@ static const size_t F2Q_PAIR_WINDOW = (size_t)1 << 30;      // most text of one 
 extern "C" int f2q_block_from_fastq_paired(f2q_ctx *c, const uint8_t *fastq1, size_t n1, const uint8_t *fastq2, size_t n2, f2q_block **out)
 {
     if (!c || !out || (!fastq1 && n1) || (!fastq2 && n2)) return F2Q_EINVAL;
-    if (!c->n_mate1) return fail(c, F2Q_ESTATE, "not a paired context: call f2q_set_mate2 first");
+    if (int rc = paired_only(c)) return rc;
     if (n1 >= F2Q_PAIR_WINDOW || n2 >= F2Q_PAIR_WINDOW) return fail(c, F2Q_EINVAL, "a resident block of pairs holds less than 1 GiB of text per mate");
     HIPC(c, hipSetDevice(c->device));
     size_t u1, u2;
@@ -1643,7 +1655,7 @@ extern "C" int f2q_count_block_paired(f2q_ctx *c, const uint8_t *fastq1, size_t 
                                       size_t *consumed1, size_t *consumed2, f2q_timing *t)
 {
     if (!c || (!fastq1 && n1) || (!fastq2 && n2)) return F2Q_EINVAL;
-    if (!c->n_mate1) return fail(c, F2Q_ESTATE, "not a paired context: call f2q_set_mate2 first");
+    if (int rc = paired_only(c)) return rc;
     HIPC(c, hipSetDevice(c->device));
     if (t) { memset(t, 0, sizeof *t); HIPC(c, hipEventRecord(c->ev_a, c->stream)); }
     if (consumed1) *consumed1 = 0;
@@ -1696,7 +1708,7 @@ extern "C" int f2q_text_upload(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, 
 extern "C" int f2q_count_text(f2q_ctx *c, f2q_text *txt, size_t *consumed, f2q_timing *t)
 {
     if (!c || !txt) return F2Q_EINVAL;
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
+    if (int rc = single_only(c)) return rc;
     HIPC(c, hipSetDevice(c->device));
     if (t) { memset(t, 0, sizeof *t); HIPC(c, hipEventRecord(c->ev_a, c->stream)); }
     if (consumed) *consumed = 0;
@@ -1739,9 +1751,9 @@ static int inflate_members(f2q_ctx *c, const uint8_t *d_in, uint64_t in_cap, con
     res.assign(n, BgzfResult{});
     *first_bad = n;
     if (n == 0) return F2Q_OK;
-    std::vector<void *> tmp;
+    DevScope tmp(c);
     BgzfResult *d_res;
-    int rc = dev_alloc(c, n, &d_res, tmp, 0xFF);
+    int rc = dev_alloc(c, n, &d_res, tmp.v, 0xFF);
     if (rc) return rc;
     // LDS holds two workgroups per CU; each walks its share of the members
     const uint32_t grid = std::min<uint32_t>(n, (uint32_t)c->n_cu * 2u);
@@ -1749,7 +1761,6 @@ static int inflate_members(f2q_ctx *c, const uint8_t *d_in, uint64_t in_cap, con
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_res, (size_t)n * sizeof(BgzfResult), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    free_all(c, tmp);
     if (e != hipSuccess) return fail(c, F2Q_EHIP, std::string("k_inflate_bgzf: ") + hipGetErrorString(e));
     for (uint32_t i = 0; i < n; i++) if (res[i].status != F2Q_INF_OK) { *first_bad = i; break; }
     return F2Q_OK;
@@ -1766,6 +1777,41 @@ static void members_tail(const std::vector<BgzfMember> &ms, const std::vector<Bg
     for (uint32_t i = n; last_byte < 0 && i-- > 0;) if (ms[i].isize) last_byte = (int)res[i].last_byte;
 }
 
+// The table entry of the BGZF member at p (avail bytes from there on): its deflate bytes start at in_base + header, its
+// text goes to out_off; CRC and ISIZE come from its trailer.  -1: no whole member there; 0: damaged, the block size has
+// no room for header and trailer; 1: m and bsize are set.
+static int bgzf_entry(const uint8_t *p, size_t avail, uint64_t in_base, uint64_t out_off, BgzfMember &m, uint32_t &bsize)
+{
+    uint32_t hdr;
+    if (!TextSource::bgzf_member(p, avail, bsize, hdr) || bsize > avail) return -1;
+    if (bsize < hdr + 8) return 0;
+    const uint8_t *t = p + bsize - 8;
+    m = BgzfMember{};
+    m.in_off = in_base + hdr; m.in_len = bsize - hdr - 8; m.out_off = (uint32_t)out_off;
+    m.crc = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
+    m.isize = t[4] | (t[5] << 8) | (t[6] << 16) | ((uint32_t)t[7] << 24);
+    return 1;
+}
+
+// The member index of a BGZF file (compressed offsets, text sizes) cut into runs of whole members: a new run starts
+// when the member would take the run's text past text_cap or, with a byte_cap, its compressed bytes and member table
+// past byte_cap.  A run of empty members keeps its place.
+struct MemberRun { size_t m0, m1; uint64_t text, bytes; };
+static std::vector<MemberRun> member_runs(const std::vector<uint64_t> &off, const std::vector<uint32_t> &isz, uint64_t file_size,
+                                          uint64_t text_cap, uint64_t byte_cap = 0)
+{
+    std::vector<MemberRun> runs;
+    for (size_t i = 0; i < off.size(); i++) {
+        const uint64_t bs = (i + 1 < off.size() ? off[i + 1] : file_size) - off[i];
+        if (runs.empty() || runs.back().text + isz[i] > text_cap ||
+            (byte_cap && runs.back().bytes + bs + sizeof(BgzfMember) * (runs.back().m1 - runs.back().m0 + 1) + 16 > byte_cap))
+            runs.push_back(MemberRun{i, i, 0, 0});
+        MemberRun &r = runs.back();
+        r.m1 = i + 1; r.text += isz[i]; r.bytes += bs;
+    }
+    return runs;
+}
+
 extern "C" int f2q_text_from_bgzf(f2q_ctx *c, const uint8_t *bgzf, size_t nbytes, f2q_text **out)
 {
     if (!c || !out || (!bgzf && nbytes)) return F2Q_EINVAL;
@@ -1775,15 +1821,10 @@ extern "C" int f2q_text_from_bgzf(f2q_ctx *c, const uint8_t *bgzf, size_t nbytes
     uint64_t text = 0;
     bool bad = false;
     for (size_t pos = 0; pos < nbytes;) {
-        uint32_t bsize, hdr;
-        if (!TextSource::bgzf_member(bgzf + pos, nbytes - pos, bsize, hdr) || bsize > nbytes - pos)
-            return fail(c, F2Q_EUNSUPPORTED, "f2q_text_from_bgzf: the buffer is not a run of whole BGZF members");
-        if (bsize < hdr + 8) { bad = true; break; }
-        const uint8_t *t = bgzf + pos + bsize - 8;
-        BgzfMember m{};
-        m.in_off = pos + hdr; m.in_len = bsize - hdr - 8; m.out_off = (uint32_t)text;
-        m.crc = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
-        m.isize = t[4] | (t[5] << 8) | (t[6] << 16) | ((uint32_t)t[7] << 24);
+        uint32_t bsize; BgzfMember m;
+        const int got = bgzf_entry(bgzf + pos, nbytes - pos, pos, text, m, bsize);
+        if (got < 0) return fail(c, F2Q_EUNSUPPORTED, "f2q_text_from_bgzf: the buffer is not a run of whole BGZF members");
+        if (got == 0) { bad = true; break; }
         if (m.isize > F2Q_INF_OUT_BYTES) return fail(c, F2Q_EUNSUPPORTED, "f2q_text_from_bgzf: a member holds more than 64 KiB of text");
         text += m.isize;
         if (text > ((uint64_t)1 << 30)) return fail(c, F2Q_EINVAL, "f2q_text_from_bgzf: at most 1 GiB of text (the device framing indexes a text with 32 bits)");
@@ -1795,7 +1836,7 @@ extern "C" int f2q_text_from_bgzf(f2q_ctx *c, const uint8_t *bgzf, size_t nbytes
     uint8_t *d_in; BgzfMember *d_mem;
     int rc = dev_alloc(c, nbytes + 64, &d_in, tmp);
     if (!rc) rc = dev_upload(c, ms.data(), ms.size(), &d_mem, tmp);
-    if (!rc && nbytes) { hipError_t e = hipMemcpyAsync(d_in, bgzf, nbytes, hipMemcpyHostToDevice, c->stream); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
+    if (!rc && nbytes) rc = hip_rc(c, hipMemcpyAsync(d_in, bgzf, nbytes, hipMemcpyHostToDevice, c->stream));
     f2q_text *t = new f2q_text();
     const size_t n_chunks = ((size_t)text + F2Q_NL_CHUNK - 1) / F2Q_NL_CHUNK;
     t->cap = n_chunks * F2Q_NL_CHUNK + 16;
@@ -1863,7 +1904,7 @@ static void free_staged(f2q_ctx *c, Staged &st, hipStream_t s)
 {
     if (!st.buf) return;
     (void)hipStreamSynchronize(s);
-    std::vector<void *> v{st.buf}; free_all(c, v);
+    { DevScope own(c, st.buf); }
     st = Staged();
 }
 
@@ -1970,22 +2011,21 @@ struct PieceStream {
     }
 };
 
-// Count text that was sent ahead.  It starts `off` bytes into the staged buffer, where the tail_n host bytes at `tail`
-// (a carried tail) are first put on c->stream in front of the staged bytes; n bytes in all, the last one last_byte.
-// The up to 15 bytes between the 16-byte boundary below the text and the text are filled with 'x': they lengthen the
-// first line, a record's header line, which is never looked at (fast2q.py:324-328 takes lines 2 and 4 only).  Unless
-// that fails, the buffer belongs to the block from here on; *used counts from the start of the text.
-static int count_staged(f2q_ctx *c, Staged &st, size_t off, const uint8_t *tail, size_t tail_n, size_t n, uint8_t last_byte,
-                        uint64_t max_records, size_t *used, f2q_timing *one)
+// Count n bytes of text that are in device memory (or on their way there), `off` bytes into the buffer st; their last byte
+// is last_byte.  The tail_n host bytes at `tail` (a carried tail) are first put on c->stream at the head of the text.  The
+// up to 15 bytes between the 16-byte boundary below the text and the text are filled with 'x': they lengthen the first
+// line, a record's header line, which is never looked at (fast2q.py:324-328 takes lines 2 and 4 only).  With `keep` the
+// caller keeps the buffer; otherwise, unless the call fails before framing, it belongs to the block from here on and st
+// is emptied.  *used counts from the start of the text.
+static int count_dev_text(f2q_ctx *c, Staged &st, bool keep, size_t off, const uint8_t *tail, size_t tail_n, size_t n, uint8_t last_byte,
+                          uint64_t max_records, size_t *used, f2q_timing *one)
 {
     const size_t al = off & ~(size_t)15, lead = off - al;
     uint8_t *d = (uint8_t *)st.buf;
-    hipError_t e = hipSuccess;
-    if (tail_n) e = hipMemcpyAsync(d + off, tail, tail_n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && lead) e = hipMemsetAsync(d + al, 'x', lead, c->stream);
-    if (e != hipSuccess) return fail(c, F2Q_EHIP, hipGetErrorString(e));
-    DevText pre; pre.buf = st.buf; pre.cap = st.cap; pre.text = d + al; pre.last_byte = last_byte;
-    st = Staged();
+    if (tail_n) HIPC(c, hipMemcpyAsync(d + off, tail, tail_n, hipMemcpyHostToDevice, c->stream));
+    if (lead) HIPC(c, hipMemsetAsync(d + al, 'x', lead, c->stream));
+    DevText pre; pre.buf = st.buf; pre.cap = st.cap; pre.text = d + al; pre.last_byte = last_byte; pre.borrowed = keep;
+    if (!keep) st = Staged();
     size_t used_dev = 0;
     const int rc = count_window(c, nullptr, lead + n, &pre, &used_dev, one, max_records);
     *used = used_dev > lead ? used_dev - lead : 0;
@@ -2036,19 +2076,6 @@ static size_t skip_piece(const uint8_t *p, size_t n, int threads, uint64_t *n_re
     return n;
 }
 
-// Count `n` bytes of text that start `off` bytes into the device buffer buf (cap bytes); the caller keeps the buffer.
-// As in count_staged, the bytes between the 16-byte boundary below the text and the text become 'x'.
-static int count_dev_text(f2q_ctx *c, uint8_t *buf, size_t cap, size_t off, size_t n, uint8_t last_byte, size_t *used, f2q_timing *one)
-{
-    const size_t al = off & ~(size_t)15, lead = off - al;
-    if (lead) HIPC(c, hipMemsetAsync(buf + al, 'x', lead, c->stream));
-    DevText pre; pre.buf = buf; pre.cap = cap; pre.text = buf + al; pre.last_byte = last_byte; pre.borrowed = true;
-    size_t used_dev = 0;
-    const int rc = count_window(c, nullptr, lead + n, &pre, &used_dev, one);
-    *used = used_dev > lead ? used_dev - lead : 0;
-    return rc;
-}
-
 // f2q_count_file on a BGZF file with F2Q_DEVICE_INFLATE=1 (count_file_impl decides).  Pieces are runs of whole members
 // with at most CH bytes of text, as piece_map cuts them; the reader thread only preads each run's compressed bytes into
 // a pinned slot behind its member table, and PieceStream sends both to the device ahead.  k_inflate_bgzf writes the
@@ -2062,21 +2089,13 @@ static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, cons
     CH = std::min<size_t>(CH, (size_t)512 << 20);
     // the pieces: text <= CH, member table + compressed bytes <= PB (a run of empty members takes little text)
     const size_t PB = std::max<size_t>(CH, (size_t)1 << 20);
-    struct Run { size_t m0, m1; uint64_t text, bytes; };
-    std::vector<Run> runs;
-    for (size_t i = 0; i < off.size(); i++) {
-        const uint64_t bs = (i + 1 < off.size() ? off[i + 1] : src.file_size) - off[i];
-        if (runs.empty() || runs.back().text + isz[i] > CH || runs.back().bytes + bs + sizeof(BgzfMember) * (runs.back().m1 - runs.back().m0 + 1) + 16 > PB)
-            runs.push_back(Run{i, i, 0, 0});
-        Run &r = runs.back();
-        r.m1 = i + 1; r.text += isz[i]; r.bytes += bs;
-    }
+    const std::vector<MemberRun> runs = member_runs(off, isz, src.file_size, CH, PB);
     // what the reader leaves for each slot: the member table (also at the head of the slot) and a damaged header
     struct SlotInfo { std::vector<BgzfMember> ms; uint64_t text = 0; bool bad = false, io = false; };
     SlotInfo info[PieceStream::NSLOT];
     auto fill = [&](uint64_t j, uint8_t *p, Piece &pc) {
         if (j >= runs.size()) { pc.last = true; return; }
-        const Run &r = runs[j];
+        const MemberRun &r = runs[j];
         SlotInfo &si = info[pc.slot];
         si = SlotInfo();
         const size_t nm = r.m1 - r.m0, T = (nm * sizeof(BgzfMember) + 15) & ~(size_t)15;
@@ -2096,13 +2115,9 @@ static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, cons
         for (size_t i = r.m0; i < r.m1; i++) {
             const size_t at = (size_t)(off[i] - off[r.m0]);
             const uint32_t want = (uint32_t)((i + 1 < off.size() ? off[i + 1] : src.file_size) - off[i]);
-            uint32_t bsize = 0, hdr = 0;
-            if (!TextSource::bgzf_member(z + at, r.bytes - at, bsize, hdr) || bsize != want || bsize < hdr + 8) { si.bad = true; break; }
-            const uint8_t *tl = z + at + bsize - 8;
-            BgzfMember m{};
-            m.in_off = T + at + hdr; m.in_len = bsize - hdr - 8; m.out_off = (uint32_t)si.text;
-            m.crc = tl[0] | (tl[1] << 8) | (tl[2] << 16) | ((uint32_t)tl[3] << 24);
-            m.isize = isz[i];
+            uint32_t bsize = 0; BgzfMember m;
+            if (bgzf_entry(z + at, r.bytes - at, T + at, si.text, m, bsize) != 1 || bsize != want) { si.bad = true; break; }
+            m.isize = isz[i];                        // (what the runs were cut by)
             si.ms.push_back(m); si.text += m.isize;
         }
         if (!si.ms.empty()) memcpy(p, si.ms.data(), si.ms.size() * sizeof(BgzfMember));
@@ -2113,18 +2128,17 @@ static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, cons
     if (rc) return rc;
     f2q_timing sum; memset(&sum, 0, sizeof sum);
     double inflate_ms = 0;
-    uint8_t *prev = nullptr; size_t prev_cap = 0;   // the text buffer of the last piece; its tail [carry_at, carry_at + carry_n) is carried
+    DevScope text(c);                               // owns the text buffer of the last piece ...
+    Staged prev;                                    // ... this one; its tail [carry_at, carry_at + carry_n) is carried
     size_t carry_at = 0, carry_n = 0;
     uint8_t carry_last = 0;
     bool truncated = false;
-    std::vector<void *> hold;                        // prev, for free_all
-    auto release_prev = [&]() { if (prev) { hold.assign(1, prev); free_all(c, hold); prev = nullptr; } };
     for (;;) {
         const Piece pc = ps.next();
         f2q_timing one; memset(&one, 0, sizeof one);
         if (pc.last) {                               // the last partial record, counted in place (:392)
             size_t used = 0;
-            if (carry_n) rc = count_dev_text(c, prev, prev_cap, carry_at, carry_n, carry_last, &used, &one);
+            if (carry_n) rc = count_dev_text(c, prev, true, carry_at, nullptr, 0, carry_n, carry_last, ~0ull, &used, &one);
             timing_add(sum, one);
             ps.done(pc, true);
             break;
@@ -2144,19 +2158,16 @@ static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, cons
         if (!rc && !d_in) {                          // not sent ahead: copy it now
             rc = dev_get(c, pc.n + 64, &zb);
             if (!rc) { scratch.push_back(zb); d_in = (const uint8_t *)zb; in_cap = pc.n + 64; }
-            if (!rc) { hipError_t e = hipMemcpyAsync(zb, ps.text(pc), pc.n, hipMemcpyHostToDevice, c->stream); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
+            if (!rc) rc = hip_rc(c, hipMemcpyAsync(zb, ps.text(pc), pc.n, hipMemcpyHostToDevice, c->stream));
         }
-        if (!rc && carry_n) {
-            hipError_t e = hipMemcpyAsync((uint8_t *)tb + hr - carry_n, prev + carry_at, carry_n, hipMemcpyDeviceToDevice, c->stream);
-            if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e));
-        }
+        if (!rc && carry_n) rc = hip_rc(c, hipMemcpyAsync((uint8_t *)tb + hr - carry_n, (uint8_t *)prev.buf + carry_at, carry_n, hipMemcpyDeviceToDevice, c->stream));
         std::vector<BgzfResult> res;
         uint32_t fb = nm;
         if (!rc) rc = inflate_members(c, d_in, in_cap, (const BgzfMember *)d_in, nm, (uint8_t *)tb + hr, si.text, res, &fb);
         free_all(c, scratch);
         inflate_ms += now_ms() - i0;
-        release_prev();
-        if (tb) { prev = (uint8_t *)tb; prev_cap = cap; }
+        free_all(c, text.v); prev = Staged();
+        if (tb) { text.v.push_back(tb); prev.buf = tb; prev.cap = cap; }
         if (rc) { ps.done(pc, true); break; }
         const bool bad = si.bad || fb < nm;
         const uint64_t text_n = fb < nm ? si.ms[fb].out_off : si.text;
@@ -2168,12 +2179,12 @@ static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, cons
         if (nl) {                                    // whole lines only: a line is never split between blocks
             // the framing zeroes the bytes behind the window: the partial line there is kept aside and put back
             const size_t cut = carry_n + (size_t)nl, rest = have - cut;
-            void *aside = nullptr;
-            if (rest) rc = dev_get(c, rest, &aside);
-            if (!rc && rest) { hipError_t e = hipMemcpyAsync(aside, prev + start + cut, rest, hipMemcpyDeviceToDevice, c->stream); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
-            if (!rc) rc = count_dev_text(c, prev, prev_cap, start, cut, 0x0a, &used, &one);
-            if (!rc && rest) { hipError_t e = hipMemcpyAsync(prev + start + cut, aside, rest, hipMemcpyDeviceToDevice, c->stream); if (e != hipSuccess) rc = fail(c, F2Q_EHIP, hipGetErrorString(e)); }
-            if (aside) { hold.assign(1, aside); free_all(c, hold); }
+            DevScope own(c);
+            uint8_t *aside = nullptr, *const rest_at = (uint8_t *)prev.buf + start + cut;
+            if (rest) rc = dev_alloc(c, rest, &aside, own.v);
+            if (!rc && rest) rc = hip_rc(c, hipMemcpyAsync(aside, rest_at, rest, hipMemcpyDeviceToDevice, c->stream));
+            if (!rc) rc = count_dev_text(c, prev, true, start, nullptr, 0, cut, 0x0a, ~0ull, &used, &one);
+            if (!rc && rest) rc = hip_rc(c, hipMemcpyAsync(rest_at, aside, rest, hipMemcpyDeviceToDevice, c->stream));
             timing_add(sum, one);
         }
         carry_at = start + used; carry_n = have - used;
@@ -2182,7 +2193,6 @@ static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, cons
         if (rc || bad) break;
     }
     ps.close();
-    release_prev();
     if (t) *t = sum;
     if (c->trace) fprintf(stderr, "[f2q trace] %s (bgzf-device, %d io threads): pinned %.1f ms, reader busy %.1f ms, waited for reader %.1f ms, inflate %.1f ms, frame+pack %.1f ms (H2D copy %.1f), count %.1f ms, free %.1f ms\n",
                           path, src.n_threads, ps.pin_ms, ps.read_ms, ps.wait_ms, inflate_ms, c->tr_frame, c->tr_copy, c->tr_count, c->tr_free);
@@ -2194,10 +2204,9 @@ static int count_bgzf_device(f2q_ctx *c, const char *path, TextSource &src, cons
 static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t world, f2q_timing *t)
 {
     if (!c || !path || world == 0 || rank >= world) return F2Q_EINVAL;
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
+    if (int rc = single_only(c)) return rc;
     HIPC(c, hipSetDevice(c->device));
-    size_t CH = (size_t)256 << 20;                 // bytes of text per piece; F2Q_FILE_CHUNK overrides (tests)
-    { const char *e = getenv("F2Q_FILE_CHUNK"); if (e && atol(e) >= 4096) CH = (size_t)atol(e); }
+    size_t CH = file_chunk_bytes((size_t)256 << 20);
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }
     const size_t HEAD = 64 << 10;                  // room in front of each piece for the carried tail
@@ -2212,7 +2221,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
     }
     // The text of piece k+1 is copied to the device while piece k is framed, packed and counted.  Its carried tail is
     // only known once piece k is framed, so the piece lands HEAD bytes into its device buffer and the tail is put in
-    // front of it later (count_staged).
+    // front of it later (count_dev_text).
     PieceStream ps(c);
     int rc = ps.start(HEAD, HEAD + CH, world == 1 && !c->host_pack && !getenv("F2Q_NO_STAGING"),
                       [&](uint64_t, uint8_t *p, Piece &pc) { pc.n = src.read(p, CH); pc.last = pc.n == 0; });
@@ -2242,7 +2251,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
             if (!eof || src.truncated()) while (cut > 0 && base[cut - 1] != 0x0a) cut--;
             if (cut) {
                 if (ps.cur.buf && carry.size() <= HEAD)
-                    rc = count_staged(c, ps.cur, HEAD - carry.size(), carry.data(), carry.size(), cut, base[cut - 1], ~0ull, &used, &one);
+                    rc = count_dev_text(c, ps.cur, false, HEAD - carry.size(), carry.data(), carry.size(), cut, base[cut - 1], ~0ull, &used, &one);
                 else if (piece_no % world == rank) rc = f2q_count_block(c, base, cut, &used, &one);
                 else {                             // another rank's piece: only its framing matters here
                     uint64_t n_rec = 0;
@@ -2305,24 +2314,17 @@ struct MateStream {
     bool has_record() const
     {
         const size_t n = whole();
-        size_t pos = 0; int lines = 0;
-        while (pos < n && lines < 4) {
-            const uint8_t *nl = (const uint8_t *)memchr(data() + pos, 0x0a, n - pos);
-            lines++;
-            pos = nl ? (size_t)(nl - data()) + 1 : n;
-        }
-        return lines == 4;
+        const LineStep s = skip_lines(data(), n, 0, 3);
+        return s.seen == 3 && s.pos < n;
     }
 };
 
 extern "C" int f2q_count_file_paired(f2q_ctx *c, const char *path1, const char *path2, f2q_timing *t)
 {
     if (!c || !path1 || !path2) return F2Q_EINVAL;
-    if (!c->n_mate1) return fail(c, F2Q_ESTATE, "not a paired context: call f2q_set_mate2 first");
+    if (int rc = paired_only(c)) return rc;
     HIPC(c, hipSetDevice(c->device));
-    size_t CH = (size_t)64 << 20;                  // bytes of text per piece and file; F2Q_FILE_CHUNK overrides (tests)
-    { const char *e = getenv("F2Q_FILE_CHUNK"); if (e && atol(e) >= 4096) CH = (size_t)atol(e); }
-    CH = std::min(CH, F2Q_PAIR_WINDOW / 4);
+    const size_t CH = std::min(file_chunk_bytes((size_t)64 << 20), F2Q_PAIR_WINDOW / 4);      // per piece and file
     MateStream m[2];
     { std::string err; if (m[0].src.open(path1, err) != 0) return fail(c, F2Q_EIO, err); }
     { std::string err; if (m[1].src.open(path2, err) != 0) return fail(c, F2Q_EIO, err); }
@@ -2400,16 +2402,11 @@ static int piece_map(TextSource &src, const char *path, uint64_t piece_bytes, Pi
     std::vector<uint64_t> off; std::vector<uint32_t> isz;
     if (!src.bgzf_index(off, isz)) return F2Q_EUNSUPPORTED;
     pm.bgzf = true;
-    uint64_t acc = 0;
-    for (size_t i = 0; i < off.size(); i++) {
-        if (pm.c_off.empty() || acc + isz[i] > piece_bytes) {
-            if (!pm.c_off.empty() && acc == 0) { pm.c_off.back() = pm.c_off.back(); }      // (an empty run keeps its place)
-            pm.c_off.push_back(off[i]); pm.text.push_back(0); acc = 0;
-        }
-        acc += isz[i]; pm.text.back() = acc;
+    for (const MemberRun &r : member_runs(off, isz, src.file_size, piece_bytes)) {
+        pm.c_off.push_back(off[r.m0]); pm.text.push_back(r.text);
+        pm.max_text = std::max(pm.max_text, r.text);
     }
     pm.n = pm.c_off.size();
-    for (uint64_t t : pm.text) pm.max_text = std::max(pm.max_text, t);
     { std::lock_guard<std::mutex> g(mu); last_key = key; last = pm; }
     return F2Q_OK;
 }
@@ -2490,7 +2487,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
                                 const uint64_t *census, uint64_t n_pieces, f2q_timing *t)
 {
     if (!c || !path || !census || world == 0 || rank >= world || !piece_bytes_ok(piece_bytes)) return F2Q_EINVAL;
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
+    if (int rc = single_only(c)) return rc;
     HIPC(c, hipSetDevice(c->device));
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }
@@ -2539,7 +2536,8 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
                 const size_t g = src.read(p + n, (size_t)std::min<uint64_t>((uint64_t)1 << 16, sp.size + MARGIN - n));
                 if (!g) { more = false; if (src.truncated()) pc.ok = false; break; }
                 n += g;
-                while (seen < 4 && o < n) { const uint8_t *q = (const uint8_t *)memchr(p + o, 0x0a, n - o); if (!q) { o = n; break; } o = (size_t)(q - p) + 1; seen++; }
+                const LineStep s = skip_lines(p, n, o, 4 - seen);
+                o = s.pos; seen += (size_t)s.seen;
             }
             // (for the check below: "the file goes on behind what was read" <=> the margin filled up without 4 newlines)
             want = n; sp.base = 0;
@@ -2547,14 +2545,10 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
             if (file_goes_on) pc.ok = false;
         }
         // the first record start: the line after the one cut by the piece's start, then `skip_lines` more
-        size_t a = 0;
-        uint64_t skip = jb.skip_lines + (jb.at_line_start ? 0 : 1);
-        while (skip && a < n) { const uint8_t *q = (const uint8_t *)memchr(p + a, 0x0a, n - a); if (!q) { a = n; break; } a = (size_t)(q - p) + 1; skip--; }
+        const size_t a = skip_lines(p, n, 0, jb.skip_lines + (jb.at_line_start ? 0 : 1)).pos;
         // the margin must hold the rest of the last record (4 more newlines, or the end of the file)
         if (!pm.bgzf && sp.base + want < src.file_size) {
-            size_t seen = 0, o = (size_t)sp.size;
-            while (seen < 4 && o < n) { const uint8_t *q = (const uint8_t *)memchr(p + o, 0x0a, n - o); if (!q) break; o = (size_t)(q - p) + 1; seen++; }
-            if (seen < 4) pc.ok = false;           // lines too long for the margin: the caller falls back
+            if (skip_lines(p, n, (size_t)sp.size, 4).seen < 4) pc.ok = false;           // lines too long for the margin: the caller falls back
         }
         pc.n = n; pc.a = a; pc.max_records = jb.n_records; pc.first_read = jb.first_read;
     });
@@ -2568,7 +2562,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
             size_t used = 0;
             c->reads_seen = pc.first_read;
             uint8_t *base = ps.text(pc) + pc.a;
-            if (ps.cur.buf) rc = count_staged(c, ps.cur, HEAD + pc.a, nullptr, 0, pc.n - pc.a, base[pc.n - pc.a - 1], pc.max_records, &used, &one);
+            if (ps.cur.buf) rc = count_dev_text(c, ps.cur, false, HEAD + pc.a, nullptr, 0, pc.n - pc.a, base[pc.n - pc.a - 1], pc.max_records, &used, &one);
             else rc = count_window(c, base, pc.n - pc.a, nullptr, &used, &one, pc.max_records);
             timing_add(sum, one);
         }
@@ -2687,7 +2681,7 @@ extern "C" int f2q_synth_create(f2q_ctx *c, const f2q_synth *s, f2q_block **out)
 {
     if (!c || !s || !out) return F2Q_EINVAL;
     HIPC(c, hipSetDevice(c->device));
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls");
+    if (int rc = single_only(c)) return rc;
     SynthDev d; int rc = synth_to_dev(c, s, d);
     if (rc) return rc;
     const int R = d.read_len;

@@ -68,6 +68,46 @@ def test_bgzf_pieces_and_census_on_the_host(tmp_path):
     assert L.f2q_file_pieces(os.fsencode(str(other)), 1 << 16, C.byref(n), C.byref(ok)) == 0 and ok.value == 0 and n.value == 0
 
 
+def test_bgzf_pieces_follow_the_member_text_sizes(tmp_path):
+    """the cut of a BGZF file into pieces is the one the ISIZE fields give by the rule "a new piece when adding the member
+    would exceed piece_bytes": about 40 members, some runs filling a piece exactly, two empty members in a row in the
+    middle and the EOF marker at the end; and the census of every rank's pieces adds up to the newlines of the text"""
+    import ctypes as C
+    import struct
+    import numpy as np
+    from conftest import bgzf_bytes
+    import __graft_entry__ as g
+    g.build()
+    L = binding.load()
+    piece = 65536
+    text = b"".join(b"@r%d\nACGTACGTAC\n+\nIIIIIIIIII\n" % i for i in range(22000))
+    cut = 20 * 16384                                   # four members of 16384 bytes fill a piece to the byte
+    data = bgzf_bytes(text[:cut], block=16384) + bgzf_bytes(b"") + bgzf_bytes(text[cut:], block=20480)
+    isize, pos = [], 0
+    while pos < len(data):                             # (bgzf_bytes: BSIZE - 1 at offset 16 of a member, ISIZE in its last 4 bytes)
+        bsize = struct.unpack_from("<H", data, pos + 16)[0] + 1
+        isize.append(struct.unpack_from("<I", data, pos + bsize - 4)[0])
+        pos += bsize
+    assert 38 <= len(isize) <= 42 and isize[-1] == 0 and (0, 0) in zip(isize, isize[1:-1]) and sum(isize) == len(text)
+    expect, acc = 0, 0
+    for s in isize:
+        if expect == 0 or acc + s > piece:
+            expect, acc = expect + 1, 0
+        acc += s
+    path = tmp_path / "x.fastq.gz"
+    path.write_bytes(data)
+    for world in (1, 3):
+        n, ok = C.c_uint64(), C.c_int()
+        assert L.f2q_file_pieces(os.fsencode(str(path)), piece, C.byref(n), C.byref(ok)) == 0
+        assert ok.value == 2 and n.value == expect
+        total = np.zeros(2 * n.value, dtype=np.uint64)
+        for rank in range(world):
+            cen = np.zeros(2 * n.value, dtype=np.uint64)
+            assert L.f2q_census_pieces(os.fsencode(str(path)), rank, world, piece, cen.ctypes.data_as(C.POINTER(C.c_uint64)), n.value) == 0
+            total += cen
+        assert int(total[0::2].sum()) == text.count(b"\n")
+
+
 def test_build_sees_every_source_file():
     import __graft_entry__ as g
     deps = {os.path.basename(d) for d in g.hip_deps()}
