@@ -21,6 +21,7 @@ EXPORTS = (
     "f2q_counts_device_ptr", "f2q_stream", "f2q_ec_size", "f2q_ec_fetch", "f2q_set_read_base", "f2q_synth_guides",
     "f2q_text_upload", "f2q_count_text", "f2q_text_free", "f2q_text_from_bgzf", "f2q_text_read",
     "f2q_set_mate2", "f2q_count_block_paired", "f2q_block_from_fastq_paired", "f2q_count_file_paired",
+    "f2q_set_assign_library", "f2q_ec_assign", "f2q_ec_fetch_assigned",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
@@ -167,6 +168,9 @@ def load(path=None):
     L.f2q_stream.argtypes = [vp]; L.f2q_stream.restype = vp
     L.f2q_ec_size.argtypes = [vp, u64p, u64p]
     L.f2q_ec_fetch.argtypes = [vp, C.c_char_p, u64p, i64p, u64p]
+    L.f2q_set_assign_library.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32]
+    L.f2q_ec_assign.argtypes = [vp, i64p, i64p, C.POINTER(Timing)]
+    L.f2q_ec_fetch_assigned.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     if path == LIB_PATH:
         _lib = L
     return L
@@ -250,6 +254,7 @@ class Counter:
             raise F2QError(rc, (self._L.f2q_last_error(None) or b"").decode())
         self._h = h
         self.n_features = 0
+        self.n_assign = 0
         self.paired = False
         if start2 is not None:
             self.set_mate2(start2, rc2)
@@ -279,14 +284,24 @@ class Counter:
         self.close()
 
     # -- library --
-    def set_features(self, seqs):
+    @staticmethod
+    def _blob(seqs):
         enc = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
         offs = np.zeros(len(enc) + 1, dtype=np.uint32)
         if enc:
             offs[1:] = np.cumsum([len(b) for b in enc], dtype=np.uint64).astype(np.uint32)
-        blob = b"".join(enc)
-        self._check(self._L.f2q_set_features(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_uint32)), len(enc)))
-        self.n_features = len(enc)
+        return b"".join(enc), offs, len(enc)
+
+    def set_features(self, seqs):
+        blob, offs, n = self._blob(seqs)
+        self._check(self._L.f2q_set_features(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        self.n_features = n
+
+    def set_assign_library(self, seqs):
+        """Extract+Count contexts: the library ec_assign matches the extracted keys against (once per context)"""
+        blob, offs, n = self._blob(seqs)
+        self._check(self._L.f2q_set_assign_library(self._h, blob, offs.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        self.n_assign = n
 
     def set_mate2(self, start2, rc2=False):
         """windows of mate 2 (paired-end samples); before set_features"""
@@ -492,5 +507,38 @@ class Counter:
                                          first.ctypes.data_as(C.POINTER(C.c_uint64))))
         raw = keys.raw
         rows = [(raw[int(offs[i]):int(offs[i + 1])].decode("latin-1"), int(counts[i]), int(first[i])) for i in range(n)]
+        rows.sort(key=lambda r: r[2])
+        return rows
+
+    def ec_assign(self, want_timing=False):
+        """match every key the Extract+Count tables hold against the assign library: (counts, stats) as Counter mode
+        would have returned them for the same reads (and the timing)"""
+        counts = np.zeros(max(self.n_assign, 1), dtype=np.int64)
+        stats = np.zeros(5, dtype=np.int64)
+        t = Timing()
+        self._check(self._L.f2q_ec_assign(self._h, counts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          stats.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(t)))
+        return (counts[:self.n_assign], stats, t.as_dict()) if want_timing else (counts[:self.n_assign], stats)
+
+    def ec_assigned(self):
+        """[(key, count, first_read, feature, mismatches)] of the last ec_assign in first-occurrence order; feature is
+        an index into the assign library, -1 (with mismatches -1) for a key assigned to none"""
+        nk, nb = C.c_uint64(), C.c_uint64()
+        self._check(self._L.f2q_ec_size(self._h, C.byref(nk), C.byref(nb)))
+        n = nk.value
+        keys = C.create_string_buffer(max(nb.value, 1))
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        first = np.zeros(max(n, 1), dtype=np.uint64)
+        feat = np.zeros(max(n, 1), dtype=np.int32)
+        dist = np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self._L.f2q_ec_fetch_assigned(self._h, feat.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  dist.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._check(self._L.f2q_ec_fetch(self._h, keys, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         counts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         first.ctypes.data_as(C.POINTER(C.c_uint64))))
+        raw = keys.raw
+        rows = [(raw[int(offs[i]):int(offs[i + 1])].decode("latin-1"), int(counts[i]), int(first[i]), int(feat[i]), int(dist[i]))
+                for i in range(n)]
         rows.sort(key=lambda r: r[2])
         return rows

@@ -604,10 +604,31 @@ F2Q_HD void gk_near(const LibDev &lib, const GkGroup &g, const KV &kv, MinTrack 
     }
 }
 
+// the regular road of match_key: a plain key of 1..31 bases as 2-bit codes against a library of regular features only.
+// `forced` marks the positions that hold a non-ACGT symbol (bit 2j for base j; nforced of them, their code stored as 0).
+// true: exact hit, idx set; false: the features within reach have been offered to t
+F2Q_HD bool match_regular(const RunDev &run, const LibDev &lib, uint64_t key, int len, uint64_t forced, int nforced, MinTrack &t, uint32_t &idx)
+{
+    if (nforced == 0) {
+        int e = lib_exact(lib, key, len);
+        if (e >= 0) { idx = (uint32_t)e; return true; }
+    }
+    // regular features: a non-ACGT query symbol mismatches every one of them
+    if (run.miss > 0 && nforced <= run.miss) lib_near(lib, key, len, forced, t);
+    return false;
+}
+// what the unique-nearest state says once every candidate has been offered (:734-750)
+F2Q_HD int match_verdict(const MinTrack &t, uint32_t &idx, int &dist)
+{
+    if (t.cnt == 1) { idx = t.idx; dist = t.best; return t.best == 0 ? 1 : 2; }
+    // best == 0 with cnt > 1 cannot happen (library sequences are unique)
+    return 3;
+}
+
 // Counter-mode decision for one extracted key: returns 1 perfect, 2 imperfect, 3 non-aligned,
-// and the feature index in `idx`.
+// the feature index in `idx` and its distance from the key in `dist` (both left alone when non-aligned).
 template <bool WORDS = false, class KV>
-F2Q_HD int match_key(const RunDev &run, const LibDev &lib, const KV &kv, uint32_t &idx)
+F2Q_HD int match_key_dist(const RunDev &run, const LibDev &lib, const KV &kv, uint32_t &idx, int &dist)
 {
     // is the key a plain ACGT string short enough for the 2-bit index?
     bool regular = (kv.nseg == 1 && kv.len >= 1 && kv.len <= F2Q_REG_MAXLEN);
@@ -622,28 +643,100 @@ F2Q_HD int match_key(const RunDev &run, const LibDev &lib, const KV &kv, uint32_
     }
     MinTrack t; t.init(run.miss);
     if (regular && lib.n_irregular == 0) {
-        if (nforced == 0) {
-            int e = lib_exact(lib, key, kv.len);
-            if (e >= 0) { idx = (uint32_t)e; return 1; }
-        }
-        // regular features: a non-ACGT query symbol mismatches every one of them
-        if (run.miss > 0 && nforced <= run.miss) lib_near(lib, key, kv.len, forced, t);
+        if (match_regular(run, lib, key, kv.len, forced, nforced, t, idx)) { dist = 0; return 1; }
     } else {
         // ':'-joined, long or odd-symbol keys, and every key once the library itself holds such features: the byte-string
         // index over ALL features of the key's length (the reference compares with every same-length feature, :683)
         const GkGroup *g = gk_find(lib, kv.len);
         if (g) {
             const int e = gk_exact<WORDS>(lib, *g, kv);
-            if (e >= 0) { idx = (uint32_t)e; return 1; }
+            if (e >= 0) { idx = (uint32_t)e; dist = 0; return 1; }
             if (run.miss > 0) {
                 if (g->n_pieces) gk_near<WORDS>(lib, *g, kv, t);
                 else lib_scan(lib, kv, lib.gk.ids + g->ids_off, g->n, t);   // fewer bytes than pieces: the whole group is within reach
             }
         }
     }
-    if (t.cnt == 1) { idx = t.idx; return t.best == 0 ? 1 : 2; }
-    // best == 0 with cnt > 1 cannot happen (library sequences are unique)
-    return 3;
+    return match_verdict(t, idx, dist);
+}
+template <bool WORDS = false, class KV>
+F2Q_HD int match_key(const RunDev &run, const LibDev &lib, const KV &kv, uint32_t &idx)
+{
+    int dist = 0;
+    return match_key_dist<WORDS>(run, lib, kv, idx, dist);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Extract+Count keys against a library (f2q_ec_assign).  The Counter-mode outcome of a read is a function of its joined
+// key alone (fast2q.py:362-380), so one match_key per DISTINCT key of the Extract+Count tables, weighted by the key's
+// read count, gives the Counter-mode count vector and stats of the same reads.
+// ---------------------------------------------------------------------------------------------
+#define F2Q_ASG_NONE 0xFFFFFFFFu     // feature of a key that is assigned to none
+#define F2Q_ASG_NODIST 255u          // ... and its distance
+#define F2Q_ASG_EMPTY 254u           // distance word of an unoccupied single-word slot
+struct AssignDev {
+    uint32_t *feat_b; uint8_t *dist_b;         // parallel to the byte-string entries [0, ctr[0])
+    uint32_t *feat_w; uint8_t *dist_w;         // parallel to the single-word slots [0, k64_mask]
+    unsigned long long *counts;                // [n_features] reads per feature
+    unsigned long long *bad;                   // entries met that are not filled in (an internal error: the host reports it)
+};
+
+// a single-word slot (see ec64_word): match_key's verdict.  With a library of regular features only, the word's codes,
+// length and 'N' positions are the regular road's inputs as they stand (no text is made); the empty key, and every key
+// once the library holds irregular features, goes through match_key as text (the byte-string index).
+F2Q_HD int assign_word(const RunDev &run, const LibDev &lib, unsigned long long word, uint32_t &idx, int &dist)
+{
+    const uint32_t lf = (uint32_t)(word >> 58), len = lf & 31u;
+    if (len >= 1u && lib.n_irregular == 0) {
+        const uint64_t key = word & ((1ull << (2 * len)) - 1ull);
+        uint64_t forced = 0;
+        int nforced = 0;
+        if (lf & F2Q_EC64_NFLAG) {
+            nforced = (int)((word >> (2 * len)) & 3u);
+            for (int i = 0; i < nforced; i++) forced |= 1ull << (2 * ((word >> (2 * len + 2 + 5 * i)) & 31u));
+        }
+        MinTrack t; t.init(run.miss);
+        if (match_regular(run, lib, key, (int)len, forced, nforced, t, idx)) { dist = 0; return 1; }
+        return match_verdict(t, idx, dist);
+    }
+    char text[32];
+    ec64_text(word, text);
+    KeyView kv; kv.seq = (const uint8_t *)text; kv.nseg = 1; kv.a[0] = 0; kv.b[0] = (int)len; kv.len = (int)len;
+    return match_key_dist(run, lib, kv, idx, dist);
+}
+
+// One lane of k_assign_slots: slot s of the single-word table.  Returns the verdict (0: the slot is empty) and the reads
+// that carried the key in n.
+F2Q_HD int assign_slot_lane(const RunDev &run, const LibDev &lib, const EcDev &ec, const AssignDev &out, uint32_t s, unsigned long long &n)
+{
+    const unsigned long long word = gp(ec.k64_slots)[s];
+    if (word == KEY_EMPTY) { gpw(out.feat_w)[s] = F2Q_ASG_NONE; gpw(out.dist_w)[s] = (uint8_t)F2Q_ASG_EMPTY; n = 0; return 0; }
+    n = gp(ec.k64_count)[s] + 1ull;                              // (the count word holds n - 1)
+    uint32_t idx = 0; int dist = 0;
+    const int res = assign_word(run, lib, word, idx, dist);
+    const bool hit = res == 1 || res == 2;
+    gpw(out.feat_w)[s] = hit ? idx : F2Q_ASG_NONE; gpw(out.dist_w)[s] = hit ? (uint8_t)dist : (uint8_t)F2Q_ASG_NODIST;
+    if (hit) acc_add(&out.counts[idx], n);
+    return res;
+}
+// One lane of k_assign_entries: entry e of the byte-string table, its key read in place from the arena (the joined text
+// of a multi-window key holds its ':' separators; the empty key is legal).  arena_used: the arena words handed out.
+F2Q_HD int assign_entry_lane(const RunDev &run, const LibDev &lib, const EcDev &ec, const AssignDev &out, unsigned long long e,
+                             unsigned long long arena_used, unsigned long long &n)
+{
+    const unsigned long long off = gp(ec.ent_off)[e];
+    const uint32_t len = gp(ec.ent_len)[e];
+    n = gp(ec.ent_count)[e];
+    uint32_t idx = 0; int dist = 0, res = 0;
+    if (len > 0x7FFFFFFFu || off + ((unsigned long long)len + 3ull) / 4ull > arena_used) { acc_add(out.bad, 1ull); n = 0; }
+    else {
+        KeyViewG kv; kv.seq = gp(reinterpret_cast<const uint8_t *>(ec.arena + off)); kv.nseg = 1; kv.a[0] = 0; kv.b[0] = (int)len; kv.len = (int)len;
+        res = match_key_dist<true>(run, lib, kv, idx, dist);
+    }
+    const bool hit = res == 1 || res == 2;
+    gpw(out.feat_b)[e] = hit ? idx : F2Q_ASG_NONE; gpw(out.dist_b)[e] = hit ? (uint8_t)dist : (uint8_t)F2Q_ASG_NODIST;
+    if (hit) acc_add(&out.counts[idx], n);
+    return res;
 }
 
 // Phred test of quality bytes [a,b) against threshold thr

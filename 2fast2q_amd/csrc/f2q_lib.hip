@@ -31,6 +31,7 @@ using namespace f2q;
 #include "f2q_aux_kernels.h"
 #include "f2q_pair_kernels.h"
 #include "f2q_inflate_kernels.h"
+#include "f2q_assign_kernels.h"
 
 // ===============================================================================================
 // host side
@@ -95,6 +96,18 @@ struct f2q_ctx {
     uint64_t hot_learn = (uint64_t)1 << 18, ec_learned = 0;
     unsigned long long *defer_d = nullptr; size_t defer_cap = 0;
     uint64_t reads_seen = 0;             // global read index of the next block's read 0
+    // Extract+Count with a library (f2q_set_assign_library / f2q_ec_assign): an index of its own -- the context's lib_d
+    // stays the empty library the counting kernels are handed -- a result vector of its own (counts then 5 stats then
+    // the bad-entry word) and the per-key arrays of the last assign, valid while asg_gen == ec_gen
+    bool have_asg = false;
+    HostIndex asg_ix;
+    LibDev asg_lib_h{};
+    LibDev *asg_lib_d = nullptr;
+    std::vector<void *> asg_lib_allocs, asg_allocs;
+    unsigned long long *asg_acc_d = nullptr;
+    AssignDev asg{};
+    uint64_t asg_nb = 0, asg_nw = 0;     // entries / slots the per-key arrays cover
+    uint64_t ec_gen = 1, asg_gen = 0;    // ec_gen: bumped by every count call, reset and table growth
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
     int n_cu = 256;
     bool force_generic = false;           // F2Q_GENERIC=1: run-time window geometry even where a specialisation exists
@@ -245,65 +258,66 @@ static int setup_run(f2q_ctx *c)
     return F2Q_OK;
 }
 
-static int upload_lib(f2q_ctx *c)
+// the index ix on the device: L = its host-side descriptor, *lib_d = the device copy of L, owner = the allocations
+static int upload_index(f2q_ctx *c, const HostIndex &ix, LibDev &L, LibDev **lib_d, std::vector<void *> &owner, uint64_t **guide_keys)
 {
-    free_all(c, c->lib_allocs);
-    LibDev &L = c->lib_h;
+    free_all(c, owner);
     memset(&L, 0, sizeof L);
-    L.n_features = c->ix.n_features;
-    L.n_irregular = c->ix.n_irregular;
-    memcpy(L.grp, c->ix.grp, sizeof L.grp);
-    L.pk = c->ix.pk;
-    memcpy(L.mpk, c->ix.mpk, sizeof L.mpk);
-    L.mw_ok = c->ix.mw_ok;
+    L.n_features = ix.n_features;
+    L.n_irregular = ix.n_irregular;
+    memcpy(L.grp, ix.grp, sizeof L.grp);
+    L.pk = ix.pk;
+    memcpy(L.mpk, ix.mpk, sizeof L.mpk);
+    L.mw_ok = ix.mw_ok;
     uint64_t *tk; uint32_t *ti; uint8_t *fb; uint32_t *fo; uint32_t *ir; uint64_t *gk; uint64_t *pt;
     int rc;
-    if ((rc = dev_upload(c, c->ix.tab_keys.data(), c->ix.tab_keys.size(), &tk, c->lib_allocs))) return rc;
-    if ((rc = dev_upload(c, c->ix.tab_idx.data(), c->ix.tab_idx.size(), &ti, c->lib_allocs))) return rc;
-    if ((rc = dev_upload(c, c->ix.feat_bytes.data(), c->ix.feat_bytes.size(), &fb, c->lib_allocs))) return rc;
-    if ((rc = dev_upload(c, c->ix.feat_off.data(), c->ix.feat_off.size(), &fo, c->lib_allocs))) return rc;
-    if ((rc = dev_upload(c, c->ix.irr_ids.data(), c->ix.irr_ids.size(), &ir, c->lib_allocs))) return rc;
-    if ((rc = dev_upload(c, c->ix.key2.data(), c->ix.key2.size(), &gk, c->lib_allocs))) return rc;
-    if ((rc = dev_upload(c, c->ix.ptab.data(), c->ix.ptab.size(), &pt, c->lib_allocs))) return rc;
+    if ((rc = dev_upload(c, ix.tab_keys.data(), ix.tab_keys.size(), &tk, owner))) return rc;
+    if ((rc = dev_upload(c, ix.tab_idx.data(), ix.tab_idx.size(), &ti, owner))) return rc;
+    if ((rc = dev_upload(c, ix.feat_bytes.data(), ix.feat_bytes.size(), &fb, owner))) return rc;
+    if ((rc = dev_upload(c, ix.feat_off.data(), ix.feat_off.size(), &fo, owner))) return rc;
+    if ((rc = dev_upload(c, ix.irr_ids.data(), ix.irr_ids.size(), &ir, owner))) return rc;
+    if ((rc = dev_upload(c, ix.key2.data(), ix.key2.size(), &gk, owner))) return rc;
+    if ((rc = dev_upload(c, ix.ptab.data(), ix.ptab.size(), &pt, owner))) return rc;
     L.ptab = pt;
     {
         uint32_t *lt_tags, *lt_feat; uint16_t *lt_slot;
-        if ((rc = dev_upload(c, c->ix.lt_tags.data(), c->ix.lt_tags.size(), &lt_tags, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.lt_feat_of.data(), c->ix.lt_feat_of.size(), &lt_feat, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.lt_slot_of.data(), c->ix.lt_slot_of.size(), &lt_slot, c->lib_allocs))) return rc;
-        L.lt = c->ix.lt; L.lt.tags = lt_tags; L.lt.feat_of = lt_feat; L.lt.slot_of = lt_slot;
+        if ((rc = dev_upload(c, ix.lt_tags.data(), ix.lt_tags.size(), &lt_tags, owner))) return rc;
+        if ((rc = dev_upload(c, ix.lt_feat_of.data(), ix.lt_feat_of.size(), &lt_feat, owner))) return rc;
+        if ((rc = dev_upload(c, ix.lt_slot_of.data(), ix.lt_slot_of.size(), &lt_slot, owner))) return rc;
+        L.lt = ix.lt; L.lt.tags = lt_tags; L.lt.feat_of = lt_feat; L.lt.slot_of = lt_slot;
         uint64_t *pw_tab;
-        if ((rc = dev_upload(c, c->ix.pw_tab.data(), c->ix.pw_tab.size(), &pw_tab, c->lib_allocs))) return rc;
-        L.pw = c->ix.pw; L.pw.tab = pw_tab;
+        if ((rc = dev_upload(c, ix.pw_tab.data(), ix.pw_tab.size(), &pw_tab, owner))) return rc;
+        L.pw = ix.pw; L.pw.tab = pw_tab;
         { const char *e = getenv("F2Q_NO_PW"); if (e && e[0] == '1') L.pw.ok = 0; }      // A/B runs: the joined key as a string (byte-string index)
         uint32_t *pt_t0, *pt_t1, *pt_ps, *pt_s1, *pt_fo, *pt_f0; uint16_t *pt_s0;
-        if ((rc = dev_upload(c, c->ix.pt_tags0.data(), c->ix.pt_tags0.size(), &pt_t0, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.pt_tags1.data(), c->ix.pt_tags1.size(), &pt_t1, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.pt_pstart.data(), c->ix.pt_pstart.size(), &pt_ps, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.pt_slot0_of.data(), c->ix.pt_slot0_of.size(), &pt_s0, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.pt_slot1_of.data(), c->ix.pt_slot1_of.size(), &pt_s1, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.pt_feat_of.data(), c->ix.pt_feat_of.size(), &pt_fo, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.pt_feat0_of.data(), c->ix.pt_feat0_of.size(), &pt_f0, c->lib_allocs))) return rc;
-        L.pt = c->ix.pt; L.pt.tags0 = pt_t0; L.pt.tags1 = pt_t1; L.pt.pstart = pt_ps; L.pt.slot0_of = pt_s0; L.pt.slot1_of = pt_s1;
+        if ((rc = dev_upload(c, ix.pt_tags0.data(), ix.pt_tags0.size(), &pt_t0, owner))) return rc;
+        if ((rc = dev_upload(c, ix.pt_tags1.data(), ix.pt_tags1.size(), &pt_t1, owner))) return rc;
+        if ((rc = dev_upload(c, ix.pt_pstart.data(), ix.pt_pstart.size(), &pt_ps, owner))) return rc;
+        if ((rc = dev_upload(c, ix.pt_slot0_of.data(), ix.pt_slot0_of.size(), &pt_s0, owner))) return rc;
+        if ((rc = dev_upload(c, ix.pt_slot1_of.data(), ix.pt_slot1_of.size(), &pt_s1, owner))) return rc;
+        if ((rc = dev_upload(c, ix.pt_feat_of.data(), ix.pt_feat_of.size(), &pt_fo, owner))) return rc;
+        if ((rc = dev_upload(c, ix.pt_feat0_of.data(), ix.pt_feat0_of.size(), &pt_f0, owner))) return rc;
+        L.pt = ix.pt; L.pt.tags0 = pt_t0; L.pt.tags1 = pt_t1; L.pt.pstart = pt_ps; L.pt.slot0_of = pt_s0; L.pt.slot1_of = pt_s1;
         L.pt.feat_of = pt_fo; L.pt.feat0_of = pt_f0;
         GkGroup *gk_grp; uint32_t *gk_tab, *gk_ids;
-        if ((rc = dev_upload(c, c->ix.gk_groups.data(), c->ix.gk_groups.size(), &gk_grp, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.gk_tab.data(), c->ix.gk_tab.size(), &gk_tab, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.gk_ids.data(), c->ix.gk_ids.size(), &gk_ids, c->lib_allocs))) return rc;
-        L.gk.n_groups = c->ix.n_features ? (uint32_t)c->ix.gk_groups.size() : 0u; L.gk.grp = gk_grp; L.gk.tab = gk_tab; L.gk.ids = gk_ids;
+        if ((rc = dev_upload(c, ix.gk_groups.data(), ix.gk_groups.size(), &gk_grp, owner))) return rc;
+        if ((rc = dev_upload(c, ix.gk_tab.data(), ix.gk_tab.size(), &gk_tab, owner))) return rc;
+        if ((rc = dev_upload(c, ix.gk_ids.data(), ix.gk_ids.size(), &gk_ids, owner))) return rc;
+        L.gk.n_groups = ix.n_features ? (uint32_t)ix.gk_groups.size() : 0u; L.gk.grp = gk_grp; L.gk.tab = gk_tab; L.gk.ids = gk_ids;
         unsigned long long *gk_fw; uint32_t *gk_fwoff;
-        if ((rc = dev_upload(c, c->ix.gk_fw.data(), c->ix.gk_fw.size(), &gk_fw, c->lib_allocs))) return rc;
-        if ((rc = dev_upload(c, c->ix.gk_fwoff.data(), c->ix.gk_fwoff.size(), &gk_fwoff, c->lib_allocs))) return rc;
+        if ((rc = dev_upload(c, ix.gk_fw.data(), ix.gk_fw.size(), &gk_fw, owner))) return rc;
+        if ((rc = dev_upload(c, ix.gk_fwoff.data(), ix.gk_fwoff.size(), &gk_fwoff, owner))) return rc;
         L.gk.fw = gk_fw; L.gk.fwoff = gk_fwoff;
     }
     L.tab_keys = tk; L.tab_idx = ti; L.feat_bytes = fb; L.feat_off = fo; L.irr_ids = ir;
-    c->guide_keys_d = gk;
+    if (guide_keys) *guide_keys = gk;
     LibDev *ld;
-    if ((rc = dev_upload(c, &L, 1, &ld, c->lib_allocs))) return rc;
-    c->lib_d = ld;
+    if ((rc = dev_upload(c, &L, 1, &ld, owner))) return rc;
+    *lib_d = ld;
     HIPC(c, hipStreamSynchronize(c->stream));
     return F2Q_OK;
 }
+static int upload_lib(f2q_ctx *c) { return upload_index(c, c->ix, c->lib_h, &c->lib_d, c->lib_allocs, &c->guide_keys_d); }
 
 static int alloc_acc(f2q_ctx *c, uint64_t n_features)
 {
@@ -382,6 +396,8 @@ extern "C" void f2q_destroy(f2q_ctx *c)
                           (unsigned long long)c->n_malloc, c->tr_malloc, (unsigned long long)c->n_hipfree, c->tr_hipfree, (unsigned long long)c->n_reuse, c->tr_reserve, (unsigned long long)c->n_rehash);
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
     free_all(c, c->lib_allocs); free_all(c, c->ec_allocs); free_all(c, c->ec_allocs64); free_all(c, c->ec_allocs_ctr); free_all(c, c->hot_allocs);
+    free_all(c, c->asg_lib_allocs); free_all(c, c->asg_allocs);
+    if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
     c->dev_idle.clear(); c->dev_size.clear();
@@ -455,6 +471,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
         memset(&c->ec, 0, sizeof c->ec); c->ec_slots = 0; c->hot_valid = false; c->ec_learned = 0;
     }
     c->reads_seen = 0;
+    c->ec_gen++;
     // no host synchronisation: the clear is ordered on the context's stream like every launch and read-back after it
     return F2Q_OK;
 }
@@ -540,6 +557,7 @@ static int ec_reserve(f2q_ctx *c, uint64_t keys64, uint64_t reads, uint64_t key_
     const bool growB = !c->ec.slots || need_b > c->ec.max_entries || need_w > c->ec.arena_words;
     if (!grow64 && !growB) return F2Q_OK;
     const double rs0 = now_ms();
+    c->ec_gen++;                                                 // the tables move: per-key arrays of an earlier assign are stale
     // nothing may still be counting into the tables that are about to move
     if (c->aux_busy) { HIPC(c, hipStreamSynchronize(c->aux_stream)); c->aux_busy = false; }
     if (c->ec.ctr) {                                             // the exact counters: they say how much is carried over
@@ -1074,6 +1092,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
 #endif
     uint32_t launches = 0;
     HIPC(c, hipEventRecord(k0, c->stream));
+    c->ec_gen++;
     if (c->prm.mode == 0) {
         int rc = launch_view(c, b->pb, b->rb, acc, launches);
         if (rc) return rc;
@@ -2818,5 +2837,117 @@ extern "C" int f2q_ec_fetch(f2q_ctx *c, char *keys, uint64_t *offs, int64_t *cou
         if (counts) counts[e] = (int64_t)h.cnt[e];
         if (first_read) first_read[e] = h.first[e];
     }
+    return F2Q_OK;
+}
+
+// ---- Extract+Count with a library --------------------------------------------------------------------
+extern "C" int f2q_set_assign_library(f2q_ctx *c, const char *seqs, const uint32_t *offs, uint32_t n)
+{
+    if (!c || !offs || (!seqs && n)) return fail(c, F2Q_EINVAL, "null argument");
+    if (c->prm.mode != 1) return fail(c, F2Q_ESTATE, "an assign library belongs to an Extract+Count context (Counter mode: f2q_set_features)");
+    if (c->have_asg) return fail(c, F2Q_ESTATE, "f2q_set_assign_library may be called once per context");
+    HIPC(c, hipSetDevice(c->device));
+    for (uint32_t i = 0; i < n; i++) if (offs[i + 1] < offs[i]) return fail(c, F2Q_EINVAL, "offsets must be non-decreasing");
+    // the index match_key reads: the 2-bit tables by length and the byte-string index; no packed tables (no kernel of
+    // this context counts against it), so the pack plan and the path choice stay what they were
+    build_index(c->asg_ix, seqs ? seqs : "", offs, n, c->run_h.miss);
+    int rc = upload_index(c, c->asg_ix, c->asg_lib_h, &c->asg_lib_d, c->asg_lib_allocs, nullptr);
+    if (rc) return rc;
+    HIPC(c, hipMalloc((void **)&c->asg_acc_d, ((size_t)n + 6) * sizeof(unsigned long long)));
+    c->have_asg = true;
+    return F2Q_OK;
+}
+
+extern "C" int f2q_ec_assign(f2q_ctx *c, int64_t *counts, int64_t stats[5], f2q_timing *t)
+{
+    if (!c) return F2Q_EINVAL;
+    if (t) memset(t, 0, sizeof *t);
+    if (c->prm.mode != 1) return fail(c, F2Q_ESTATE, "not in Extract+Count mode");
+    if (!c->have_asg) return fail(c, F2Q_ESTATE, "f2q_set_assign_library must be called before f2q_ec_assign");
+    HIPC(c, hipSetDevice(c->device));
+    const uint64_t nf = c->asg_lib_h.n_features;
+    // everything that still counts into the tables comes first: the raw records' stream is joined as f2q_reset_counts and
+    // the table growth join it; the hot-key launches (whose workgroups add their LDS counters to the table as they end)
+    // and the deferred passes are on the context's stream, ahead of the kernels below
+    if (c->aux_busy) { HIPC(c, hipStreamSynchronize(c->aux_stream)); c->aux_busy = false; }
+    unsigned long long ctr[F2Q_CTR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int rc;
+    if (c->ec.ctr && (rc = ec_counters(c, ctr))) return rc;
+    const uint64_t nb = c->ec.slots ? ctr[0] : 0, nw = c->ec.k64_slots ? (uint64_t)c->ec.k64_mask + 1 : 0;
+    c->asg_gen = 0;
+    free_all(c, c->asg_allocs);
+    memset(&c->asg, 0, sizeof c->asg);
+    if ((rc = dev_alloc(c, (size_t)nb, &c->asg.feat_b, c->asg_allocs))) return rc;
+    if ((rc = dev_alloc(c, (size_t)nb, &c->asg.dist_b, c->asg_allocs))) return rc;
+    if ((rc = dev_alloc(c, (size_t)nw, &c->asg.feat_w, c->asg_allocs))) return rc;
+    if ((rc = dev_alloc(c, (size_t)nw, &c->asg.dist_w, c->asg_allocs))) return rc;
+    c->asg.counts = c->asg_acc_d; c->asg.bad = c->asg_acc_d + nf + 5;
+    unsigned long long *st_d = c->asg_acc_d + nf;
+    // a result vector of its own, cleared by every call: assigning never adds to an earlier result
+    HIPC(c, hipMemsetAsync(c->asg_acc_d, 0, (nf + 6) * sizeof(unsigned long long), c->stream));
+    uint32_t launches = 0;
+    HIPC(c, hipEventRecord(c->ev_k0, c->stream));
+    if (nb) {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((nb + F2Q_ASG_THREADS - 1) / F2Q_ASG_THREADS, (uint64_t)c->n_cu * 8u);
+        hipLaunchKernelGGL(k_assign_entries, dim3(grid), dim3(F2Q_ASG_THREADS), 0, c->stream, c->run_d, c->asg_lib_d, c->ec, c->asg,
+                           (unsigned long long)nb, ctr[1], st_d);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, "k_assign_entries");
+    }
+    if (nw && ctr[3]) {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((nw + F2Q_ASG_THREADS - 1) / F2Q_ASG_THREADS, (uint64_t)c->n_cu * 8u);
+        hipLaunchKernelGGL(k_assign_slots, dim3(grid), dim3(F2Q_ASG_THREADS), 0, c->stream, c->run_d, c->asg_lib_d, c->ec, c->asg, st_d);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, "k_assign_slots");
+    }
+    HIPC(c, hipEventRecord(c->ev_k1, c->stream));
+    // reads and quality_failed are the context's own (fast2q.py:389-393 do not depend on the library)
+    HIPC(c, hipMemcpyAsync(st_d + F2Q_READS, c->acc_d + (c->acc_n - 5) + F2Q_READS, 8, hipMemcpyDeviceToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(st_d + F2Q_QUALITY_FAILED, c->acc_d + (c->acc_n - 5) + F2Q_QUALITY_FAILED, 8, hipMemcpyDeviceToDevice, c->stream));
+    std::vector<unsigned long long> h(nf + 6);
+    HIPC(c, hipMemcpyAsync(h.data(), c->asg_acc_d, (nf + 6) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (h[nf + 5]) return fail(c, F2Q_ESTATE, std::to_string(h[nf + 5]) + " Extract+Count entries are not filled in");
+    if (counts) for (uint64_t i = 0; i < nf; i++) counts[i] = (int64_t)h[i];
+    if (stats) for (int k = 0; k < 5; k++) stats[k] = (int64_t)h[nf + k];
+    if (t) {
+        float ms = 0;
+        HIPC(c, hipEventElapsedTime(&ms, c->ev_k0, c->ev_k1));
+        t->kernel_ms = ms; t->total_ms = ms; t->reads = h[nf + F2Q_READS]; t->launches = launches;
+    }
+    // the per-key arrays cover the single-word table only when it was walked
+    c->asg_nb = nb; c->asg_nw = ctr[3] ? nw : 0; c->asg_gen = c->ec_gen;
+    return F2Q_OK;
+}
+
+extern "C" int f2q_ec_fetch_assigned(f2q_ctx *c, int32_t *feature, int32_t *dist)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->prm.mode != 1) return fail(c, F2Q_ESTATE, "not in Extract+Count mode");
+    if (!c->have_asg || c->asg_gen != c->ec_gen)
+        return fail(c, F2Q_ESTATE, "the Extract+Count tables have changed since the last f2q_ec_assign (or it was never called)");
+    HIPC(c, hipSetDevice(c->device));
+    std::vector<uint32_t> fb(c->asg_nb), fw(c->asg_nw);
+    std::vector<uint8_t> db(c->asg_nb), dw(c->asg_nw);
+    if (c->asg_nb) {
+        HIPC(c, hipMemcpyAsync(fb.data(), c->asg.feat_b, c->asg_nb * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(db.data(), c->asg.dist_b, c->asg_nb, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (c->asg_nw) {
+        HIPC(c, hipMemcpyAsync(fw.data(), c->asg.feat_w, c->asg_nw * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(dw.data(), c->asg.dist_w, c->asg_nw, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    // f2q_ec_fetch's order: the byte-string entries, then the occupied single-word slots
+    size_t o = 0;
+    auto put = [&](uint32_t f, uint8_t d) {
+        if (feature) feature[o] = f == F2Q_ASG_NONE ? -1 : (int32_t)f;
+        if (dist) dist[o] = d == F2Q_ASG_NODIST ? -1 : (int32_t)d;
+        o++;
+    };
+    for (size_t e = 0; e < fb.size(); e++) put(fb[e], db[e]);
+    for (size_t s = 0; s < fw.size(); s++) if (dw[s] != F2Q_ASG_EMPTY) put(fw[s], dw[s]);
     return F2Q_OK;
 }

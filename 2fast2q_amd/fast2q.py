@@ -123,8 +123,11 @@ _CTX_TLS = threading.local()
 _CTX_GEN = [0]
 
 
-def _context_for(seqs, kwargs):
+def _context_for(seqs, kwargs, assign=None):
+    """assign: the library an Extract+Count context matches its keys against (--as), set once when the context is made"""
     key = (tuple(sorted((k, str(v)) for k, v in kwargs.items())), None if seqs is None else tuple(seqs))      # (compared by value: a few ms for 100 k features)
+    if assign is not None:
+        key = (key, tuple(assign))
     cur = getattr(_CTX_TLS, "entry", None)
     if os.environ.get("F2Q_NO_CTX_CACHE") == "1":              # A/B runs: a fresh context per sample
         key = (key, object())
@@ -134,6 +137,8 @@ def _context_for(seqs, kwargs):
     if cur is not None and cur[0] == _CTX_GEN[0]:
         _drop_context(cur[2])
     ctx = binding.Counter(features=seqs, **kwargs)
+    if assign is not None:
+        ctx.set_assign_library(assign)
     _CTX_TLS.entry = (_CTX_GEN[0], key, ctx)
     with _CTX_LOCK:
         _CTX_ALL.append(ctx)
@@ -214,7 +219,10 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         return features, reads_stats, local_read_stats
     counter_mode = param['Running Mode'] == 'C'
     seqs = list(features) if counter_mode else None
-    ctx = _context_for(seqs, _counter_kwargs(param))
+    assign = list(param['assign_features']) if param.get('assign') and not counter_mode else None
+    if assign is not None and sharding.world().size > 1:
+        raise RuntimeError("--as: assignments are not merged across several ranks; run one process")
+    ctx = _context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
         if param.get('paired'):
@@ -236,6 +244,11 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             _, truncated = ctx.count_file(raw)
             counts, stats = ctx.read_counts()
             ec_rows = None if counter_mode else ctx.ec_results()
+        if assign is not None:
+            # one match per distinct key on the device: the Counter-mode count vector and counters of the same reads, and
+            # every key's feature (f2q_ec_assign)
+            acounts, stats = ctx.ec_assign()
+            param.setdefault('assigned', {})[raw] = ([int(n) for n in acounts], ctx.ec_assigned())
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -301,19 +314,34 @@ def aligner(i, raw, features, param, reads_stats):
     if packed is None:
         return reads_stats
     features, reads_stats, local = packed
-    rows = [[f.name, f.counts] for f in features.values()]
+    rows = _sample_rows([f.name, f.counts] for f in features.values())
     value, unit = _elapsed_text(time.perf_counter() - started)
-    try:
-        rows.sort(key=lambda row: int(row[0]))       # all names numeric: numerical order
-    except ValueError:
-        rows.sort(key=lambda row: row[0])
     sample = SampleResult(_sample_name(raw), value, unit, rows, dict(local))
+    if raw in param.get('assigned', {}):             # --as: the table Counter mode would have given, and every key's feature
+        acounts, arows = param['assigned'].pop(raw)
+        names = [f.name for f in param['assign_features'].values()]
+        param.setdefault("assign_samples", {})[sample.name] = SampleResult(sample.name, value, unit, _sample_rows(zip(names, acounts)), dict(local))
+        if sharding.world().rank == 0:
+            os.makedirs(param["directory"], exist_ok=True)
+            csv_writer(os.path.join(param["directory"], sample.name + "_assigned.csv"),
+                       [["#key", "reads", "feature_name", "mismatches"]] +
+                       [[key, n, names[f] if f >= 0 else "", d] for key, n, _first, f, d in arows])
     if not param['Progress bar']:
         colourful_errors("INFO", f"Sample {sample.name} was processed in {value} {unit}")
     param.setdefault("samples", {})[sample.name] = sample     # a later file of the same name replaces the earlier one,
     if not param.get("delete", True) and sharding.world().rank == 0:   # as its _reads.csv would upstream
         csv_writer(os.path.join(param["directory"], sample.name + "_reads.csv"), sample.reads_csv_rows())
     return reads_stats
+
+
+def _sample_rows(pairs):
+    """[name, reads] rows in a sample's order: numeric when every name is a number, else alphabetical (:790-793)"""
+    rows = [[name, reads] for name, reads in pairs]
+    try:
+        rows.sort(key=lambda row: int(row[0]))       # all names numeric: numerical order
+    except ValueError:
+        rows.sort(key=lambda row: row[0])
+    return rows
 
 
 def csv_writer(path, outfile):
@@ -356,6 +384,8 @@ def initializer(cmd):
         print(f" Finding features with the folowing length: {param['length']}bp")
     if (param['upstream'] is None) and (param['downstream'] is None):
         print(f" Read alignment start position: {param['start']}")
+    if param.get('assign'):
+        print(f" Extracted sequences are assigned to the features of {param['feature']} ({param['miss']} mismatches allowed)")
     if param.get('paired'):
         print(f" Paired-end: mate 2 start position: {param['start2']}" + (" (mate 2 reverse-complemented)" if param['rc2'] else ""))
     print(f" All data will be saved into {param['directory']}")
@@ -422,6 +452,7 @@ def input_parser(argv=None):
     ap.add_argument("--pe", nargs='?', const=True, help="Paired-end: the files of --s are paired by name (_R1/_R2, else _1/_2); --st names the feature parts in mate 1, --st2 those in mate 2")
     ap.add_argument("--st2", help="With --pe: the start position(s) of the feature part(s) within mate 2")
     ap.add_argument("--rc2", nargs='?', const=True, help="With --pe: mate 2 is reverse-complemented before its parts are taken")
+    ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
     if args.v is not None:
         print(f"\nVersion: {version}\n")
@@ -431,9 +462,12 @@ def input_parser(argv=None):
     if args.pe is not None and args.t is not None:
         colourful_errors("FATAL", "--pe cannot be combined with -t: the test mode runs on one packaged single-end sample.")
         sys.exit(2)
+    if args.assign is not None and (args.g is None or args.t is not None):
+        colourful_errors("FATAL", "--as needs --g: the .csv file with the features the extracted sequences are assigned to.")
+        sys.exit(2)
     p = {"cmd": True, "big_file_split": args.fs is not None}
     p['used_cmd'] = " ".join(f"--{k}" if isinstance(v, bool) and v else f"--{k} {v}"
-                             for k, v in vars(args).items() if v is not None)
+                             for k, v in ((("as" if k == "assign" else k), v) for k, v in vars(args).items()) if v is not None)
     p['Running Mode'] = "EC" if (args.mo is not None and "EC" in args.mo.upper()) else "C"
     if args.t is None:
         p["test_mode"] = False
@@ -467,6 +501,11 @@ def input_parser(argv=None):
     elif args.st2 is not None or args.rc2 is not None:
         colourful_errors("FATAL", f"{'--st2' if args.st2 is not None else '--rc2'} only has a meaning with --pe.")
         sys.exit(2)
+    if args.assign is not None:
+        if p['Running Mode'] != "EC":
+            colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
+            sys.exit(2)
+        p['assign'] = True
     for value, key in paths:                                   # :1178-1191
         if value is None:
             p[key] = os.getcwd()
@@ -500,6 +539,9 @@ def file_sizer_split(param):
             sys.exit(2)
         param['mates'] = dict(pairs)
         files = [r1 for r1, _ in pairs]
+    if param.get('assign') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--as: assignments are not merged across several ranks; run one process.")
+        sys.exit(2)
     param["sequencing_files"] = {"len_files": len(files), "preprocess_files": files[:1], "files": files}
     return param
 
@@ -608,6 +650,10 @@ def compiling(param):
     run_stats(run_headers(param), param, table, head, ordered)
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}.csv"),
                [head] + [[feature] + counts for feature, counts in table.items()])
+    if param.get("assign_samples"):                  # --as: the table Counter mode would have written for the same samples
+        _, ahead, atable = compile_table(param["assign_samples"])
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_features.csv"),
+                   [ahead] + [[feature] + counts for feature, counts in atable.items()])
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -709,6 +755,8 @@ def main(argv=None):
     features = {}
     if param['Running Mode'] == 'C':
         features = features_loader(param["feature"])
+    elif param.get('assign'):
+        param['assign_features'] = features_loader(param["feature"])
     aligner_mp_dispenser(features, param)
     sharding.barrier()
     if sharding.world().rank == 0:

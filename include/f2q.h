@@ -270,6 +270,31 @@ void *f2q_stream(f2q_ctx *ctx);
 int f2q_ec_size(f2q_ctx *ctx, uint64_t *n_keys, uint64_t *n_bytes);
 int f2q_ec_fetch(f2q_ctx *ctx, char *keys, uint64_t *offs, int64_t *counts, uint64_t *first_read);
 
+/* ---- Extract+Count with a library ------------------------------------------------------------
+ * The reference makes a run either Counter or Extract+Count (fast2q.py:364,382).  Its Counter-mode outcome for a read is
+ * a function of the read's joined key alone: `seq in features`, else mismatch_search_handler(seq, ...), else
+ * non-aligned (fast2q.py:362-380).  So one Extract+Count pass plus one match per DISTINCT key gives the de-novo table,
+ * the feature every key belongs to, and the exact Counter-mode count vector and stats of the same reads.
+ *
+ * f2q_set_assign_library gives an Extract+Count context the library to match its keys against; seqs/offs/n as for
+ * f2q_set_features (binary_converter, fast2q.py:188-213; features_loader :148-166 stays in Python), the allowed
+ * mismatches are the context's --m (f2q_params.miss, unused by Extract+Count counting itself).  Once per context, before
+ * or after counting, also on a paired context (the keys are then the ':'-joined parts of both mates); counting is
+ * unchanged by it.  F2Q_ESTATE on a Counter context or when called twice. */
+int f2q_set_assign_library(f2q_ctx *ctx, const char *seqs, const uint32_t *offs, uint32_t n);
+/* Matches every key the Extract+Count tables hold NOW (exact hit fast2q.py:365-367, else the unique-nearest search of
+ * mismatch_search_handler :692-750, else non-aligned :379-380), each weighted by the reads that carried it:
+ * counts[n] = what Counter mode would have counted per feature, stats[5] = its five counters (F2Q_READS and
+ * F2Q_QUALITY_FAILED are the context's own, :389-393).  The result is computed afresh by every call -- it never adds
+ * to an earlier one -- and only it crosses to the host.  t->kernel_ms: HIP-event time of the assign kernels.
+ * F2Q_ESTATE when no assign library has been set. */
+int f2q_ec_assign(f2q_ctx *ctx, int64_t *counts, int64_t stats[5], f2q_timing *t);
+/* Per key, in exactly the order f2q_ec_fetch returns the keys: the feature index the last f2q_ec_assign gave it (-1:
+ * none -- non-aligned, fast2q.py:379-380 / :734-750 with no unique nearest feature) and its mismatches (0 for an exact
+ * hit :365-367, -1: none); arrays of n_keys (f2q_ec_size) entries, either may be NULL.  F2Q_ESTATE when the tables have
+ * changed since that f2q_ec_assign (a counting call, f2q_reset_counts) or it was never called. */
+int f2q_ec_fetch_assigned(f2q_ctx *ctx, int32_t *feature, int32_t *dist);
+
 #ifdef __cplusplus
 }
 #endif
