@@ -524,22 +524,29 @@ __device__ __forceinline__ U2 lds_u2(const uint32_t *p)
     return U2{v.x, v.y};
 }
 
-__device__ __forceinline__ uint32_t lt_count_add(uint32_t *cnt, uint32_t slot)      // the word's old value
+// a counter is named by its word (the table-0 bucket, slot >> 1) and its increment (1 or 0x10000: slot even / odd)
+__device__ __forceinline__ uint32_t lt_count_inc(uint32_t slot) { return 1u << ((slot & 1u) << 4); }
+__device__ __forceinline__ uint32_t lt_count_add(uint32_t *cnt, uint32_t bucket, uint32_t inc)      // the word's old value
 {
-    return atomicAdd(&cnt[slot >> 1], 1u << ((slot & 1u) << 4));
+    return atomicAdd(&cnt[bucket], inc);
 }
-__device__ __forceinline__ bool lt_count_passed(uint32_t old, uint32_t slot) { return ((old >> ((slot & 1u) << 4)) & 0xFFFFu) == 0x7FFFu; }
+__device__ __forceinline__ bool lt_count_passed(uint32_t old, uint32_t inc) { return ((old >> (inc >> 12)) & 0xFFFFu) == 0x7FFFu; }
+// a counter that stands at 0x7FFF has bit 14 set: one test for several old values at once.  Necessary, not sufficient
+// (any counter of the words from 0x4000 on answers yes): who gets a yes asks lt_count_passed.  An old value of 0 (no add)
+// answers no.
+__device__ __forceinline__ bool lt_count_maybe_passed(uint32_t old_or) { return (old_or & 0x40004000u) != 0u; }
 // exactly one adder sees the counter pass 0x7FFF -> 0x8000; it takes 0x8000 out again (no borrow: the counter only
 // grows until then, and by far less than another 0x8000 -- also when the adder tests its old value some LDS operations
 // later) and credits the feature's global counter
-__device__ __forceinline__ void lt_count_handoff(uint32_t *cnt, uint32_t slot, const Accum &acc, const LtDesc &lt)
+__device__ __forceinline__ void lt_count_handoff(uint32_t *cnt, uint32_t bucket, uint32_t inc, const Accum &acc, const LtDesc &lt)
 {
-    atomicSub(&cnt[slot >> 1], 0x8000u << ((slot & 1u) << 4));
-    acc_add(&acc.counts[gp(lt.feat_of)[slot]], 0x8000ull);
+    atomicSub(&cnt[bucket], inc << 15);
+    acc_add(&acc.counts[gp(lt.feat_of)[2u * bucket + (inc >> 16)]], 0x8000ull);
 }
 __device__ __forceinline__ void lt_count(uint32_t *cnt, uint32_t slot, const Accum &acc, const LtDesc &lt)
 {
-    if (lt_count_passed(lt_count_add(cnt, slot), slot)) lt_count_handoff(cnt, slot, acc, lt);
+    const uint32_t bucket = slot >> 1, inc = lt_count_inc(slot);
+    if (lt_count_passed(lt_count_add(cnt, bucket, inc), inc)) lt_count_handoff(cnt, bucket, inc, acc, lt);
 }
 
 // A20: the window is 20 bases starting at a multiple of 16 (--l 20 with --st 0, 16, ...: the usual guide-counting run):
@@ -576,7 +583,7 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
     // All loads of a tile are unconditional and their number is fixed (the host guarantees the rows and the length plane
     // exist): the compiler's s_waitcnt bookkeeping is then exact, and waiting for this tile's rows does not also wait
     // for the next tile's, which were requested after them.  One 64-bit address per plane, the rows at immediate offsets.
-    const uint64_t q_stride = (uint64_t)pb.wq * F2Q_TILE, b_stride = (uint64_t)pb.wb * F2Q_TILE;
+    const uint32_t q_stride = pb.wq * F2Q_TILE, b_stride = pb.wb * F2Q_TILE;     // words per tile: 32 x 32 -> 64-bit products below
     const auto q_base = gp(pb.qual) + (uint64_t)g.qw0 * F2Q_TILE + 4u * lane;
     const auto b_base = gp(pb.bases) + (uint64_t)g.bw0 * F2Q_TILE + 4u * lane;
     const auto l_base = gp(pb.len) + 4u * lane;
@@ -592,20 +599,15 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
         r.len01 = lv.x; r.len23 = lv.y;
     };
     // Histogram adds leave the chain: a stage's returning adds are tested by the next stage, after the LDS wait that
-    // stage has anyway (a wave's LDS operations complete in order), instead of right away.  n_pend (wave-uniform): adds
-    // of the last stage in pend_old / pend_slot (a lane without an add holds 0, which tests as not passing).
-    uint32_t pend_old[4] = {0, 0, 0, 0}, pend_slot[4] = {0, 0, 0, 0}, n_pend = 0;
+    // stage has anyway (a wave's LDS operations complete in order), instead of right away.  pend_old / pend_bucket /
+    // pend_inc: the adds of the last stage (a lane without an add holds an old value of 0, which tests as not passing).
+    uint32_t pend_old[4] = {0, 0, 0, 0}, pend_bucket[4] = {0, 0, 0, 0}, pend_inc[4] = {1, 1, 1, 1};
     auto settle = [&]() {
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if ((uint32_t)k < n_pend) any |= lt_count_passed(pend_old[k], pend_slot[k]);
-        if (any) {                                              // rare: a counter of the lane passed 0x8000
+        if (lt_count_maybe_passed(pend_old[0] | pend_old[1] | pend_old[2] | pend_old[3])) {      // rare: a counter of the lane is at 0x4000 or beyond
 #pragma unroll
             for (int k = 0; k < 4; k++)
-                if ((uint32_t)k < n_pend && lt_count_passed(pend_old[k], pend_slot[k])) lt_count_handoff(cnt, pend_slot[k], acc, lt);
+                if (lt_count_passed(pend_old[k], pend_inc[k])) lt_count_handoff(cnt, pend_bucket[k], pend_inc[k], acc, lt);
         }
-        n_pend = 0;
     };
     auto decide_tile = [&](const Rows &r) {
         uint32_t bad[4] = {0, 0, 0, 0};
@@ -616,38 +618,41 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
                 const int pv = mw_part_verdict(fixed4_failbits(g, r.q, j), run.n_iter, run.length);
                 bad[j] = pv == 2 ? 1u : 0u; part_fail[j] = pv == 1;
             }
-        } else if (g.add_hi) {
-            if (A20) {
-                // every byte of the five rows is under the window: OR the rows' verdicts, mask once
+        } else if (A20) {
+            // every byte of the five rows is under the window: OR the rows' verdicts, mask once.  No branch on "rule
+            // off" (--ph below 33) in the tile loop: the mask is then 0, and the verdicts stay in vector registers
+            const uint32_t qm = g.add_hi ? 0x80808080u : 0u;
 #pragma unroll
-                for (int i = 0; i < QR; i++) {
+            for (int i = 0; i < QR; i++) {
 #pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const uint32_t w = u4get(r.q[i], j) & 0x7F7F7F7Fu;       // bit 7 = non-ACGT flag, not quality
-                        bad[j] |= (w + g.add_lo) & ~(w + g.add_hi);
-                    }
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t w = u4get(r.q[i], j) & 0x7F7F7F7Fu;       // bit 7 = non-ACGT flag, not quality
+                    bad[j] |= (w + g.add_lo) & ~(w + g.add_hi);
                 }
-#pragma unroll
-                for (int j = 0; j < 4; j++) bad[j] &= 0x80808080u;
-            } else {
-#pragma unroll
-                for (int i = 0; i < QR; i++)
-                    if (NQ || i < g.nq) fixed4_qrow(g, i, r.q[i], bad);
             }
+#pragma unroll
+            for (int j = 0; j < 4; j++) bad[j] &= qm;
+        } else if (g.add_hi) {
+#pragma unroll
+            for (int i = 0; i < QR; i++)
+                if (NQ || i < g.nq) fixed4_qrow(g, i, r.q[i], bad);
         }
-        // exact stage: table 0 only, the eight bucket reads of the lane's four reads in flight together
-        LtProbe0 p[4]; U2 e0[4], e1[4]; uint32_t klo[4], khi[4], forced[4]; bool cand[4];
+        // exact stage: table 0 only, the eight bucket reads of the lane's four reads in flight together.  Every
+        // per-read verdict is a lane mask (LtPred) from the compare that made it: none becomes a 0/1 register
+        LtProbe0 p[4]; U2 e0[4], e1[4]; uint32_t klo[4], khi[4], forced[4]; LtPred cand[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const uint32_t l = ((j < 2 ? r.len01 : r.len23) >> (16 * (j & 1))) & 0xFFFFu;
-            const bool live = l != F2Q_LEN_SKIP, qf = live && bad[j] != 0u;
+            const LtPred live = LT_P(l != F2Q_LEN_SKIP), qf = live & LT_P(bad[j] != 0u);
             // a read that ends inside the window gives a shorter key (:354); every feature is L long, so it can equal
             // or approach none (:683); its bytes past the end are stored as 0 and never fail the Phred test
-            cand[j] = live && !qf && (int)(l & F2Q_LEN_MASK) >= need && !(MW && part_fail[j]);
-            w_reads += (uint32_t)__popcll(__ballot(live));
-            w_qfail += (uint32_t)__popcll(__ballot(qf));
+            cand[j] = live & LT_NOT(qf) & LT_P((int)(l & F2Q_LEN_MASK) >= need);
+            if (MW) cand[j] = cand[j] & LT_NOT(LT_P(part_fail[j]));
+            w_reads += (uint32_t)__popcll(live);
+            w_qfail += (uint32_t)__popcll(qf);
             forced[j] = 0;
-            if ((l & F2Q_LEN_FLAG) && cand[j]) forced[j] = fixed4_flags(g, r.q, j);   // non-ACGT symbols in the window (rare)
+            if (LT_TRUE(LT_P((l & F2Q_LEN_FLAG) != 0u) & cand[j]))                     // non-ACGT symbols in the window (rare)
+                forced[j] = A20 ? fixed4_flags_whole5(r.q, j) : fixed4_flags(g, r.q, j);
             uint64_t key = fixed4_key(g, r.b, j);
             if (MW && lt.mix) { key = mw_mix(key, lt.mix); if (forced[j]) forced[j] = mw_mix_mask(forced[j], lt.mix); }
             p[j] = lt_probe0(lt, key);
@@ -655,18 +660,17 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
             e1[j] = lds_u2(tg + 2u * p[j].b1);
             klo[j] = (uint32_t)key; khi[j] = lt_rec_hi(key, forced[j]);
         }
-        LtExact x[4];
+        LtExactP x[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) x[j] = lt_exact_stage(p[j], e0[j], e1[j], cand[j], forced[j]);
+        for (int j = 0; j < 4; j++) x[j] = lt_exact_pred(p[j], e0[j], e1[j], cand[j], LT_P(forced[j] == 0u));
         settle();                                               // the previous stage's histogram adds have returned by now
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             pend_old[j] = 0;
-            if (x[j].hit) pend_old[j] = lt_count_add(cnt, x[j].slot);
-            pend_slot[j] = x[j].slot;
-            w_perfect += (uint32_t)__popcll(__ballot(x[j].hit));
+            pend_bucket[j] = x[j].bucket; pend_inc[j] = LT_TRUE(x[j].odd) ? 0x10000u : 1u;
+            if (LT_TRUE(x[j].hit)) pend_old[j] = lt_count_add(cnt, pend_bucket[j], pend_inc[j]);
+            w_perfect += (uint32_t)__popcll(x[j].hit);
         }
-        n_pend = 4;
         if (!NEAR) return;                                      // --m 0: a read without an exact hit matches nothing
         // batch stage: the wave's candidates numbered slot by slot, moved to consecutive lanes with a forward permute
         // (no LDS memory), and decided 64 at a time by the whole --m 1 routine
@@ -674,7 +678,7 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
         pre[0] = 0;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const unsigned long long m = __ballot(x[j].batch);
+            const unsigned long long m = x[j].batch;
             pos[j] = pre[j] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             pre[j + 1] = pre[j] + (uint32_t)__popcll(m);
         }
@@ -684,7 +688,7 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 if (!lt_batch_has(pre, j, lo)) continue;
-                const bool send = x[j].batch && pos[j] - lo < 64u;
+                const bool send = LT_TRUE(x[j].batch) && pos[j] - lo < 64u;
                 const int to = (int)(4u * (send ? pos[j] - lo : lt_dump(pre, j, lo)));
                 const uint32_t a = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)klo[j]);
                 const uint32_t b = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)khi[j]);
@@ -699,10 +703,9 @@ __global__ __launch_bounds__(F2Q_LT_THREADS) void k_count_fixed4_lds(const RunDe
             const LtVerdict v = lt_decide<NEAR>(lt, q, e, lt_rec_forced(rhi), [&](uint32_t bk) { return lds_u2(tg + 2u * bk); });
             settle();
             const LtPred cm = LT_P(valid), perfect = v.perfect & cm, imperfect = v.imperfect & cm;
-            pend_old[0] = 0;
-            if (LT_TRUE(perfect | imperfect)) pend_old[0] = lt_count_add(cnt, v.slot);
-            pend_slot[0] = v.slot;
-            n_pend = 1;
+            pend_old[0] = 0; pend_old[1] = 0; pend_old[2] = 0; pend_old[3] = 0;
+            pend_bucket[0] = v.slot >> 1; pend_inc[0] = lt_count_inc(v.slot);
+            if (LT_TRUE(perfect | imperfect)) pend_old[0] = lt_count_add(cnt, pend_bucket[0], pend_inc[0]);
             w_perfect += (uint32_t)__popcll(perfect);
             w_imperfect += (uint32_t)__popcll(imperfect);
         }

@@ -1285,6 +1285,30 @@ F2Q_HD uint32_t fixed4_flags(const FixedGeom &g, const U4 (&q)[QR], int j)
     return (uint32_t)(bits >> (g.st & 3));
 }
 
+// byte-wise dot product of two words plus c (v_dot4_u32_u8)
+F2Q_HD uint32_t dot4_u8(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_udot4(a, b, c, false);
+#else
+    for (int k = 0; k < 32; k += 8) c += ((a >> k) & 0xFFu) * ((b >> k) & 0xFFu);
+    return c;
+#endif
+}
+// fixed4_flags for a window that is exactly the 20 bytes of five whole quality rows (start a multiple of 4): a row's
+// four flag bits, each worth 128, are gathered into a nibble by one byte-wise dot product with the weights 1, 2, 4, 8
+// (16 .. 128 for the nibble above it, added in the same instruction)
+template <int QR>
+F2Q_HD uint32_t fixed4_flags_whole5(const U4 (&q)[QR], int j)
+{
+    static_assert(QR >= 5, "five rows");
+    const uint32_t m = 0x80808080u, lo = 0x08040201u, hi = 0x80402010u;
+    const uint32_t a = dot4_u8(u4get(q[1], j) & m, hi, dot4_u8(u4get(q[0], j) & m, lo, 0u));    // (rows 0, 1) << 7
+    const uint32_t b = dot4_u8(u4get(q[3], j) & m, hi, dot4_u8(u4get(q[2], j) & m, lo, 0u));    // (rows 2, 3) << 7
+    const uint32_t c = dot4_u8(u4get(q[4], j) & m, lo, 0u);                                     // row 4 << 7
+    return (a >> 7) | (b << 1) | (c << 9);
+}
+
 // Two windows A, B of L bases each: the joined key with its middle quarters swapped, [A_lo B_lo A_hi B_hi] (A_lo = the
 // first L/2 bases of A).  The LDS tables bucket by the halves of the key they are given; with the plain joined key a half
 // IS a window, and in a combinatorial pair library (one guide with many partners) more features share a half than a
@@ -1693,23 +1717,41 @@ F2Q_HD LtVerdict lt_decide(const LtDesc &lt, const LtProbe &q, const U2 (&e)[4],
 struct LtProbe0 { uint32_t b0, b1, w0, w1; };          // table-0 buckets of a key and the tag it would have in each
 F2Q_HD LtProbe0 lt_probe0(const LtDesc &lt, uint64_t key)
 {
+    // lt_hash + lt_tag for both choices, with the multiplies' products used as they are: the fold of lt_perm only
+    // touches the low 10 bits (below the bucket bits), so a tag's scrambled part is bits [F2Q_LT_BBITS, hb0) of the product
     const uint32_t h0 = (uint32_t)key & ((1u << lt.hb0) - 1u), h1 = (uint32_t)(key >> lt.hb0);
+    const uint32_t r0 = lt_mul24(h0, 0x85EBCBu), r1 = lt_mul24(h0, 0x9E3779u);
+    const uint32_t fold = lt.hb0 - 10u, tb = lt.hb0 - F2Q_LT_BBITS, bm = (1u << F2Q_LT_BBITS) - 1u;
     LtProbe0 p;
-    uint32_t c0, c1;
-    lt_hash(h0, lt.hb0, lt.hb1, 0, p.b0, c0);
-    lt_hash(h0, lt.hb0, lt.hb1, 1, p.b1, c1);
-    p.w0 = lt_tag(c0, h1, lt.hb1); p.w1 = lt_tag(c1, h1, lt.hb1);
+    p.b0 = (r0 ^ ((r0 >> fold) & 0x3FFu)) & bm;
+    p.b1 = (r1 ^ ((r1 >> fold) & 0x3FFu)) & bm;
+    p.w0 = (((r0 >> F2Q_LT_BBITS) & ((1u << tb) - 1u)) << lt.hb1) | h1;
+    p.w1 = (((r1 >> F2Q_LT_BBITS) & ((1u << tb) - 1u)) << lt.hb1) | (h1 | 0x80000000u);
     return p;
 }
-// cand: the read is live, passes its Phred test (every part of it, MW) and covers the window
+// cand: the read is live, passes its Phred test (every part of it, MW) and covers the window.  The verdicts are lane
+// predicates (LtPred): in the kernel none becomes a 0/1 register.  The histogram counter of the hit is word `bucket`,
+// upper half if `odd` (slot = 2 * bucket + odd)
+struct LtExactP { LtPred hit, batch, odd; uint32_t bucket; };
+F2Q_HD LtExactP lt_exact_pred(const LtProbe0 &p, const U2 &e0, const U2 &e1, LtPred cand, LtPred unforced)
+{
+    const LtPred a0 = LT_P(e0.x == p.w0), a1 = LT_P(e0.y == p.w0), b0 = LT_P(e1.x == p.w1), b1 = LT_P(e1.y == p.w1);
+    const LtPred first = a0 | a1;
+    LtExactP r;
+    r.hit = cand & unforced & (first | b0 | b1);              // a flagged base equals no feature's base
+    r.batch = cand & LT_NOT(r.hit);
+    r.odd = a1 | (LT_NOT(first) & b1);
+    r.bucket = LT_SEL(first, p.b0, p.b1);
+    return r;
+}
+// the same per read, with the slot spelt out (tests/emu)
 struct LtExact { bool hit, batch; uint32_t slot; };
 F2Q_HD LtExact lt_exact_stage(const LtProbe0 &p, const U2 &e0, const U2 &e1, bool cand, uint32_t forced)
 {
-    const bool a0 = e0.x == p.w0, a1 = e0.y == p.w0, b0 = e1.x == p.w1, b1 = e1.y == p.w1;
+    const LtExactP x = lt_exact_pred(p, e0, e1, LT_P(cand), LT_P(forced == 0u));
     LtExact r;
-    r.hit = cand && forced == 0u && (a0 | a1 | b0 | b1);      // a flagged base equals no feature's base
-    r.batch = cand && !r.hit;
-    r.slot = (a0 | a1) ? 2u * p.b0 + (uint32_t)a1 : 2u * p.b1 + (uint32_t)b1;
+    r.hit = LT_TRUE(x.hit); r.batch = LT_TRUE(x.batch);
+    r.slot = 2u * x.bucket + (LT_TRUE(x.odd) ? 1u : 0u);
     return r;
 }
 // a batch record: two dwords, the key (2L <= 42 bits) and the flagged-base mask (L <= 21 bits)

@@ -115,6 +115,7 @@ struct f2q_ctx {
     bool force_general = false;           // F2Q_FORCE_GENERAL=1: every read through the byte-exact general kernel (cross-checks)
     bool force_v1 = false;                // F2Q_FORCE_V1=1: keep the one-read-per-lane kernel (A/B runs)
     bool no_lt = false;                   // F2Q_NO_LT=1: never the LDS-table kernel (A/B runs, cross-checks)
+    uint32_t lt_max_wgs = 0;              // F2Q_LT_WGS=n: at most n workgroups of the LDS-table kernel (tests: many reads per histogram)
     bool no_pt = false;                   // F2Q_NO_PT=1: never the partitioned-table kernels (A/B runs, cross-checks)
     uint64_t pt_chunk_reads = (uint64_t)1 << 28;   // F2Q_PT_CHUNK: most reads per scatter/count round of the partitioned path (1.7 GB of streams per 200 M reads; 400 M reads in two rounds run 8 % faster than in six)
     uint64_t pt_min_reads = (uint64_t)1 << 21;     // F2Q_PT_MIN_READS: smaller blocks keep the packed-table kernel (three launches and the
@@ -350,6 +351,7 @@ extern "C" int f2q_create(const f2q_params *p, f2q_ctx **out)
     { const char *dc = getenv("F2Q_DEV_CACHE_MB"); if (dc && atol(dc) >= 0) c->dev_idle_cap = (size_t)atol(dc) << 20; }
     { const char *fv = getenv("F2Q_GENERIC"); c->force_generic = fv && fv[0] == '1'; }
     { const char *fv = getenv("F2Q_NO_LT"); c->no_lt = fv && fv[0] == '1'; }
+    { const char *fv = getenv("F2Q_LT_WGS"); if (fv && atoi(fv) > 0) c->lt_max_wgs = (uint32_t)atoi(fv); }
     { const char *fv = getenv("F2Q_NO_HOT"); c->no_hot = fv && fv[0] == '1'; }
     { const char *fv = getenv("F2Q_NO_PT"); c->no_pt = fv && fv[0] == '1'; }
     { const char *fv = getenv("F2Q_PT_PARTS"); if (fv && atoi(fv) > 0) c->ix.pt_force_parts = std::min(atoi(fv), (int)F2Q_PT_MAXP); }
@@ -865,7 +867,7 @@ static auto fixed_lds_kernel(bool near, FixedVariant fv)
 static int launch_fixed_lds(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches, bool mw)
 {
     const uint32_t wgs = (pb.n_tiles + F2Q_LT_WAVES - 1) / F2Q_LT_WAVES;
-    const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu);
+    const uint32_t grid = std::min<uint32_t>(wgs, c->lt_max_wgs ? std::min<uint32_t>(c->lt_max_wgs, (uint32_t)c->n_cu) : (uint32_t)c->n_cu);
     const bool near = c->run_h.miss > 0;
     const size_t shmem = ((near ? 2u : 1u) * (size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4;
     const FixedVariant fv = fixed_variant(c, mw ? fixed_geom_at(0, c->run_h.n_iter * c->run_h.length, c->run_h.thr) : fixed_geom(c->run_h));
