@@ -22,6 +22,7 @@ EXPORTS = (
     "f2q_text_upload", "f2q_count_text", "f2q_text_free", "f2q_text_from_bgzf", "f2q_text_read",
     "f2q_set_mate2", "f2q_count_block_paired", "f2q_block_from_fastq_paired", "f2q_count_file_paired",
     "f2q_set_assign_library", "f2q_ec_assign", "f2q_ec_fetch_assigned",
+    "f2q_set_umi", "f2q_read_umis",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
@@ -171,6 +172,8 @@ def load(path=None):
     L.f2q_set_assign_library.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32]
     L.f2q_ec_assign.argtypes = [vp, i64p, i64p, C.POINTER(Timing)]
     L.f2q_ec_fetch_assigned.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.f2q_set_umi.argtypes = [vp, C.c_int32, C.c_int32]
+    L.f2q_read_umis.argtypes = [vp, i64p, i64p]
     if path == LIB_PATH:
         _lib = L
     return L
@@ -240,11 +243,14 @@ class Counter:
     ``features``: ordered list of sequences as features_loader leaves them
     (upper-case, blanks removed, unique); row i of the count vector is feature i.
 
+    ``umi=(S, L)`` counts distinct UMIs per feature (f2q_set_umi): the UMI is read positions [S, S + L); Counter mode,
+    single reads; ``read_umis()`` returns them.
+
     ``start2`` ("b[,b...]" or a list) makes it a paired context (f2q_set_mate2): ``start`` names the windows in mate 1,
     ``start2`` those in mate 2, ``rc2`` takes mate 2 reverse-complemented; such a context counts with the *_paired calls.
     """
 
-    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, **params):
+    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -256,8 +262,15 @@ class Counter:
         self.n_features = 0
         self.n_assign = 0
         self.paired = False
-        if start2 is not None:
-            self.set_mate2(start2, rc2)
+        self.umi = None
+        try:
+            if start2 is not None:
+                self.set_mate2(start2, rc2)
+            if umi is not None:
+                self.set_umi(*umi)
+        except BaseException:
+            self.close()
+            raise
         if features is not None:
             self.set_features(features)
 
@@ -309,6 +322,11 @@ class Counter:
         arr = (C.c_int32 * max(len(st), 1))(*st)
         self._check(self._L.f2q_set_mate2(self._h, arr, len(st), 1 if rc2 else 0))
         self.paired = True
+
+    def set_umi(self, start, length):
+        """the UMI window of every read (f2q_set_umi); before counting"""
+        self._check(self._L.f2q_set_umi(self._h, int(start), int(length)))
+        self.umi = (int(start), int(length))
 
     # -- counting: paired-end --
     @staticmethod
@@ -484,6 +502,14 @@ class Counter:
         self._check(self._L.f2q_read_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_int64)),
                                             stats.ctypes.data_as(C.POINTER(C.c_int64))))
         return counts[:self.n_features], stats
+
+    def read_umis(self):
+        """(umis[n_features], umi_reads, umi_failed): distinct UMIs per feature, assigned reads with a valid / an invalid UMI"""
+        umis = np.zeros(max(self.n_features, 1), dtype=np.int64)
+        extra = np.zeros(2, dtype=np.int64)
+        self._check(self._L.f2q_read_umis(self._h, umis.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          extra.ctypes.data_as(C.POINTER(C.c_int64))))
+        return umis[:self.n_features], int(extra[0]), int(extra[1])
 
     def counts_device_ptr(self):
         p, n = C.c_void_p(), C.c_uint64()

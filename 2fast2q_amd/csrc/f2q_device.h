@@ -1021,16 +1021,90 @@ F2Q_HD void ec_count_key(const EcDev &ec, const KV &kv, unsigned long long read_
 }
 
 // ---------------------------------------------------------------------------------------------
+// distinct UMIs per feature (--umi S,L: Counter mode, the byte-exact road only)
+// ---------------------------------------------------------------------------------------------
+// The UMI of a read is upper(seq[S:S+L]), 1 <= L <= 16: valid only when the read holds all L bases, each is A/C/G/T and
+// the quality slice [S:S+L] is all there and passes --ph by the rule of a feature window (thr < 33: no test).  A read
+// that match_key assigns to feature f (exactly or within --m) and whose UMI u is valid brings the pair (f, u); the set
+// below holds every pair once, umis[f] counts the pairs of f.  UMIs are compared by identity (no error collapsing).
+#define F2Q_UMI_MAXLEN 16
+#define F2Q_UMI_READS 0              // words of UmiDev.ctr: assigned reads with a valid UMI ...
+#define F2Q_UMI_FAILED 1             // ... with an invalid one
+#define F2Q_UMI_OVERFLOW 2           // a probe sequence found no room (the host sizes the set so that it cannot)
+#define F2Q_UMI_HELD 3               // pairs the set holds
+#define F2Q_UMI_CTR_WORDS 4
+struct UmiDev {
+    unsigned long long *slots;       // open addressing: (feature << 32) | 2-bit codes of the UMI, base j in bits 2j..2j+1; ~0 = empty
+    uint32_t mask;                   // slots - 1
+    int32_t start, length;           // the window [start, start + length) of the read
+    unsigned long long *umis;        // [n_features] distinct UMIs seen per feature
+    unsigned long long *ctr;         // [F2Q_UMI_CTR_WORDS]
+};
+// claims a slot for word k with one CAS: 1 = new, 0 = already there, 2 = no room (probe bound, as ec64_insert_word)
+F2Q_HD uint32_t umi_claim(const UmiDev &u, unsigned long long k)
+{
+    uint32_t s = hash32(k ^ (k >> 29), 32) & u.mask;
+    for (uint32_t guard = 0; guard <= u.mask; guard++) {
+        unsigned long long v = F2Q_LD64(&u.slots[s]);
+        if (v == KEY_EMPTY) {
+            v = ec_cas(&u.slots[s], KEY_EMPTY, k);
+            if (v == KEY_EMPTY) return 1u;
+        }
+        if (v == k) return 0u;
+        s = (s + 1) & u.mask;
+    }
+    F2Q_ST64(&u.ctr[F2Q_UMI_OVERFLOW], 1ull);
+    return 2u;
+}
+// the pair (f, codes): 1 when it is new -- the claim adds 1 to umis[f] -- else 0
+F2Q_HD uint32_t umi_insert(const UmiDev &u, uint32_t f, uint32_t codes)
+{
+    if (umi_claim(u, ((unsigned long long)f << 32) | codes) != 1u) return 0u;
+    acc_add(&u.umis[f], 1ull);
+    return 1u;
+}
+// the UMI of a read as 2-bit codes; false: invalid
+template <class P>
+F2Q_HD bool umi_codes(const UmiDev &u, int thr, P seq, int r, P qual, int qn, uint32_t &codes)
+{
+    const int a = u.start, b = u.start + u.length;
+    if (b > r || b > qn) return false;
+    if (qual_range_fails(qual, a, b, thr)) return false;
+    uint32_t w = 0;
+    for (int j = a; j < b; j++) {
+        const uint32_t c = base_code(up8(seq[j]));
+        if (c > 3u) return false;
+        w |= c << (2 * (j - a));
+    }
+    codes = w;
+    return true;
+}
+// general_read calls hook.assigned(idx) for a read match_key has given feature idx; the default does nothing
+struct NoReadHook { F2Q_HD void assigned(uint32_t) const {} };
+// ust: thread-local sums -- [0] valid, [1] invalid, [2] new pairs
+template <class P>
+struct UmiHook {
+    const UmiDev *u; int thr; P seq; int r; P qual; int qn; unsigned long long *ust;
+    F2Q_HD void assigned(uint32_t f) const
+    {
+        uint32_t codes = 0;
+        if (umi_codes(*u, thr, seq, r, qual, qn, codes)) { ust[0]++; ust[2] += umi_insert(*u, f, codes); }
+        else ust[1]++;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
 // general path: one read given as raw bytes.  st[] = the 5 reference counters (thread-local).
 // ---------------------------------------------------------------------------------------------
 // WORDS: see gk_exact (true where this routine is the main road: k_count_general, the host twin)
 // PAIRED: the record is a merged pair, seq = mate 1 (r1 bytes) then mate 2 as the run takes it, qual likewise (qn1 bytes
 // of mate 1 first); a fixed window is sliced inside its own mate, so it clips at the end of THAT mate (:354 per mate)
-template <class P, bool WORDS = false, bool PAIRED = false>
+// HOOK: see NoReadHook (the default: every instantiation without one is the routine as it was)
+template <class P, bool WORDS = false, bool PAIRED = false, class HOOK = NoReadHook>
 F2Q_HD void general_read(const RunDev &run, const LibDev &lib, const EcDev &ec, const Accum &acc,
                          P seq, int r, P qual, int qn,
                          unsigned long long read_index, unsigned long long st[5], uint32_t *n_new = nullptr,
-                         int r1 = 0, int qn1 = 0)
+                         int r1 = 0, int qn1 = 0, const HOOK &hook = HOOK())
 {
     KeyViewT<P> kv; kv.seq = seq; kv.nseg = 0; kv.len = 0;
     bool all_failed = true;
@@ -1060,7 +1134,7 @@ F2Q_HD void general_read(const RunDev &run, const LibDev &lib, const EcDev &ec, 
         if (run.mode == 0) {
             uint32_t idx = 0;
             int res = match_key<WORDS>(run, lib, kv, idx);
-            if (res == 1 || res == 2) acc_add(&acc.counts[idx], 1ull);
+            if (res == 1 || res == 2) { acc_add(&acc.counts[idx], 1ull); hook.assigned(idx); }
             st[res]++;
         } else {
             ec_count_key(ec, kv, read_index, n_new);

@@ -32,6 +32,7 @@ using namespace f2q;
 #include "f2q_pair_kernels.h"
 #include "f2q_inflate_kernels.h"
 #include "f2q_assign_kernels.h"
+#include "f2q_umi_kernels.h"
 
 // ===============================================================================================
 // host side
@@ -108,6 +109,15 @@ struct f2q_ctx {
     AssignDev asg{};
     uint64_t asg_nb = 0, asg_nw = 0;     // entries / slots the per-key arrays cover
     uint64_t ec_gen = 1, asg_gen = 0;    // ec_gen: bumped by every count call, reset and table growth
+    // distinct UMIs per feature (f2q_set_umi): the set of (feature, UMI) pairs, umis[n_features] and the counters.  The set
+    // outlives the pieces of a file; umi_reserve sizes it before every launch
+    bool umi_on = false;
+    UmiDev umi{};
+    std::vector<void *> umi_set_allocs, umi_fix_allocs;      // the slots / umis[] and the counters
+    uint64_t umi_slots = 0, umi_min_slots = (uint64_t)1 << 16;   // F2Q_UMI_SLOTS: the first set's size (tests: growth from a small one)
+    uint64_t umi_held_ub = 0;            // pairs held, an upper bound: every record launched since the last exact reading taken as new
+    uint64_t umi_rehashes = 0;
+    bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
     int n_cu = 256;
     bool force_generic = false;           // F2Q_GENERIC=1: run-time window geometry even where a specialisation exists
@@ -399,6 +409,8 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
     free_all(c, c->lib_allocs); free_all(c, c->ec_allocs); free_all(c, c->ec_allocs64); free_all(c, c->ec_allocs_ctr); free_all(c, c->hot_allocs);
     free_all(c, c->asg_lib_allocs); free_all(c, c->asg_allocs);
+    if (c->trace && c->umi_on) fprintf(stderr, "[f2q trace] UMI set: %llu slots, %llu rehashes\n", (unsigned long long)c->umi_slots, (unsigned long long)c->umi_rehashes);
+    free_all(c, c->umi_set_allocs); free_all(c, c->umi_fix_allocs);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
@@ -452,6 +464,10 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (rc) return rc;
     rc = alloc_acc(c, n);
     if (rc) return rc;
+    if (c->umi_on) {                                  // umis[] has a word per feature: a new library starts a new set
+        free_all(c, c->umi_set_allocs); free_all(c, c->umi_fix_allocs);
+        c->umi.slots = nullptr; c->umi.umis = nullptr; c->umi.ctr = nullptr; c->umi_slots = 0; c->umi_held_ub = 0;
+    }
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
     // symbol of any feature), every other odd symbol still sends the read to the byte-exact routine
@@ -471,6 +487,12 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
         c->aux_busy = false;
         free_all(c, c->ec_allocs); free_all(c, c->ec_allocs64); free_all(c, c->ec_allocs_ctr);
         memset(&c->ec, 0, sizeof c->ec); c->ec_slots = 0; c->hot_valid = false; c->ec_learned = 0;
+    }
+    if (c->umi_on && c->umi.umis) {
+        if (c->umi.slots) HIPC(c, hipMemsetAsync(c->umi.slots, 0xFF, c->umi_slots * sizeof(unsigned long long), c->stream));
+        HIPC(c, hipMemsetAsync(c->umi.umis, 0, std::max<uint64_t>(c->lib_h.n_features, 1) * sizeof(unsigned long long), c->stream));
+        HIPC(c, hipMemsetAsync(c->umi.ctr, 0, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), c->stream));
+        c->umi_held_ub = 0;
     }
     c->reads_seen = 0;
     c->ec_gen++;
@@ -501,6 +523,42 @@ extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 {
     if (!c || !dptr || !n_int64) return F2Q_EINVAL;
     *dptr = c->acc_d; *n_int64 = c->acc_n;
+    return F2Q_OK;
+}
+
+// ---- distinct UMIs per feature: the ABI ---------------------------------------------------------------------------
+extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi takes a Counter context: Extract+Count assigns no read to a feature");
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) is not implemented");
+    if (c->umi_on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
+    if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
+        return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
+    c->umi_on = true; c->umi.start = start; c->umi.length = length;
+    { const char *e = getenv("F2Q_UMI_SLOTS"); if (e && atol(e) > 0) { c->umi_min_slots = 2; while (c->umi_min_slots < (uint64_t)atol(e) && c->umi_min_slots < (1ull << 32)) c->umi_min_slots <<= 1; } }
+    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
+    c->force_general = true;
+    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
+    c->plan.inband_n = false; c->plan.n_only = false;
+    return F2Q_OK;
+}
+
+extern "C" int f2q_read_umis(f2q_ctx *c, int64_t *umis, int64_t extra[2])
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->umi_on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    HIPC(c, hipSetDevice(c->device));
+    const uint64_t nf = c->lib_h.n_features;
+    std::vector<unsigned long long> h(nf + F2Q_UMI_CTR_WORDS, 0ull);
+    if (c->umi.umis) {                                           // (nothing counted yet: all zero)
+        if (nf) HIPC(c, hipMemcpyAsync(h.data(), c->umi.umis, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(h.data() + nf, c->umi.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (h[nf + F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+    if (umis) for (uint64_t i = 0; i < nf; i++) umis[i] = (int64_t)h[i];
+    if (extra) { extra[0] = (int64_t)h[nf + F2Q_UMI_READS]; extra[1] = (int64_t)h[nf + F2Q_UMI_FAILED]; }
     return F2Q_OK;
 }
 
@@ -930,6 +988,55 @@ static int launch_fixed_v1(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32
     return F2Q_OK;
 }
 
+// ---- distinct UMIs per feature -------------------------------------------------------------------------------------
+// the (feature, UMI) set before a launch over n records: afterwards it is at most half full even if every record brings a
+// new pair, so k_count_umi always finds room.  The pairs held are read from the device only when the bound kept on the
+// host says the set might be too small; a set that is grows to hold twice what it must (amortised rehash).  The new set
+// is allocated before the old one is given back: a failed allocation leaves the context as it was.
+static int umi_reserve(f2q_ctx *c, uint64_t n)
+{
+    int rc;
+    if (!c->umi.umis) {
+        UmiDev u = c->umi; std::vector<void *> owner;
+        if ((rc = dev_alloc(c, (size_t)std::max<uint64_t>(c->lib_h.n_features, 1), &u.umis, owner, 0)) ||
+            (rc = dev_alloc(c, (size_t)F2Q_UMI_CTR_WORDS, &u.ctr, owner, 0))) {
+            free_all(c, owner);
+            return fail(c, F2Q_ENOMEM, "no device memory for the UMI counters: " + c->err);
+        }
+        c->umi.umis = u.umis; c->umi.ctr = u.ctr; c->umi_fix_allocs = owner;
+    }
+    if (c->umi.slots && 2 * (c->umi_held_ub + n) <= c->umi_slots) { c->umi_held_ub += n; return F2Q_OK; }
+    unsigned long long ctr[F2Q_UMI_CTR_WORDS] = {0, 0, 0, 0};
+    if (c->umi.slots) {
+        HIPC(c, hipMemcpyAsync(ctr, c->umi.ctr, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+        if (2 * (ctr[F2Q_UMI_HELD] + n) <= c->umi_slots) { c->umi_held_ub = ctr[F2Q_UMI_HELD] + n; return F2Q_OK; }
+    }
+    const uint64_t held = ctr[F2Q_UMI_HELD];
+    uint64_t slots = std::max<uint64_t>(c->umi_min_slots, 2);
+    while (slots < 2 * (held + n) || slots < 4 * held) slots <<= 1;
+    if (slots > (1ull << 32)) return fail(c, F2Q_ENOMEM, "the UMI set would exceed 2^32 slots");
+    UmiDev fresh = c->umi; std::vector<void *> owner;
+    if ((rc = dev_alloc(c, (size_t)slots, &fresh.slots, owner, 0xFF))) {
+        free_all(c, owner);
+        return fail(c, F2Q_ENOMEM, "no device memory for a UMI set of " + std::to_string(slots) + " slots: " + c->err);
+    }
+    fresh.mask = (uint32_t)(slots - 1);
+    if (c->umi.slots && held) {
+        hipLaunchKernelGGL(k_umi_rehash, dim3((unsigned)((c->umi_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi, fresh);
+        HIPC(c, hipGetLastError());
+        c->umi_rehashes++;
+        if (c->trace) fprintf(stderr, "[f2q trace] UMI set rehash %llu: %llu pairs, %llu -> %llu slots\n", (unsigned long long)c->umi_rehashes,
+                              (unsigned long long)held, (unsigned long long)c->umi_slots, (unsigned long long)slots);
+    }
+    free_all(c, c->umi_set_allocs);                              // (waits for the stream)
+    c->umi_set_allocs = owner;
+    c->umi.slots = fresh.slots; c->umi.mask = fresh.mask; c->umi_slots = slots;
+    c->umi_held_ub = held + n;
+    return F2Q_OK;
+}
+
 // one set of launches over a view of a block (all of it in Counter mode, a step of it in Extract+Count mode)
 static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, Accum &acc, uint32_t &launches)
 {
@@ -951,6 +1058,14 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
     rb.first_index += c->reads_seen;
     const uint64_t wg = (rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
+    if (c->umi_on) {                                             // the same road with the (feature, UMI) set (f2q_set_umi)
+        if ((rc = umi_reserve(c, rb.n))) return rc;
+        hipLaunchKernelGGL(k_count_umi, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, "k_count_umi");
+        return F2Q_OK;
+    }
     if (rb.len1) hipLaunchKernelGGL(k_count_general<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     else hipLaunchKernelGGL(k_count_general<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     HIPC(c, hipGetLastError());
@@ -1086,6 +1201,8 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
 {
     if (!k0) { k0 = c->ev_k0; k1 = c->ev_k1; }          // (a queued step brings its own pair)
     if (c->prm.mode == 0 && !c->have_lib) return fail(c, F2Q_ESTATE, "f2q_set_features must be called before counting in Counter mode");
+    if (c->umi_on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
+    c->counted = true;
     Accum acc{c->acc_d, c->acc_d + (c->acc_n - 5), nullptr, nullptr, nullptr, nullptr};
 #ifdef F2Q_STAMP
     static unsigned long long *stamp_d = nullptr;
@@ -1556,6 +1673,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
 {
     if (!c) return F2Q_EINVAL;
     if (c->have_lib || c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_mate2 comes once, after f2q_create and before f2q_set_features");
+    if (c->umi_on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only");
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
     for (int i = 0; i < n_start2; i++) if (start2[i] < 0) return fail(c, F2Q_EINVAL, "a mate-2 window starts before the mate");
@@ -2226,6 +2344,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
 {
     if (!c || !path || world == 0 || rank >= world) return F2Q_EINVAL;
     if (int rc = single_only(c)) return rc;
+    if (c->umi_on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     size_t CH = file_chunk_bytes((size_t)256 << 20);
     TextSource src;
@@ -2509,6 +2628,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
 {
     if (!c || !path || !census || world == 0 || rank >= world || !piece_bytes_ok(piece_bytes)) return F2Q_EINVAL;
     if (int rc = single_only(c)) return rc;
+    if (c->umi_on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }

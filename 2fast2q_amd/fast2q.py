@@ -105,11 +105,14 @@ def _counter_kwargs(param):
     if param.get('paired'):                         # a paired context: the windows of mate 2 and its direction (f2q_set_mate2)
         plain = {k: v for k, v in param.items() if k != 'paired'}
         return dict(_counter_kwargs(plain), start2=param['start2'], rc2=bool(param.get('rc2')))
-    return dict(mode=param['Running Mode'], miss=param['miss'], phred=param['phred'], length=param['length'],
-                start=param['start'], upstream=param['upstream'], downstream=param['downstream'],
-                miss_search_up=param['miss_search_up'], miss_search_down=param['miss_search_down'],
-                qual_up=param['qual_up'], qual_down=param['qual_down'],
-                device=int(param.get('device', os.environ.get("F2Q_DEVICE", os.environ.get("LOCAL_RANK", 0)))))
+    kwargs = dict(mode=param['Running Mode'], miss=param['miss'], phred=param['phred'], length=param['length'],
+                  start=param['start'], upstream=param['upstream'], downstream=param['downstream'],
+                  miss_search_up=param['miss_search_up'], miss_search_down=param['miss_search_down'],
+                  qual_up=param['qual_up'], qual_down=param['qual_down'],
+                  device=int(param.get('device', os.environ.get("F2Q_DEVICE", os.environ.get("LOCAL_RANK", 0)))))
+    if param.get('umi'):                            # a UMI context (f2q_set_umi); part of the key contexts are kept under
+        kwargs['umi'] = tuple(param['umi'])
+    return kwargs
 
 
 # ---- contexts are kept between samples ----------------------------------------------------------------------------
@@ -222,6 +225,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
     assign = list(param['assign_features']) if param.get('assign') and not counter_mode else None
     if assign is not None and sharding.world().size > 1:
         raise RuntimeError("--as: assignments are not merged across several ranks; run one process")
+    if param.get('umi') and sharding.world().size > 1:
+        raise RuntimeError("--umi: the UMI sets are not merged across several ranks; run one process")
     ctx = _context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
@@ -249,6 +254,9 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             # every key's feature (f2q_ec_assign)
             acounts, stats = ctx.ec_assign()
             param.setdefault('assigned', {})[raw] = ([int(n) for n in acounts], ctx.ec_assigned())
+        if param.get('umi'):                        # distinct UMIs per feature and the two sample-level counters (f2q_read_umis)
+            umis, umi_reads, umi_failed = ctx.read_umis()
+            param.setdefault('umi_counted', {})[raw] = ([int(n) for n in umis], umi_reads, umi_failed)
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -326,6 +334,16 @@ def aligner(i, raw, features, param, reads_stats):
             csv_writer(os.path.join(param["directory"], sample.name + "_assigned.csv"),
                        [["#key", "reads", "feature_name", "mismatches"]] +
                        [[key, n, names[f] if f >= 0 else "", d] for key, n, _first, f, d in arows])
+    if raw in param.get('umi_counted', {}):          # --umi: the same rows holding distinct UMIs instead of reads
+        umis, umi_reads, umi_failed = param['umi_counted'].pop(raw)
+        names = [f.name for f in features.values()]
+        param.setdefault("umi_samples", {})[sample.name] = SampleResult(sample.name, value, unit, _sample_rows(zip(names, umis)),
+                                                                        dict(local, umi_reads=umi_reads, umi_failed=umi_failed))
+        if not param.get("delete", True) and sharding.world().rank == 0:
+            os.makedirs(param["directory"], exist_ok=True)
+            both = _sample_rows((f.name, (f.counts, n)) for f, n in zip(features.values(), umis))      # (the order of `rows`)
+            csv_writer(os.path.join(param["directory"], sample.name + "_umi_reads.csv"),
+                       [["#Feature", "Reads", "UMIs"]] + [[name, reads, n] for name, (reads, n) in both])
     if not param['Progress bar']:
         colourful_errors("INFO", f"Sample {sample.name} was processed in {value} {unit}")
     param.setdefault("samples", {})[sample.name] = sample     # a later file of the same name replaces the earlier one,
@@ -388,6 +406,8 @@ def initializer(cmd):
         print(f" Extracted sequences are assigned to the features of {param['feature']} ({param['miss']} mismatches allowed)")
     if param.get('paired'):
         print(f" Paired-end: mate 2 start position: {param['start2']}" + (" (mate 2 reverse-complemented)" if param['rc2'] else ""))
+    if param.get('umi'):
+        print(f" Distinct UMIs are counted per feature: UMI start position in the read: {param['umi'][0]}, length: {param['umi'][1]}bp")
     print(f" All data will be saved into {param['directory']}")
     print("\n ---- ")
     param["cpu"] = param["cpu"] if isinstance(param["cpu"], int) and param["cpu"] > 0 else (os.cpu_count() or 1)
@@ -423,6 +443,14 @@ def ensure_example_fastq():
     return path
 
 
+def parse_umi(text):
+    """(S, L) of a --umi value, None for a malformed or out-of-range one"""
+    m = re.fullmatch(r"\s*(\d+)\s*,\s*(\d+)\s*", str(text))
+    if not m or int(m.group(1)) > 0x3FFFFFFF or not 1 <= int(m.group(2)) <= 16:
+        return None
+    return int(m.group(1)), int(m.group(2))
+
+
 def input_parser(argv=None):
     """the reference's flag set (:1193-1216) and defaults (:1246-1309), plus --gpu (device ordinal)"""
     ap = argparse.ArgumentParser(prog="2fast2q")
@@ -452,6 +480,7 @@ def input_parser(argv=None):
     ap.add_argument("--pe", nargs='?', const=True, help="Paired-end: the files of --s are paired by name (_R1/_R2, else _1/_2); --st names the feature parts in mate 1, --st2 those in mate 2")
     ap.add_argument("--st2", help="With --pe: the start position(s) of the feature part(s) within mate 2")
     ap.add_argument("--rc2", nargs='?', const=True, help="With --pe: mate 2 is reverse-complemented before its parts are taken")
+    ap.add_argument("--umi", help="S,L: every read carries a UMI of L bases (1-16) at position S; Counter mode also reports the distinct UMIs per feature (<name>_umi.csv)")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
     if args.v is not None:
@@ -501,6 +530,17 @@ def input_parser(argv=None):
     elif args.st2 is not None or args.rc2 is not None:
         colourful_errors("FATAL", f"{'--st2' if args.st2 is not None else '--rc2'} only has a meaning with --pe.")
         sys.exit(2)
+    if args.umi is not None:
+        if p['Running Mode'] != "C":
+            colourful_errors("FATAL", "--umi only has a meaning in Counter mode: it cannot be combined with --mo EC.")
+            sys.exit(2)
+        if args.pe is not None:
+            colourful_errors("FATAL", "--umi takes single reads: it cannot be combined with --pe.")
+            sys.exit(2)
+        p['umi'] = parse_umi(args.umi)
+        if p['umi'] is None:
+            colourful_errors("FATAL", f"--umi {args.umi}: expected S,L with a start S >= 0 and a length 1 <= L <= 16.")
+            sys.exit(2)
     if args.assign is not None:
         if p['Running Mode'] != "EC":
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
@@ -541,6 +581,9 @@ def file_sizer_split(param):
         files = [r1 for r1, _ in pairs]
     if param.get('assign') and sharding.world().size > 1:
         colourful_errors("FATAL", "--as: assignments are not merged across several ranks; run one process.")
+        sys.exit(2)
+    if param.get('umi') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--umi: the UMI sets are not merged across several ranks; run one process.")
         sys.exit(2)
     param["sequencing_files"] = {"len_files": len(files), "preprocess_files": files[:1], "files": files}
     return param
@@ -621,6 +664,8 @@ def run_headers(param):
     if param.get('paired'):
         lines += [f"#Paired-end, feature start position in mate 2: {param['start2']}",
                   f"#Mate 2 reverse-complemented: {'yes' if param['rc2'] else 'no'}"]
+    if param.get('umi'):
+        lines.append(f"#UMI start position in the read, length: {param['umi'][0]},{param['umi'][1]}")
     return lines
 
 
@@ -654,6 +699,10 @@ def compiling(param):
         _, ahead, atable = compile_table(param["assign_samples"])
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_features.csv"),
                    [ahead] + [[feature] + counts for feature, counts in atable.items()])
+    if param.get("umi_samples"):                     # --umi: <name>.csv's layout and row order, distinct UMIs instead of reads
+        _, uhead, utable = compile_table(param["umi_samples"])
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_umi.csv"),
+                   [uhead] + [[feature] + counts for feature, counts in utable.items()])
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -670,6 +719,9 @@ STATS_HEAD = ["#Sample name", "Running Time", "Running Time unit", "Total number
               'Number of reads that did not pass quality filtering.']
 
 
+UMI_STATS_HEAD = ["#Sample name (UMI)", "Number of aligned reads with a valid UMI", "Number of aligned reads with an invalid UMI"]
+
+
 def run_stats(headers, param, compiled, head, ordered):
     """<name>_stats.csv -- the run's '#key: value' lines, the column names, one row of numbers per sample (:1386-1412,
     taken from the counters themselves) -- plus the four overview plots (:1414-1527)"""
@@ -677,6 +729,9 @@ def run_stats(headers, param, compiled, head, ordered):
              s.stats["perfect_counter"], s.stats["imperfect_counter"], s.stats["non_aligned_counter"],
              s.stats["quality_failed"]] for s in ordered]
     global_stat = [[line] for line in headers] + [STATS_HEAD] + rows
+    if param.get("umi_samples"):                     # --umi: the two sample-level counters, one line per sample
+        global_stat += [UMI_STATS_HEAD] + [[s.name, u.stats["umi_reads"], u.stats["umi_failed"]]
+                                           for s in ordered for u in [param["umi_samples"].get(s.name)] if u is not None]
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib

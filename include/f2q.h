@@ -295,6 +295,30 @@ int f2q_ec_assign(f2q_ctx *ctx, int64_t *counts, int64_t stats[5], f2q_timing *t
  * changed since that f2q_ec_assign (a counting call, f2q_reset_counts) or it was never called. */
 int f2q_ec_fetch_assigned(f2q_ctx *ctx, int32_t *feature, int32_t *dist);
 
+/* ---- distinct UMIs per feature ---------------------------------------------------------------
+ * Libraries with an inline UMI next to the feature: how many MOLECULES does a feature's read count stand for?  The
+ * reference has no counterpart; the verdict of every read stays the reference's (fast2q.py:362-380), so counts, the
+ * five counters and everything made from them are what the same context gives without the call.
+ *
+ * f2q_set_umi names the UMI window [start, start + length) of every read, a plain read position in fixed-offset and
+ * anchored runs alike; after f2q_create and before counting.  F2Q_ESTATE on an Extract+Count or a paired context, when
+ * called twice or after a counting call; F2Q_EINVAL unless start >= 0 and 1 <= length <= 16.  From then on every read
+ * of the context takes the byte-exact raw-record road (k_count_umi) through every counting entry point; f2q_set_mate2,
+ * and the sharded calls with world > 1, return F2Q_ESTATE (the sets of several ranks are not merged).
+ *
+ * The UMI of a read is upper(seq[start:start+length]); it is valid when the read holds all `length` bases, each of them
+ * is A/C/G/T, and the quality slice of the same positions is complete and passes --ph by the rule of a feature window
+ * (fast2q.py:355-360).  A read assigned to feature f, exactly or within --m, with a valid UMI u brings the pair (f, u);
+ * UMIs are compared by identity (no error collapsing).  The set of pairs lives across the pieces of a file and across
+ * counting calls until f2q_reset_counts; it grows through the context's device-memory cache (F2Q_ENOMEM: a larger set
+ * could not be allocated, the old one is intact).
+ *
+ * f2q_read_umis (synchronises the stream, as f2q_read_counts): umis[n_features] = distinct UMIs seen per feature;
+ * extra[0] = assigned reads with a valid UMI, extra[1] = assigned reads with an invalid one; extra[0] + extra[1] ==
+ * F2Q_PERFECT + F2Q_IMPERFECT.  Either pointer may be NULL.  F2Q_ESTATE without f2q_set_umi. */
+int f2q_set_umi(f2q_ctx *ctx, int32_t start, int32_t length);
+int f2q_read_umis(f2q_ctx *ctx, int64_t *umis, int64_t extra[2]);
+
 #ifdef __cplusplus
 }
 #endif
