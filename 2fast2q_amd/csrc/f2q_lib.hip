@@ -125,7 +125,7 @@ struct f2q_ctx {
     bool force_general = false;           // F2Q_FORCE_GENERAL=1: every read through the byte-exact general kernel (cross-checks)
     bool force_v1 = false;                // F2Q_FORCE_V1=1: keep the one-read-per-lane kernel (A/B runs)
     bool no_lt = false;                   // F2Q_NO_LT=1: never the LDS-table kernel (A/B runs, cross-checks)
-    uint32_t lt_max_wgs = 0;              // F2Q_LT_WGS=n: at most n workgroups of the LDS-table kernel (tests: many reads per histogram)
+    uint32_t lt_max_wgs = 0;              // F2Q_LT_WGS=n: at most n workgroups of the kernels that count in u16 LDS counters -- k_count_fixed4_lds, k_count_anchor_lt, k_count_anchor_pairs (tests: many reads per histogram)
     bool no_pt = false;                   // F2Q_NO_PT=1: never the partitioned-table kernels (A/B runs, cross-checks)
     uint64_t pt_chunk_reads = (uint64_t)1 << 28;   // F2Q_PT_CHUNK: most reads per scatter/count round of the partitioned path (1.7 GB of streams per 200 M reads; 400 M reads in two rounds run 8 % faster than in six)
     uint64_t pt_min_reads = (uint64_t)1 << 21;     // F2Q_PT_MIN_READS: smaller blocks keep the packed-table kernel (three launches and the
@@ -780,7 +780,8 @@ static uint32_t choose_path(const f2q_ctx *c, const PackedBlock &pb)
 static int launch_pairs(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
 {
     const bool lds = c->prm.mode == 0 && c->lib_h.n_features <= F2Q_HIST_MAX;
-    const uint32_t grid = std::min<uint32_t>(pb.n_tiles, (uint32_t)c->n_cu * 8u);          // (four workgroups of 256 threads are resident per CU at 128 VGPRs: two rounds)
+    uint32_t grid = std::min<uint32_t>(pb.n_tiles, (uint32_t)c->n_cu * 8u);                // (four workgroups of 256 threads are resident per CU at 128 VGPRs: two rounds)
+    if (c->lt_max_wgs) grid = std::min<uint32_t>(grid, c->lt_max_wgs);
     const size_t shmem = lds ? std::max<size_t>(4, (((size_t)c->lib_h.n_features + 1) / 2) * 4) : 4;
     anchored_geom<true>(pb.planar_nw, c->plan.kb, same_q(c->run_h), [&](auto NW, auto KB, auto SQ) {
         auto kern = lds ? k_count_anchor_pairs<NW, KB, SQ, true> : k_count_anchor_pairs<NW, KB, SQ, false>;
@@ -814,7 +815,8 @@ static int launch_anchor(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t
 static int launch_anchor_lds(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &launches)
 {
     const uint32_t groups = (pb.n_tiles + F2Q_ALT_GROUPS - 1) / F2Q_ALT_GROUPS;
-    const uint32_t grid = std::min<uint32_t>(groups, (uint32_t)c->n_cu);
+    uint32_t grid = std::min<uint32_t>(groups, (uint32_t)c->n_cu);
+    if (c->lt_max_wgs) grid = std::min<uint32_t>(grid, c->lt_max_wgs);
     const bool near = c->run_h.miss > 0;
     const size_t shmem = ((near ? 2u : 1u) * (size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4;
     int rc = slab_rows(c, grid, grid, acc);
@@ -1138,6 +1140,7 @@ static int launch_hot(f2q_ctx *c, const PackedBlock &v, uint64_t slot_base, Accu
 {
     int rc = hot_arrays(c);
     if (rc) return rc;
+    c->last_path = F2Q_PATH_EXTRACT;                             // (these launches do not go through launch_view)
     if (learning) HIPC(c, hipMemsetAsync(c->hot.keys, 0xFF, (size_t)F2Q_HOT_SLOTS * 8, c->stream));   // an empty set
     const size_t shmem = (size_t)F2Q_HOT_SLOTS * 12;             // key words + counters
     if (!v.planar_nw) {

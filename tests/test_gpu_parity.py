@@ -212,6 +212,8 @@ def test_packed_anchor_kernel_vs_oracle(P, mode, anchors, ms, qs):
         counts, stats = c.read_counts()
         assert list(stats) == orc.stats()
         assert t["fast_reads"] > 0.9 * t["reads"]
+        # choose_path: the library-in-LDS kernel needs --qsu == --qsd == --ph; Extract+Count has kernels of its own
+        assert t["path"] == (9 if mode == "EC" else 7 if qs == 30 else 6)
         if mode == "C":
             assert list(counts) == orc.counts()
         else:
@@ -1138,6 +1140,7 @@ def test_packed_anchor_long_reads_gpu(P, mode, anchors, ms, rl):
         counts, stats = c.read_counts()
         # (with ':' features in the library the few reads that carry an N take the byte-exact routine as well)
         assert t["general_reads"] + t["fast_reads"] == 32300 and (t["general_reads"] == 300 if anchors != "pairs" else 300 <= t["general_reads"] < 340)
+        assert t["path"] == (8 if anchors == "pairs" else 9 if mode == "EC" else 6)       # (ten plane words: never the library-in-LDS kernel)
         assert list(stats) == orc.stats()
         if mode == "C":
             assert list(counts) == orc.counts()
@@ -1180,6 +1183,7 @@ def test_packed_anchor_mixed_case_reads_gpu(P, mode, anchors, ms):
         _, t = c.count_block(fq, want_timing=True)
         counts, stats = c.read_counts()
         assert t["fast_reads"] + t["general_reads"] == 60000 and t["general_reads"] < (900 if anchors != "pairs" else 1500)
+        assert t["path"] == (8 if anchors == "pairs" else 9 if mode == "EC" else 7)
         assert list(stats) == orc.stats()
         if mode == "C":
             assert list(counts) == orc.counts()
