@@ -22,7 +22,7 @@ EXPORTS = (
     "f2q_text_upload", "f2q_count_text", "f2q_text_free", "f2q_text_from_bgzf", "f2q_text_read",
     "f2q_set_mate2", "f2q_count_block_paired", "f2q_block_from_fastq_paired", "f2q_count_file_paired",
     "f2q_set_assign_library", "f2q_ec_assign", "f2q_ec_fetch_assigned",
-    "f2q_set_umi", "f2q_read_umis",
+    "f2q_set_umi", "f2q_read_umis", "f2q_umi_collapse",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
@@ -174,6 +174,7 @@ def load(path=None):
     L.f2q_ec_fetch_assigned.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.f2q_set_umi.argtypes = [vp, C.c_int32, C.c_int32]
     L.f2q_read_umis.argtypes = [vp, i64p, i64p]
+    L.f2q_umi_collapse.argtypes = [vp, C.c_int32, i64p, i64p]
     if path == LIB_PATH:
         _lib = L
     return L
@@ -244,7 +245,8 @@ class Counter:
     (upper-case, blanks removed, unique); row i of the count vector is feature i.
 
     ``umi=(S, L)`` counts distinct UMIs per feature (f2q_set_umi): the UMI is read positions [S, S + L); Counter mode,
-    single reads; ``read_umis()`` returns them.
+    single reads; ``read_umis()`` returns them, ``collapse_umis()`` the molecules left when UMIs of one feature at Hamming
+    distance 1 are joined.
 
     ``start2`` ("b[,b...]" or a list) makes it a paired context (f2q_set_mate2): ``start`` names the windows in mate 1,
     ``start2`` those in mate 2, ``rc2`` takes mate 2 reverse-complemented; such a context counts with the *_paired calls.
@@ -510,6 +512,15 @@ class Counter:
         self._check(self._L.f2q_read_umis(self._h, umis.ctypes.data_as(C.POINTER(C.c_int64)),
                                           extra.ctypes.data_as(C.POINTER(C.c_int64))))
         return umis[:self.n_features], int(extra[0]), int(extra[1])
+
+    def collapse_umis(self, dist=1):
+        """(molecules[n_features], pairs, edges): the UMIs of a feature that differ in one base joined, the groups counted
+        (f2q_umi_collapse); pairs = (feature, UMI) pairs held, edges = joined pairs of them.  dist=0: read_umis()'s array"""
+        molecules = np.zeros(max(self.n_features, 1), dtype=np.int64)
+        extra = np.zeros(2, dtype=np.int64)
+        self._check(self._L.f2q_umi_collapse(self._h, int(dist), molecules.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             extra.ctypes.data_as(C.POINTER(C.c_int64))))
+        return molecules[:self.n_features], int(extra[0]), int(extra[1])
 
     def counts_device_ptr(self):
         p, n = C.c_void_p(), C.c_uint64()

@@ -831,6 +831,15 @@ F2Q_HD unsigned long long ec_cas(unsigned long long *p, unsigned long long cmp, 
     unsigned long long old = *p; if (old == cmp) *p = val; return old;
 #endif
 }
+F2Q_HD uint32_t ec_cas32(uint32_t *p, uint32_t cmp, uint32_t val)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_compare_exchange_strong(gpw(p), &cmp, val, __ATOMIC_RELAXED, __ATOMIC_RELAXED, F2Q_EC_SCOPE);
+    return cmp;
+#else
+    uint32_t old = *p; if (old == cmp) *p = val; return old;
+#endif
+}
 F2Q_HD void ec_add(unsigned long long *p, unsigned long long v)           // result unused: the compiler emits the no-return form
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1026,7 +1035,8 @@ F2Q_HD void ec_count_key(const EcDev &ec, const KV &kv, unsigned long long read_
 // The UMI of a read is upper(seq[S:S+L]), 1 <= L <= 16: valid only when the read holds all L bases, each is A/C/G/T and
 // the quality slice [S:S+L] is all there and passes --ph by the rule of a feature window (thr < 33: no test).  A read
 // that match_key assigns to feature f (exactly or within --m) and whose UMI u is valid brings the pair (f, u); the set
-// below holds every pair once, umis[f] counts the pairs of f.  UMIs are compared by identity (no error collapsing).
+// below holds every pair once, umis[f] counts the pairs of f.  The set compares UMIs by identity; f2q_umi_collapse joins
+// those of one feature at Hamming distance 1 afterwards (umi_find / uf_union below).
 #define F2Q_UMI_MAXLEN 16
 #define F2Q_UMI_READS 0              // words of UmiDev.ctr: assigned reads with a valid UMI ...
 #define F2Q_UMI_FAILED 1             // ... with an invalid one
@@ -1063,6 +1073,69 @@ F2Q_HD uint32_t umi_insert(const UmiDev &u, uint32_t f, uint32_t codes)
     acc_add(&u.umis[f], 1ull);
     return 1u;
 }
+// ---- UMIs at Hamming distance 1 collapsed per feature (f2q_umi_collapse) ----
+// Two pairs of ONE feature are joined when their UMIs differ in exactly one of the L bases (a substitution); the
+// molecules of a feature are the connected components of that graph.  The pass runs over the set after counting: the
+// slots are written by earlier launches only (plain loads), the forest parent[slots] is shared inside the launch.
+//
+// the slot that holds word k, else ~0u: umi_claim's hash and probe sequence, read-only
+F2Q_HD uint32_t umi_find(const UmiDev &u, unsigned long long k)
+{
+    uint32_t s = hash32(k ^ (k >> 29), 32) & u.mask;
+    for (uint32_t guard = 0; guard <= u.mask; guard++) {
+        const unsigned long long v = gp(u.slots)[s];
+        if (v == k) return s;
+        if (v == KEY_EMPTY) return ~0u;
+        s = (s + 1) & u.mask;
+    }
+    return ~0u;
+}
+// Lock-free union-find over slot indices.  Invariant: parent[x] <= x, and only a root (parent[x] == x) is ever linked,
+// by one CAS, below a smaller root; so a node that has stopped being a root never is one again and every walk ends.
+// Every access is an agent-scope atomic (F2Q_LD32 / F2Q_ST32 / ec_cas32): a CU's L1 is never refreshed by another
+// CU's stores inside a launch, a plain load could walk a stale forest.  Nothing waits for another lane.
+// the root of x; path halving stores into parent[x] a value just read from an ancestor of x (x is no root there, so
+// the store cannot race a link; whichever of two such stores lands, parent[x] stays an ancestor below x)
+F2Q_HD uint32_t uf_find(uint32_t *parent, uint32_t x)
+{
+    uint32_t p = F2Q_LD32(&parent[x]);
+    while (p != x) {
+        const uint32_t g = F2Q_LD32(&parent[p]);
+        if (g != p) F2Q_ST32(&parent[x], g);
+        x = p; p = g;
+    }
+    return x;
+}
+// joins the trees of a and b: the larger root goes below the smaller one.  A lost CAS means another union has linked
+// that root meanwhile (progress elsewhere): find again from the two roots
+F2Q_HD void uf_union(uint32_t *parent, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = uf_find(parent, a); b = uf_find(parent, b);
+        if (a == b) return;
+        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        if (ec_cas32(&parent[hi], hi, lo) == hi) return;
+    }
+}
+// neighbour n (0 .. 3L-1) of the pair k in slot i: base n / 3 substituted by XOR with 1 + n % 3 -- the field stays inside
+// the low 32 bits for every L <= 16, the feature half is never touched.  Only the larger word of an edge is looked up,
+// so every edge is found once; a hit joins the two slots.  Returns the edges found (0 / 1)
+F2Q_HD uint32_t umi_link_one(const UmiDev &u, uint32_t *parent, uint32_t i, unsigned long long k, uint32_t n)
+{
+    const unsigned long long kn = k ^ ((unsigned long long)(1u + n % 3u) << (2u * (n / 3u)));
+    if (kn < k) return 0u;
+    const uint32_t s = umi_find(u, kn);
+    if (s == ~0u) return 0u;
+    uf_union(parent, i, s);
+    return 1u;
+}
+// after linking has ended: the root of an occupied slot stands for one molecule of the feature in its word
+F2Q_HD void umi_root_one(const UmiDev &u, uint32_t *parent, unsigned long long *molecules, uint32_t i)
+{
+    const unsigned long long k = gp(u.slots)[i];
+    if (k != KEY_EMPTY && F2Q_LD32(&parent[i]) == i) acc_add(&molecules[(uint32_t)(k >> 32)], 1ull);
+}
+
 // the UMI of a read as 2-bit codes; false: invalid
 template <class P>
 F2Q_HD bool umi_codes(const UmiDev &u, int thr, P seq, int r, P qual, int qn, uint32_t &codes)

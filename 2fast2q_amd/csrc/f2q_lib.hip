@@ -1039,6 +1039,72 @@ static int umi_reserve(f2q_ctx *c, uint64_t n)
     return F2Q_OK;
 }
 
+// UMIs of one feature at Hamming distance 1 joined, the groups counted (include/f2q.h).  A pass over the set after
+// counting: parent[slots], molecules[n_features] and the edge counter are scratch from the device-memory cache and go
+// back to it; the set, umis[] and the counters are only read, so the call changes nothing another call reads.
+extern "C" int f2q_umi_collapse(f2q_ctx *c, int32_t dist, int64_t *molecules, int64_t extra[2])
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->umi_on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (dist != 0 && dist != 1) return fail(c, F2Q_EINVAL, "UMIs are collapsed at Hamming distance 1 (or 0: as they are)");
+    HIPC(c, hipSetDevice(c->device));
+    const double t0 = now_ms();
+    const uint64_t nf = c->lib_h.n_features;
+    std::vector<unsigned long long> h(nf + 1 + F2Q_UMI_CTR_WORDS, 0ull);      // molecules, edges, the set's counters
+    float ms[3] = {0, 0, 0};
+    // the linking launch (defaults and alternatives: DESIGN.md): threads per workgroup (whole waves, at most F2Q_UMI_LINK_THREADS),
+    // workgroups per CU at most, and the lane-per-slot layout instead of the wave-cooperative one (A/B runs)
+    uint32_t wg = F2Q_UMI_LINK_WG_DEFAULT, per_cu = F2Q_UMI_LINK_GRID_DEFAULT, glink = 0; bool by_lane = false;
+    { const char *e = getenv("F2Q_UMI_LINK_WG"); if (e && atol(e) >= 64 && atol(e) <= F2Q_UMI_LINK_THREADS && atol(e) % 64 == 0) wg = (uint32_t)atol(e); }
+    { const char *e = getenv("F2Q_UMI_LINK_GRID"); if (e && atol(e) >= 1 && atol(e) <= 4096) per_cu = (uint32_t)atol(e); }
+    { const char *e = getenv("F2Q_UMI_LINK"); by_lane = e && !strcmp(e, "lane"); }
+    DevScope scratch(c);
+    if (c->umi.umis && c->umi.slots) {                           // (nothing counted yet: all zero)
+        if (dist == 0) {
+            if (nf) HIPC(c, hipMemcpyAsync(h.data(), c->umi.umis, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        } else {
+            if (c->umi_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
+            uint32_t *parent = nullptr; unsigned long long *mol = nullptr;
+            if (dev_alloc(c, (size_t)c->umi_slots, &parent, scratch.v) || dev_alloc(c, (size_t)nf + 1, &mol, scratch.v, 0))
+                return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi_slots) + " slots: " + c->err);
+            struct Events { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } evs;
+            hipEvent_t *ev = evs.e;                              // F2Q_TRACE=1: the time of each launch
+            if (c->trace) for (int i = 0; i < 4; i++) HIPC(c, hipEventCreate(&ev[i]));
+            const uint32_t g256 = (uint32_t)std::min<uint64_t>((c->umi_slots + 255) / 256, (uint64_t)c->n_cu * 8u);
+            glink = (uint32_t)std::min<uint64_t>((c->umi_slots + wg - 1) / wg, (uint64_t)c->n_cu * per_cu);
+            if (ev[0]) HIPC(c, hipEventRecord(ev[0], c->stream));
+            hipLaunchKernelGGL(k_umi_uf_init, dim3(g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi_slots);
+            HIPC(c, hipGetLastError());
+            EC_POINT(c, "k_umi_uf_init");
+            if (ev[1]) HIPC(c, hipEventRecord(ev[1], c->stream));
+            if (by_lane) hipLaunchKernelGGL(k_umi_link_lane, dim3(glink), dim3(wg), 0, c->stream, c->umi, parent, mol + nf);
+            else hipLaunchKernelGGL(k_umi_link, dim3(glink), dim3(wg), 0, c->stream, c->umi, parent, mol + nf);
+            HIPC(c, hipGetLastError());
+            EC_POINT(c, "k_umi_link");
+            if (ev[2]) HIPC(c, hipEventRecord(ev[2], c->stream));
+            hipLaunchKernelGGL(k_umi_roots, dim3(g256), dim3(256), 0, c->stream, c->umi, parent, mol);
+            HIPC(c, hipGetLastError());
+            EC_POINT(c, "k_umi_roots");
+            if (ev[3]) HIPC(c, hipEventRecord(ev[3], c->stream));
+            HIPC(c, hipMemcpyAsync(h.data(), mol, (nf + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            if (ev[3]) {
+                HIPC(c, hipEventSynchronize(ev[3]));
+                for (int i = 0; i < 3; i++) HIPC(c, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+            }
+        }
+        HIPC(c, hipMemcpyAsync(h.data() + nf + 1, c->umi.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    const unsigned long long *ctr = h.data() + nf + 1;
+    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+    unsigned long long total = 0;
+    for (uint64_t i = 0; i < nf; i++) { total += h[i]; if (molecules) molecules[i] = (int64_t)h[i]; }
+    if (extra) { extra[0] = (int64_t)ctr[F2Q_UMI_HELD]; extra[1] = (int64_t)h[nf]; }
+    if (c->trace) fprintf(stderr, "[f2q trace] UMI collapse: %llu pairs, %llu edges, %llu molecules, %.3f ms (union-find init %.3f, link %.3f, roots %.3f; %s, %u x %u)\n",
+                          ctr[F2Q_UMI_HELD], h[nf], total, now_ms() - t0, ms[0], ms[1], ms[2], by_lane ? "lane" : "wave", glink, wg);
+    return F2Q_OK;
+}
+
 // one set of launches over a view of a block (all of it in Counter mode, a step of it in Extract+Count mode)
 static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, Accum &acc, uint32_t &launches)
 {

@@ -1,7 +1,10 @@
 // f2q_umi_kernels.h -- distinct UMIs per feature (--umi, f2q_set_umi; included by f2q_lib.hip only).
 //   k_count_umi    Counter mode on raw records, the byte-exact routine, plus the (feature, UMI) set: one pass
 //   k_umi_rehash   the pairs of a full set into a larger one
-// The per-lane logic (UmiDev, umi_insert, umi_codes, UmiHook) lives in f2q_device.h.
+//   k_umi_uf_init / k_umi_link / k_umi_link_lane / k_umi_roots   UMIs at Hamming distance 1 collapsed per feature
+//                  (f2q_umi_collapse): three launches over the set, the kernel boundary is the only hand-off
+// The per-lane logic (UmiDev, umi_insert, umi_codes, UmiHook, umi_find, uf_find / uf_union, umi_link_one, umi_root_one)
+// lives in f2q_device.h.
 #pragma once
 
 // k_count_general's shape (64-thread workgroups, the record's two lines staged in LDS, a record longer than the staging
@@ -54,4 +57,72 @@ __global__ __launch_bounds__(256) void k_umi_rehash(UmiDev old, UmiDev nw)
     if (i > old.mask) return;
     const unsigned long long k = gp(old.slots)[i];
     if (k != KEY_EMPTY) (void)umi_claim(nw, k);
+}
+
+// ---- f2q_umi_collapse: a union-find over the slots of the set --------------------------------------------------------
+// every slot its own root
+__global__ __launch_bounds__(256) void k_umi_uf_init(uint32_t *parent, unsigned long long n)
+{
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x)
+        gpw(parent)[i] = (uint32_t)i;
+}
+
+// The set is at most half full and one pair has 3L look-ups, each a dependent probe chain of its own: a lane that
+// walked its own slot's 3L neighbours would run them one after the other while the lanes of the empty slots idle.
+// So a wave takes 64 consecutive slots, compacts the occupied ones into its row of LDS, and then takes them 64 / 3L
+// at a time: lane g * 3L + n probes neighbour n of the g-th pair of the round, all look-ups of the round in flight
+// together.  Edges are summed per wave: one atomic per wave.  Any grid: waves stride over the set.
+#define F2Q_UMI_LINK_THREADS 256
+#define F2Q_UMI_LINK_WG_DEFAULT 256
+#define F2Q_UMI_LINK_GRID_DEFAULT 8
+__global__ __launch_bounds__(F2Q_UMI_LINK_THREADS) void k_umi_link(UmiDev u, uint32_t *parent, unsigned long long *edges)
+{
+    __shared__ unsigned long long keys[F2Q_UMI_LINK_THREADS / 64][64];
+    __shared__ uint8_t from[F2Q_UMI_LINK_THREADS / 64][64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const uint32_t per = 3u * (uint32_t)u.length, groups = 64u / per;
+    const uint32_t g = lane / per, n = lane - g * per;
+    const unsigned long long slots = (unsigned long long)u.mask + 1ull;
+    unsigned long long found = 0;
+    for (unsigned long long base = ((unsigned long long)blockIdx.x * waves + wave) * 64ull; base < slots; base += (unsigned long long)gridDim.x * waves * 64ull) {
+        const unsigned long long k = base + lane < slots ? gp(u.slots)[base + lane] : KEY_EMPTY;
+        const unsigned long long occ = __ballot(k != KEY_EMPTY);
+        if (occ == 0ull) continue;
+        if (k != KEY_EMPTY) {
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(occ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)occ, 0u));
+            keys[wave][rank] = k; from[wave][rank] = (uint8_t)lane;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const uint32_t cnt = (uint32_t)__popcll(occ);
+        for (uint32_t t = 0; t < cnt; t += groups) {
+            const uint32_t q = t + g;
+            if (g < groups && q < cnt) found += umi_link_one(u, parent, (uint32_t)base + from[wave][q], keys[wave][q], n);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+    found = wave_sum(found);
+    if (lane == 0 && found) acc_add(edges, found);
+}
+
+// the plain layout, kept for the comparison (F2Q_UMI_LINK=lane): a lane per slot, its 3L look-ups one after the other
+__global__ __launch_bounds__(F2Q_UMI_LINK_THREADS) void k_umi_link_lane(UmiDev u, uint32_t *parent, unsigned long long *edges)
+{
+    const uint32_t per = 3u * (uint32_t)u.length;
+    const unsigned long long slots = (unsigned long long)u.mask + 1ull;
+    unsigned long long found = 0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long k = gp(u.slots)[i];
+        if (k == KEY_EMPTY) continue;
+        for (uint32_t n = 0; n < per; n++) found += umi_link_one(u, parent, (uint32_t)i, k, n);
+    }
+    found = wave_sum(found);
+    if ((threadIdx.x & 63u) == 0 && found) acc_add(edges, found);
+}
+
+// after k_umi_link has ended (parent[] is stable): every root adds 1 to the molecules of its feature
+__global__ __launch_bounds__(256) void k_umi_roots(UmiDev u, uint32_t *parent, unsigned long long *molecules)
+{
+    const unsigned long long slots = (unsigned long long)u.mask + 1ull;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (unsigned long long)gridDim.x * blockDim.x)
+        umi_root_one(u, parent, molecules, (uint32_t)i);
 }

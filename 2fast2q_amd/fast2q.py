@@ -111,7 +111,7 @@ def _counter_kwargs(param):
                   qual_up=param['qual_up'], qual_down=param['qual_down'],
                   device=int(param.get('device', os.environ.get("F2Q_DEVICE", os.environ.get("LOCAL_RANK", 0)))))
     if param.get('umi'):                            # a UMI context (f2q_set_umi); part of the key contexts are kept under
-        kwargs['umi'] = tuple(param['umi'])
+        kwargs['umi'] = tuple(param['umi'])         # (--mu is not: collapsing changes no context)
     return kwargs
 
 
@@ -257,6 +257,9 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         if param.get('umi'):                        # distinct UMIs per feature and the two sample-level counters (f2q_read_umis)
             umis, umi_reads, umi_failed = ctx.read_umis()
             param.setdefault('umi_counted', {})[raw] = ([int(n) for n in umis], umi_reads, umi_failed)
+            if param.get('umi_mismatch'):           # --mu 1: UMIs of a feature one base apart joined (f2q_umi_collapse)
+                molecules, pairs, edges = ctx.collapse_umis(param['umi_mismatch'])
+                param.setdefault('umi_collapsed', {})[raw] = ([int(n) for n in molecules], pairs, edges)
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -339,11 +342,17 @@ def aligner(i, raw, features, param, reads_stats):
         names = [f.name for f in features.values()]
         param.setdefault("umi_samples", {})[sample.name] = SampleResult(sample.name, value, unit, _sample_rows(zip(names, umis)),
                                                                         dict(local, umi_reads=umi_reads, umi_failed=umi_failed))
+        molecules = None
+        if raw in param.get('umi_collapsed', {}):    # --mu 1: the same rows again, holding molecules
+            molecules, pairs, edges = param['umi_collapsed'].pop(raw)
+            param.setdefault("umi_collapsed_samples", {})[sample.name] = SampleResult(
+                sample.name, value, unit, _sample_rows(zip(names, molecules)), dict(local, umi_pairs=pairs, umi_edges=edges, umi_molecules=sum(molecules)))
         if not param.get("delete", True) and sharding.world().rank == 0:
             os.makedirs(param["directory"], exist_ok=True)
-            both = _sample_rows((f.name, (f.counts, n)) for f, n in zip(features.values(), umis))      # (the order of `rows`)
+            per = zip(umis, molecules) if molecules is not None else ((n,) for n in umis)
+            both = _sample_rows((f.name, (f.counts,) + tuple(ns)) for f, ns in zip(features.values(), per))      # (the order of `rows`)
             csv_writer(os.path.join(param["directory"], sample.name + "_umi_reads.csv"),
-                       [["#Feature", "Reads", "UMIs"]] + [[name, reads, n] for name, (reads, n) in both])
+                       [["#Feature", "Reads", "UMIs"] + (["Molecules"] if molecules is not None else [])] + [[name, *ns] for name, ns in both])
     if not param['Progress bar']:
         colourful_errors("INFO", f"Sample {sample.name} was processed in {value} {unit}")
     param.setdefault("samples", {})[sample.name] = sample     # a later file of the same name replaces the earlier one,
@@ -408,6 +417,8 @@ def initializer(cmd):
         print(f" Paired-end: mate 2 start position: {param['start2']}" + (" (mate 2 reverse-complemented)" if param['rc2'] else ""))
     if param.get('umi'):
         print(f" Distinct UMIs are counted per feature: UMI start position in the read: {param['umi'][0]}, length: {param['umi'][1]}bp")
+    if param.get('umi_mismatch'):
+        print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
     print(f" All data will be saved into {param['directory']}")
     print("\n ---- ")
     param["cpu"] = param["cpu"] if isinstance(param["cpu"], int) and param["cpu"] > 0 else (os.cpu_count() or 1)
@@ -481,6 +492,7 @@ def input_parser(argv=None):
     ap.add_argument("--st2", help="With --pe: the start position(s) of the feature part(s) within mate 2")
     ap.add_argument("--rc2", nargs='?', const=True, help="With --pe: mate 2 is reverse-complemented before its parts are taken")
     ap.add_argument("--umi", help="S,L: every read carries a UMI of L bases (1-16) at position S; Counter mode also reports the distinct UMIs per feature (<name>_umi.csv)")
+    ap.add_argument("--mu", help="With --umi: mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
     if args.v is not None:
@@ -541,6 +553,15 @@ def input_parser(argv=None):
         if p['umi'] is None:
             colourful_errors("FATAL", f"--umi {args.umi}: expected S,L with a start S >= 0 and a length 1 <= L <= 16.")
             sys.exit(2)
+    if args.mu is not None:
+        if args.umi is None:
+            colourful_errors("FATAL", "--mu only has a meaning with --umi: the mismatches allowed between two UMIs of one feature.")
+            sys.exit(2)
+        if args.mu not in ("0", "1"):
+            colourful_errors("FATAL", f"--mu {args.mu}: expected 0 or 1 (UMIs are collapsed at Hamming distance 1 at most).")
+            sys.exit(2)
+        if args.mu == "1":
+            p['umi_mismatch'] = 1
     if args.assign is not None:
         if p['Running Mode'] != "EC":
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
@@ -666,6 +687,8 @@ def run_headers(param):
                   f"#Mate 2 reverse-complemented: {'yes' if param['rc2'] else 'no'}"]
     if param.get('umi'):
         lines.append(f"#UMI start position in the read, length: {param['umi'][0]},{param['umi'][1]}")
+    if param.get('umi_mismatch'):
+        lines.append(f"#UMI mismatches collapsed: {param['umi_mismatch']}")
     return lines
 
 
@@ -703,6 +726,10 @@ def compiling(param):
         _, uhead, utable = compile_table(param["umi_samples"])
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_umi.csv"),
                    [uhead] + [[feature] + counts for feature, counts in utable.items()])
+    if param.get("umi_collapsed_samples"):           # --mu 1: the same table again, holding molecules
+        _, chead, ctable = compile_table(param["umi_collapsed_samples"])
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_umi_collapsed.csv"),
+                   [chead] + [[feature] + counts for feature, counts in ctable.items()])
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -720,6 +747,8 @@ STATS_HEAD = ["#Sample name", "Running Time", "Running Time unit", "Total number
 
 
 UMI_STATS_HEAD = ["#Sample name (UMI)", "Number of aligned reads with a valid UMI", "Number of aligned reads with an invalid UMI"]
+UMI_COLLAPSE_STATS_HEAD = ["#Sample name (UMI collapsed)", "Number of distinct (feature, UMI) pairs", "Number of pairs of them that differ in one base",
+                           "Number of molecules"]
 
 
 def run_stats(headers, param, compiled, head, ordered):
@@ -732,6 +761,9 @@ def run_stats(headers, param, compiled, head, ordered):
     if param.get("umi_samples"):                     # --umi: the two sample-level counters, one line per sample
         global_stat += [UMI_STATS_HEAD] + [[s.name, u.stats["umi_reads"], u.stats["umi_failed"]]
                                            for s in ordered for u in [param["umi_samples"].get(s.name)] if u is not None]
+    if param.get("umi_collapsed_samples"):           # --mu 1: pairs, edges and molecules, one line per sample
+        global_stat += [UMI_COLLAPSE_STATS_HEAD] + [[s.name, u.stats["umi_pairs"], u.stats["umi_edges"], u.stats["umi_molecules"]]
+                                                    for s in ordered for u in [param["umi_collapsed_samples"].get(s.name)] if u is not None]
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib

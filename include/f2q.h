@@ -309,7 +309,7 @@ int f2q_ec_fetch_assigned(f2q_ctx *ctx, int32_t *feature, int32_t *dist);
  * The UMI of a read is upper(seq[start:start+length]); it is valid when the read holds all `length` bases, each of them
  * is A/C/G/T, and the quality slice of the same positions is complete and passes --ph by the rule of a feature window
  * (fast2q.py:355-360).  A read assigned to feature f, exactly or within --m, with a valid UMI u brings the pair (f, u);
- * UMIs are compared by identity (no error collapsing).  The set of pairs lives across the pieces of a file and across
+ * the set compares UMIs by identity (f2q_umi_collapse joins near ones afterwards).  The set of pairs lives across the pieces of a file and across
  * counting calls until f2q_reset_counts; it grows through the context's device-memory cache (F2Q_ENOMEM: a larger set
  * could not be allocated, the old one is intact).
  *
@@ -318,6 +318,23 @@ int f2q_ec_fetch_assigned(f2q_ctx *ctx, int32_t *feature, int32_t *dist);
  * F2Q_PERFECT + F2Q_IMPERFECT.  Either pointer may be NULL.  F2Q_ESTATE without f2q_set_umi. */
 int f2q_set_umi(f2q_ctx *ctx, int32_t start, int32_t length);
 int f2q_read_umis(f2q_ctx *ctx, int64_t *umis, int64_t extra[2]);
+
+/* ---- UMIs at Hamming distance 1 collapsed per feature -----------------------------------------
+ * One substitution inside a UMI turns one molecule into two, so the distinct UMIs of a feature are an upper bound that
+ * grows with depth.  f2q_umi_collapse joins them by the "cluster" rule of UMI-tools: for one feature f take the distinct
+ * valid UMIs the set holds for f (those f2q_read_umis counts); two of them are joined when they differ in exactly one of
+ * their `length` bases (a substitution: same length, no indels); molecules[f] is the number of connected components of
+ * that graph.  UMIs of different features are never joined.  extra[0] = pairs the set holds (the nodes), extra[1] =
+ * joined unordered pairs, each once, over all features (the edges); with no edges molecules[f] == umis[f].  The result
+ * depends on the set alone -- not on read order, the set's size or its growth -- so it is exact and reproducible.
+ * Count-aware rules ("directional", "adjacency") need reads per pair, which the set does not hold.
+ *
+ * dist 1 collapses; dist 0 returns umis[] and 0 edges; anything else is F2Q_EINVAL.  F2Q_ESTATE without f2q_set_umi;
+ * F2Q_ENOMEM when the scratch (4 bytes per slot of the set, 8 per feature) cannot be had: the set is intact.  Nothing
+ * counted yet: all zero.  The call synchronises the stream, as f2q_read_umis; either pointer may be NULL.  It may come
+ * any number of times, also between counting calls, and changes no state that another call reads.
+ * F2Q_TRACE=1 prints one line per call: "[f2q trace] UMI collapse: P pairs, E edges, M molecules, T ms (...)". */
+int f2q_umi_collapse(f2q_ctx *ctx, int32_t dist, int64_t *molecules, int64_t extra[2]);
 
 #ifdef __cplusplus
 }
