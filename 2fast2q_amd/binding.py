@@ -23,6 +23,7 @@ EXPORTS = (
     "f2q_set_mate2", "f2q_count_block_paired", "f2q_block_from_fastq_paired", "f2q_count_file_paired",
     "f2q_set_assign_library", "f2q_ec_assign", "f2q_ec_fetch_assigned",
     "f2q_set_umi", "f2q_read_umis", "f2q_umi_collapse",
+    "f2q_set_umi_reads", "f2q_umi_collapse_directional", "f2q_umi_pairs",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
@@ -175,6 +176,10 @@ def load(path=None):
     L.f2q_set_umi.argtypes = [vp, C.c_int32, C.c_int32]
     L.f2q_read_umis.argtypes = [vp, i64p, i64p]
     L.f2q_umi_collapse.argtypes = [vp, C.c_int32, i64p, i64p]
+    L.f2q_set_umi_reads.argtypes = [vp, C.c_int32]
+    L.f2q_umi_collapse_directional.argtypes = [vp, i64p, i64p]
+    u32p = C.POINTER(C.c_uint32)
+    L.f2q_umi_pairs.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), u32p, u32p, u32p]
     if path == LIB_PATH:
         _lib = L
     return L
@@ -246,13 +251,14 @@ class Counter:
 
     ``umi=(S, L)`` counts distinct UMIs per feature (f2q_set_umi): the UMI is read positions [S, S + L); Counter mode,
     single reads; ``read_umis()`` returns them, ``collapse_umis()`` the molecules left when UMIs of one feature at Hamming
-    distance 1 are joined.
+    distance 1 are joined.  ``umi_reads=True`` also keeps the reads of every (feature, UMI) pair (f2q_set_umi_reads):
+    ``collapse_umis(rule="directional")`` and ``umi_pairs()`` need them.
 
     ``start2`` ("b[,b...]" or a list) makes it a paired context (f2q_set_mate2): ``start`` names the windows in mate 1,
     ``start2`` those in mate 2, ``rc2`` takes mate 2 reverse-complemented; such a context counts with the *_paired calls.
     """
 
-    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, **params):
+    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -265,11 +271,14 @@ class Counter:
         self.n_assign = 0
         self.paired = False
         self.umi = None
+        self.umi_reads = False
         try:
             if start2 is not None:
                 self.set_mate2(start2, rc2)
             if umi is not None:
                 self.set_umi(*umi)
+            if umi_reads:
+                self.set_umi_reads(True)
         except BaseException:
             self.close()
             raise
@@ -329,6 +338,11 @@ class Counter:
         """the UMI window of every read (f2q_set_umi); before counting"""
         self._check(self._L.f2q_set_umi(self._h, int(start), int(length)))
         self.umi = (int(start), int(length))
+
+    def set_umi_reads(self, on=True):
+        """keep the reads of every (feature, UMI) pair (f2q_set_umi_reads); after set_umi, before counting"""
+        self._check(self._L.f2q_set_umi_reads(self._h, 1 if on else 0))
+        self.umi_reads = bool(on)
 
     # -- counting: paired-end --
     @staticmethod
@@ -513,14 +527,40 @@ class Counter:
                                           extra.ctypes.data_as(C.POINTER(C.c_int64))))
         return umis[:self.n_features], int(extra[0]), int(extra[1])
 
-    def collapse_umis(self, dist=1):
+    def collapse_umis(self, dist=1, rule="cluster"):
         """(molecules[n_features], pairs, edges): the UMIs of a feature that differ in one base joined, the groups counted
-        (f2q_umi_collapse); pairs = (feature, UMI) pairs held, edges = joined pairs of them.  dist=0: read_umis()'s array"""
+        (f2q_umi_collapse); pairs = (feature, UMI) pairs held, edges = joined pairs of them.  dist=0: read_umis()'s array.
+        rule="directional" (dist 1 only; needs umi_reads=True): a UMI absorbs a neighbour only when it has at least
+        2 * reads - 1 of the neighbour's reads (f2q_umi_collapse_directional); edges = pairs of UMIs one base apart"""
+        if rule == "directional":
+            if int(dist) != 1:
+                raise ValueError("the directional rule collapses at distance 1")
+            return self.collapse_umis_directional()[:3]
+        if rule != "cluster":
+            raise ValueError("rule is 'cluster' or 'directional'")
         molecules = np.zeros(max(self.n_features, 1), dtype=np.int64)
         extra = np.zeros(2, dtype=np.int64)
         self._check(self._L.f2q_umi_collapse(self._h, int(dist), molecules.ctypes.data_as(C.POINTER(C.c_int64)),
                                              extra.ctypes.data_as(C.POINTER(C.c_int64))))
         return molecules[:self.n_features], int(extra[0]), int(extra[1])
+
+    def collapse_umis_directional(self):
+        """(molecules[n_features], pairs, edges, dominated, reads): f2q_umi_collapse_directional with all of its extra[4]"""
+        molecules = np.zeros(max(self.n_features, 1), dtype=np.int64)
+        extra = np.zeros(4, dtype=np.int64)
+        self._check(self._L.f2q_umi_collapse_directional(self._h, molecules.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                         extra.ctypes.data_as(C.POINTER(C.c_int64))))
+        return (molecules[:self.n_features],) + tuple(int(x) for x in extra)
+
+    def umi_pairs(self):
+        """(feature[n], codes[n], reads[n]) of every (feature, UMI) pair held, sorted by (feature, codes); codes: base j of
+        the UMI in bits 2j .. 2j+1, A C G T = 0 .. 3 (f2q_umi_pairs; needs umi_reads=True)"""
+        n = C.c_uint64()
+        self._check(self._L.f2q_umi_pairs(self._h, 0, C.byref(n), None, None, None))
+        arrs = [np.zeros(max(n.value, 1), dtype=np.uint32) for _ in range(3)]
+        got = C.c_uint64()
+        self._check(self._L.f2q_umi_pairs(self._h, n.value, C.byref(got), *[a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in arrs]))
+        return tuple(a[:got.value] for a in arrs)
 
     def counts_device_ptr(self):
         p, n = C.c_void_p(), C.c_uint64()

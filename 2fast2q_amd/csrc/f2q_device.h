@@ -1049,6 +1049,7 @@ struct UmiDev {
     int32_t start, length;           // the window [start, start + length) of the read
     unsigned long long *umis;        // [n_features] distinct UMIs seen per feature
     unsigned long long *ctr;         // [F2Q_UMI_CTR_WORDS]
+    uint32_t *reads;                 // [slots] reads per pair, parallel to slots[] (f2q_set_umi_reads); null: not kept
 };
 // claims a slot for word k with one CAS: 1 = new, 0 = already there, 2 = no room (probe bound, as ec64_insert_word)
 F2Q_HD uint32_t umi_claim(const UmiDev &u, unsigned long long k)
@@ -1066,12 +1067,57 @@ F2Q_HD uint32_t umi_claim(const UmiDev &u, unsigned long long k)
     F2Q_ST64(&u.ctr[F2Q_UMI_OVERFLOW], 1ull);
     return 2u;
 }
+// umi_claim that also says where: `slot` is the slot that holds k (new or not); untouched on 2
+F2Q_HD uint32_t umi_claim_at(const UmiDev &u, unsigned long long k, uint32_t &slot)
+{
+    uint32_t s = hash32(k ^ (k >> 29), 32) & u.mask;
+    for (uint32_t guard = 0; guard <= u.mask; guard++) {
+        unsigned long long v = F2Q_LD64(&u.slots[s]);
+        if (v == KEY_EMPTY) {
+            v = ec_cas(&u.slots[s], KEY_EMPTY, k);
+            if (v == KEY_EMPTY) { slot = s; return 1u; }
+        }
+        if (v == k) { slot = s; return 0u; }
+        s = (s + 1) & u.mask;
+    }
+    F2Q_ST64(&u.ctr[F2Q_UMI_OVERFLOW], 1ull);
+    return 2u;
+}
+// one read more for the pair in `slot`: relaxed, agent scope, the old value is not asked for (a no-return atomic).  The
+// claimant of a slot and a lane that found the pair there may add in either order: reads[] starts at zero, sums commute
+F2Q_HD void umi_read_add(const UmiDev &u, uint32_t slot)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)__hip_atomic_fetch_add(gpw(u.reads) + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    u.reads[slot] += 1u;
+#endif
+}
 // the pair (f, codes): 1 when it is new -- the claim adds 1 to umis[f] -- else 0
 F2Q_HD uint32_t umi_insert(const UmiDev &u, uint32_t f, uint32_t codes)
 {
     if (umi_claim(u, ((unsigned long long)f << 32) | codes) != 1u) return 0u;
     acc_add(&u.umis[f], 1ull);
     return 1u;
+}
+// umi_insert with reads kept (u.reads set): the read also adds 1 to reads[slot of its pair], new or not
+F2Q_HD uint32_t umi_insert_reads(const UmiDev &u, uint32_t f, uint32_t codes)
+{
+    uint32_t slot = 0;
+    const uint32_t rc = umi_claim_at(u, ((unsigned long long)f << 32) | codes, slot);
+    if (rc == 2u) return 0u;
+    umi_read_add(u, slot);
+    if (rc == 1u) acc_add(&u.umis[f], 1ull);
+    return rc;
+}
+// k_umi_rehash with reads kept: the word of slot i of `old` into `nw`, its count into the slot it got there.  A plain
+// store: every word is in `old` once, so its slot of `nw` has this one writer
+F2Q_HD void umi_rehash_reads_one(const UmiDev &old, const UmiDev &nw, uint32_t i)
+{
+    const unsigned long long k = gp(old.slots)[i];
+    if (k == KEY_EMPTY) return;
+    uint32_t slot = 0;
+    if (umi_claim_at(nw, k, slot) != 2u) gpw(nw.reads)[slot] = gp(old.reads)[i];
 }
 // ---- UMIs at Hamming distance 1 collapsed per feature (f2q_umi_collapse) ----
 // Two pairs of ONE feature are joined when their UMIs differ in exactly one of the L bases (a substitution); the
@@ -1136,6 +1182,59 @@ F2Q_HD void umi_root_one(const UmiDev &u, uint32_t *parent, unsigned long long *
     if (k != KEY_EMPTY && F2Q_LD32(&parent[i]) == i) acc_add(&molecules[(uint32_t)(k >> 32)], 1ull);
 }
 
+// ---- the directional rule (f2q_umi_collapse_directional; needs reads[]) ----
+// UMI-tools' default: a absorbs its neighbour b only when c(a) >= 2 c(b) - 1 (c = reads of the pair).  Counts never rise
+// along such an edge and stay equal only at 1 / 1, so the strongly connected components of the directed graph are every
+// node with c >= 2 alone and the connected components of the Hamming-1 graph among the nodes with c == 1; the molecules
+// are the components no edge enters from outside.  dom[slot] bit 0: an edge from a node with c >= 2 enters
+// this slot (k_umi_link_dir); bit 1, roots of the c == 1 forest only: it enters a member of the tree (k_umi_dir_spread).
+//
+// neighbour n of the pair k (c reads) in slot i, as umi_link_one finds it: only the larger word of an edge is looked up,
+// so every edge is visited once, and both directions are decided at that visit.  c + 1 >= 2 c' in 64 bits: no count of
+// 32 bits overflows it
+F2Q_HD uint32_t umi_link_dir_one(const UmiDev &u, uint32_t *parent, uint32_t *dom, uint32_t i, unsigned long long k, uint32_t c, uint32_t n)
+{
+    const unsigned long long kn = k ^ ((unsigned long long)(1u + n % 3u) << (2u * (n / 3u)));
+    if (kn < k) return 0u;
+    const uint32_t s = umi_find(u, kn);
+    if (s == ~0u) return 0u;
+    const uint32_t cs = gp(u.reads)[s];
+    if (c == 1u && cs == 1u) uf_union(parent, i, s);
+    else {
+        if (c >= 2u && (unsigned long long)c + 1ull >= 2ull * cs) F2Q_ST32(&dom[s], 1u);
+        if (cs >= 2u && (unsigned long long)cs + 1ull >= 2ull * c) F2Q_ST32(&dom[i], 1u);
+    }
+    return 1u;
+}
+// after linking has ended (parent[] and bit 0 of dom[] are stable): a dominated single-read slot below a root marks the
+// root.  Only roots are written (bit 1; an OR whose old value is not asked for, so that bit 0 stays what the link left),
+// only the flag of a slot that is no root is read to decide anything -- no lane reads a word another lane of the launch
+// writes.  Bit 1 is only ever set on single-read slots: nothing else is united, so nothing else has a tree
+F2Q_HD void umi_dir_spread_one(const UmiDev &u, const uint32_t *parent, uint32_t *dom, uint32_t i)
+{
+    if (gp(u.slots)[i] == KEY_EMPTY || gp(u.reads)[i] != 1u) return;
+    uint32_t r = gp(parent)[i];
+    if (r == i || !(gp(dom)[i] & 1u)) return;
+    for (uint32_t p = gp(parent)[r]; p != r; p = gp(parent)[r]) r = p;
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)__hip_atomic_fetch_or(gpw(dom) + r, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    dom[r] |= 2u;
+#endif
+}
+// after spreading has ended: a slot with c >= 2 is a molecule when nothing dominates it, a tree of single reads is one
+// (at its root) when nothing dominates any member: d == 0 asks for neither bit (a slot with c >= 2 can only have bit 0).
+// tot[0] += slots whose flag the link set, tot[1] += reads (thread-local)
+F2Q_HD void umi_dir_root_one(const UmiDev &u, const uint32_t *parent, const uint32_t *dom, unsigned long long *molecules, uint32_t i,
+                             unsigned long long tot[2])
+{
+    const unsigned long long k = gp(u.slots)[i];
+    if (k == KEY_EMPTY) return;
+    const uint32_t c = gp(u.reads)[i], d = gp(dom)[i];
+    tot[0] += d & 1u; tot[1] += c;
+    if (!d && (c >= 2u || gp(parent)[i] == i)) acc_add(&molecules[(uint32_t)(k >> 32)], 1ull);
+}
+
 // the UMI of a read as 2-bit codes; false: invalid
 template <class P>
 F2Q_HD bool umi_codes(const UmiDev &u, int thr, P seq, int r, P qual, int qn, uint32_t &codes)
@@ -1162,6 +1261,17 @@ struct UmiHook {
     {
         uint32_t codes = 0;
         if (umi_codes(*u, thr, seq, r, qual, qn, codes)) { ust[0]++; ust[2] += umi_insert(*u, f, codes); }
+        else ust[1]++;
+    }
+};
+// the same with reads kept per pair (k_count_umi<true>)
+template <class P>
+struct UmiReadsHook {
+    const UmiDev *u; int thr; P seq; int r; P qual; int qn; unsigned long long *ust;
+    F2Q_HD void assigned(uint32_t f) const
+    {
+        uint32_t codes = 0;
+        if (umi_codes(*u, thr, seq, r, qual, qn, codes)) { ust[0]++; ust[2] += umi_insert_reads(*u, f, codes) == 1u; }
         else ust[1]++;
     }
 };

@@ -117,6 +117,7 @@ struct f2q_ctx {
     uint64_t umi_slots = 0, umi_min_slots = (uint64_t)1 << 16;   // F2Q_UMI_SLOTS: the first set's size (tests: growth from a small one)
     uint64_t umi_held_ub = 0;            // pairs held, an upper bound: every record launched since the last exact reading taken as new
     uint64_t umi_rehashes = 0;
+    bool umi_reads_on = false;           // f2q_set_umi_reads: umi.reads[] lives and dies with umi.slots[] (umi_set_allocs)
     bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
     int n_cu = 256;
@@ -466,7 +467,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (rc) return rc;
     if (c->umi_on) {                                  // umis[] has a word per feature: a new library starts a new set
         free_all(c, c->umi_set_allocs); free_all(c, c->umi_fix_allocs);
-        c->umi.slots = nullptr; c->umi.umis = nullptr; c->umi.ctr = nullptr; c->umi_slots = 0; c->umi_held_ub = 0;
+        c->umi.slots = nullptr; c->umi.reads = nullptr; c->umi.umis = nullptr; c->umi.ctr = nullptr; c->umi_slots = 0; c->umi_held_ub = 0;
     }
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
@@ -490,6 +491,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
     }
     if (c->umi_on && c->umi.umis) {
         if (c->umi.slots) HIPC(c, hipMemsetAsync(c->umi.slots, 0xFF, c->umi_slots * sizeof(unsigned long long), c->stream));
+        if (c->umi.reads) HIPC(c, hipMemsetAsync(c->umi.reads, 0, c->umi_slots * sizeof(uint32_t), c->stream));
         HIPC(c, hipMemsetAsync(c->umi.umis, 0, std::max<uint64_t>(c->lib_h.n_features, 1) * sizeof(unsigned long long), c->stream));
         HIPC(c, hipMemsetAsync(c->umi.ctr, 0, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), c->stream));
         c->umi_held_ub = 0;
@@ -541,6 +543,15 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
     c->force_general = true;
     c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
     c->plan.inband_n = false; c->plan.n_only = false;
+    return F2Q_OK;
+}
+
+extern "C" int f2q_set_umi_reads(f2q_ctx *c, int32_t on)
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->umi_on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_reads comes after f2q_set_umi and before counting");
+    c->umi_reads_on = on != 0;
     return F2Q_OK;
 }
 
@@ -994,7 +1005,8 @@ static int launch_fixed_v1(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32
 // the (feature, UMI) set before a launch over n records: afterwards it is at most half full even if every record brings a
 // new pair, so k_count_umi always finds room.  The pairs held are read from the device only when the bound kept on the
 // host says the set might be too small; a set that is grows to hold twice what it must (amortised rehash).  The new set
-// is allocated before the old one is given back: a failed allocation leaves the context as it was.
+// is allocated before the old one is given back: a failed allocation leaves the context as it was.  With reads kept
+// (f2q_set_umi_reads) reads[] comes and goes with slots[]: allocated zeroed next to it, filled by the rehash.
 static int umi_reserve(f2q_ctx *c, uint64_t n)
 {
     int rc;
@@ -1020,13 +1032,15 @@ static int umi_reserve(f2q_ctx *c, uint64_t n)
     while (slots < 2 * (held + n) || slots < 4 * held) slots <<= 1;
     if (slots > (1ull << 32)) return fail(c, F2Q_ENOMEM, "the UMI set would exceed 2^32 slots");
     UmiDev fresh = c->umi; std::vector<void *> owner;
-    if ((rc = dev_alloc(c, (size_t)slots, &fresh.slots, owner, 0xFF))) {
+    if ((rc = dev_alloc(c, (size_t)slots, &fresh.slots, owner, 0xFF)) ||
+        (c->umi_reads_on && (rc = dev_alloc(c, (size_t)slots, &fresh.reads, owner, 0)))) {
         free_all(c, owner);
         return fail(c, F2Q_ENOMEM, "no device memory for a UMI set of " + std::to_string(slots) + " slots: " + c->err);
     }
     fresh.mask = (uint32_t)(slots - 1);
     if (c->umi.slots && held) {
-        hipLaunchKernelGGL(k_umi_rehash, dim3((unsigned)((c->umi_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi, fresh);
+        if (c->umi.reads) hipLaunchKernelGGL(k_umi_rehash_reads, dim3((unsigned)((c->umi_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi, fresh);
+        else hipLaunchKernelGGL(k_umi_rehash, dim3((unsigned)((c->umi_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi, fresh);
         HIPC(c, hipGetLastError());
         c->umi_rehashes++;
         if (c->trace) fprintf(stderr, "[f2q trace] UMI set rehash %llu: %llu pairs, %llu -> %llu slots\n", (unsigned long long)c->umi_rehashes,
@@ -1034,7 +1048,7 @@ static int umi_reserve(f2q_ctx *c, uint64_t n)
     }
     free_all(c, c->umi_set_allocs);                              // (waits for the stream)
     c->umi_set_allocs = owner;
-    c->umi.slots = fresh.slots; c->umi.mask = fresh.mask; c->umi_slots = slots;
+    c->umi.slots = fresh.slots; c->umi.reads = fresh.reads; c->umi.mask = fresh.mask; c->umi_slots = slots;
     c->umi_held_ub = held + n;
     return F2Q_OK;
 }
@@ -1105,6 +1119,112 @@ extern "C" int f2q_umi_collapse(f2q_ctx *c, int32_t dist, int64_t *molecules, in
     return F2Q_OK;
 }
 
+// the wrap of a 32-bit count excluded on the host: no pair can have 2^32 reads while the context has counted fewer
+static int umi_reads_ready(f2q_ctx *c, const char *who, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
+{
+    if (!c->umi_on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (!c->umi_reads_on) return fail(c, F2Q_ESTATE, std::string(who) + " needs the reads per pair: call f2q_set_umi_reads before counting");
+    HIPC(c, hipSetDevice(c->device));
+    for (int i = 0; i < F2Q_UMI_CTR_WORDS; i++) ctr[i] = 0;
+    if (c->umi.ctr) HIPC(c, hipMemcpyAsync(ctr, c->umi.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+    if (ctr[F2Q_UMI_READS] >= (1ull << 32))
+        return fail(c, F2Q_EUNSUPPORTED, std::string(who) + ": 2^32 or more reads with a valid UMI -- a pair's 32-bit count may have wrapped");
+    return F2Q_OK;
+}
+
+// The directional rule of UMI-tools over the same set (include/f2q.h; the rule as it is computed: DESIGN.md).  Four
+// launches on the context's stream, the kernel boundary the only hand-off; parent[slots], dom[slots], molecules[n_features]
+// and three counters are scratch from the device-memory cache.  The set, reads[], umis[] and the counters are only read.
+extern "C" int f2q_umi_collapse_directional(f2q_ctx *c, int64_t *molecules, int64_t extra[4])
+{
+    if (!c) return F2Q_EINVAL;
+    unsigned long long ctr[F2Q_UMI_CTR_WORDS];
+    int rc = umi_reads_ready(c, "f2q_umi_collapse_directional", ctr);
+    if (rc) return rc;
+    const double t0 = now_ms();
+    const uint64_t nf = c->lib_h.n_features;
+    std::vector<unsigned long long> h(nf + 3, 0ull);             // molecules, edges, flagged slots, reads
+    float ms[4] = {0, 0, 0, 0};
+    uint32_t wg = F2Q_UMI_LINK_WG_DEFAULT, per_cu = F2Q_UMI_LINK_GRID_DEFAULT, glink = 0;
+    { const char *e = getenv("F2Q_UMI_LINK_WG"); if (e && atol(e) >= 64 && atol(e) <= F2Q_UMI_LINK_THREADS && atol(e) % 64 == 0) wg = (uint32_t)atol(e); }
+    { const char *e = getenv("F2Q_UMI_LINK_GRID"); if (e && atol(e) >= 1 && atol(e) <= 4096) per_cu = (uint32_t)atol(e); }
+    DevScope scratch(c);
+    if (c->umi.umis && c->umi.slots && c->umi.reads) {           // (nothing counted yet: all zero)
+        if (c->umi_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
+        uint32_t *parent = nullptr, *dom = nullptr; unsigned long long *mol = nullptr;
+        if (dev_alloc(c, (size_t)c->umi_slots, &parent, scratch.v) || dev_alloc(c, (size_t)c->umi_slots, &dom, scratch.v, 0) ||
+            dev_alloc(c, (size_t)nf + 3, &mol, scratch.v, 0))
+            return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi_slots) + " slots: " + c->err);
+        struct Events { hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } evs;
+        hipEvent_t *ev = evs.e;                                  // F2Q_TRACE=1: the time of each launch
+        if (c->trace) for (int i = 0; i < 5; i++) HIPC(c, hipEventCreate(&ev[i]));
+        const uint32_t g256 = (uint32_t)std::min<uint64_t>((c->umi_slots + 255) / 256, (uint64_t)c->n_cu * 8u);
+        glink = (uint32_t)std::min<uint64_t>((c->umi_slots + wg - 1) / wg, (uint64_t)c->n_cu * per_cu);
+        if (ev[0]) HIPC(c, hipEventRecord(ev[0], c->stream));
+        hipLaunchKernelGGL(k_umi_uf_init, dim3(g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi_slots);
+        HIPC(c, hipGetLastError());
+        EC_POINT(c, "k_umi_uf_init");
+        if (ev[1]) HIPC(c, hipEventRecord(ev[1], c->stream));
+        hipLaunchKernelGGL(k_umi_link_dir, dim3(glink), dim3(wg), 0, c->stream, c->umi, parent, dom, mol + nf);
+        HIPC(c, hipGetLastError());
+        EC_POINT(c, "k_umi_link_dir");
+        if (ev[2]) HIPC(c, hipEventRecord(ev[2], c->stream));
+        hipLaunchKernelGGL(k_umi_dir_spread, dim3(g256), dim3(256), 0, c->stream, c->umi, (const uint32_t *)parent, dom);
+        HIPC(c, hipGetLastError());
+        EC_POINT(c, "k_umi_dir_spread");
+        if (ev[3]) HIPC(c, hipEventRecord(ev[3], c->stream));
+        hipLaunchKernelGGL(k_umi_dir_roots, dim3(g256), dim3(256), 0, c->stream, c->umi, (const uint32_t *)parent, (const uint32_t *)dom, mol, mol + nf + 1);
+        HIPC(c, hipGetLastError());
+        EC_POINT(c, "k_umi_dir_roots");
+        if (ev[4]) HIPC(c, hipEventRecord(ev[4], c->stream));
+        HIPC(c, hipMemcpyAsync(h.data(), mol, (nf + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        if (ev[4]) {
+            HIPC(c, hipEventSynchronize(ev[4]));
+            for (int i = 0; i < 4; i++) HIPC(c, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+        }
+        HIPC(c, hipStreamSynchronize(c->stream));
+    }
+    unsigned long long total = 0;
+    for (uint64_t i = 0; i < nf; i++) { total += h[i]; if (molecules) molecules[i] = (int64_t)h[i]; }
+    if (extra) { extra[0] = (int64_t)ctr[F2Q_UMI_HELD]; extra[1] = (int64_t)h[nf]; extra[2] = (int64_t)h[nf + 1]; extra[3] = (int64_t)h[nf + 2]; }
+    if (c->trace) fprintf(stderr, "[f2q trace] UMI collapse directional: %llu pairs, %llu edges, %llu dominated, %llu molecules, %llu reads, %.3f ms (union-find init %.3f, link %.3f, spread %.3f, roots %.3f; wave, %u x %u)\n",
+                          ctr[F2Q_UMI_HELD], h[nf], h[nf + 1], total, h[nf + 2], now_ms() - t0, ms[0], ms[1], ms[2], ms[3], glink, wg);
+    return F2Q_OK;
+}
+
+// every pair the set holds with its reads, sorted by (feature, codes): the table copied and filtered on the host (no hot path)
+extern "C" int f2q_umi_pairs(f2q_ctx *c, uint64_t cap, uint64_t *n, uint32_t *feature, uint32_t *codes, uint32_t *reads)
+{
+    if (!c || !n) return F2Q_EINVAL;
+    unsigned long long ctr[F2Q_UMI_CTR_WORDS];
+    int rc = umi_reads_ready(c, "f2q_umi_pairs", ctr);
+    if (rc) return rc;
+    *n = ctr[F2Q_UMI_HELD];
+    if (!feature && !codes && !reads) return F2Q_OK;
+    if (cap < *n) return fail(c, F2Q_EINVAL, "f2q_umi_pairs: room for " + std::to_string(cap) + " pairs, the set holds " + std::to_string(*n));
+    if (!*n || !c->umi.slots || !c->umi.reads) return F2Q_OK;
+    std::vector<unsigned long long> words;                       // 12 bytes per slot on the host: a failure is F2Q_ENOMEM, not an exception
+    std::vector<uint32_t> cnt;
+    std::vector<std::pair<unsigned long long, uint32_t>> held;
+    try { words.resize(c->umi_slots); cnt.resize(c->umi_slots); held.reserve((size_t)*n); }
+    catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy a UMI set of " + std::to_string(c->umi_slots) + " slots"); }
+    HIPC(c, hipMemcpyAsync(words.data(), c->umi.slots, c->umi_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(cnt.data(), c->umi.reads, c->umi_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    uint64_t occupied = 0;
+    for (uint64_t i = 0; i < c->umi_slots; i++) if (words[i] != KEY_EMPTY && occupied++ < *n) held.emplace_back(words[i], cnt[i]);      // (never past the reserve)
+    if (occupied != *n) return fail(c, F2Q_EHIP, "the UMI set holds " + std::to_string(occupied) + " pairs, its counter says " + std::to_string(*n));
+    std::sort(held.begin(), held.end());                         // the word is (feature << 32) | codes
+    for (size_t i = 0; i < held.size(); i++) {
+        if (feature) feature[i] = (uint32_t)(held[i].first >> 32);
+        if (codes) codes[i] = (uint32_t)held[i].first;
+        if (reads) reads[i] = held[i].second;
+    }
+    return F2Q_OK;
+}
+
 // one set of launches over a view of a block (all of it in Counter mode, a step of it in Extract+Count mode)
 static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, Accum &acc, uint32_t &launches)
 {
@@ -1128,7 +1248,8 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
     const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
     if (c->umi_on) {                                             // the same road with the (feature, UMI) set (f2q_set_umi)
         if ((rc = umi_reserve(c, rb.n))) return rc;
-        hipLaunchKernelGGL(k_count_umi, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi);
+        if (c->umi.reads) hipLaunchKernelGGL(k_count_umi<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi);
+        else hipLaunchKernelGGL(k_count_umi<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi);
         HIPC(c, hipGetLastError());
         launches++;
         EC_POINT(c, "k_count_umi");

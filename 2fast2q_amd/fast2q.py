@@ -112,6 +112,8 @@ def _counter_kwargs(param):
                   device=int(param.get('device', os.environ.get("F2Q_DEVICE", os.environ.get("LOCAL_RANK", 0)))))
     if param.get('umi'):                            # a UMI context (f2q_set_umi); part of the key contexts are kept under
         kwargs['umi'] = tuple(param['umi'])         # (--mu is not: collapsing changes no context)
+        if param.get('umi_rule') == 'directional':  # --mur directional: the context keeps the reads of every pair (f2q_set_umi_reads)
+            kwargs['umi_reads'] = True
     return kwargs
 
 
@@ -260,6 +262,10 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             if param.get('umi_mismatch'):           # --mu 1: UMIs of a feature one base apart joined (f2q_umi_collapse)
                 molecules, pairs, edges = ctx.collapse_umis(param['umi_mismatch'])
                 param.setdefault('umi_collapsed', {})[raw] = ([int(n) for n in molecules], pairs, edges)
+            if param.get('umi_rule') == 'directional':      # --mur directional: the directional rule on the same set, and its pairs
+                molecules, pairs, edges, dominated, reads = ctx.collapse_umis_directional()
+                table = ctx.umi_pairs() if not param.get("delete", True) else None
+                param.setdefault('umi_directional', {})[raw] = ([int(n) for n in molecules], pairs, edges, dominated, reads, table)
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -347,12 +353,23 @@ def aligner(i, raw, features, param, reads_stats):
             molecules, pairs, edges = param['umi_collapsed'].pop(raw)
             param.setdefault("umi_collapsed_samples", {})[sample.name] = SampleResult(
                 sample.name, value, unit, _sample_rows(zip(names, molecules)), dict(local, umi_pairs=pairs, umi_edges=edges, umi_molecules=sum(molecules)))
+        directional = pair_table = None
+        if raw in param.get('umi_directional', {}):  # --mur directional: and again, holding molecules by the directional rule
+            directional, pairs, edges, dominated, reads, pair_table = param['umi_directional'].pop(raw)
+            param.setdefault("umi_directional_samples", {})[sample.name] = SampleResult(
+                sample.name, value, unit, _sample_rows(zip(names, directional)),
+                dict(local, umi_pairs=pairs, umi_edges=edges, umi_dominated=dominated, umi_molecules=sum(directional), umi_pair_reads=reads))
         if not param.get("delete", True) and sharding.world().rank == 0:
             os.makedirs(param["directory"], exist_ok=True)
-            per = zip(umis, molecules) if molecules is not None else ((n,) for n in umis)
-            both = _sample_rows((f.name, (f.counts,) + tuple(ns)) for f, ns in zip(features.values(), per))      # (the order of `rows`)
+            cols = [umis] + [c for c in (molecules, directional) if c is not None]
+            both = _sample_rows((f.name, (f.counts,) + tuple(ns)) for f, ns in zip(features.values(), zip(*cols)))      # (the order of `rows`)
             csv_writer(os.path.join(param["directory"], sample.name + "_umi_reads.csv"),
-                       [["#Feature", "Reads", "UMIs"] + (["Molecules"] if molecules is not None else [])] + [[name, *ns] for name, ns in both])
+                       [["#Feature", "Reads", "UMIs"] + (["Molecules"] if molecules is not None else []) + (["Directional"] if directional is not None else [])] +
+                       [[name, *ns] for name, ns in both])
+            if pair_table is not None:               # every (feature, UMI) pair with its reads, in f2q_umi_pairs' order
+                length = param['umi'][1]
+                csv_writer(os.path.join(param["directory"], sample.name + "_umi_pairs.csv"),
+                           [["#Feature", "UMI", "Reads"]] + [[names[f], umi_text(int(c), length), int(n)] for f, c, n in zip(*pair_table)])
     if not param['Progress bar']:
         colourful_errors("INFO", f"Sample {sample.name} was processed in {value} {unit}")
     param.setdefault("samples", {})[sample.name] = sample     # a later file of the same name replaces the earlier one,
@@ -419,6 +436,8 @@ def initializer(cmd):
         print(f" Distinct UMIs are counted per feature: UMI start position in the read: {param['umi'][0]}, length: {param['umi'][1]}bp")
     if param.get('umi_mismatch'):
         print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
+    if param.get('umi_rule') == 'directional':
+        print(" Molecules are also counted by the directional rule: a UMI absorbs a neighbour with at most (its reads + 1) / 2 reads (--mur directional)")
     print(f" All data will be saved into {param['directory']}")
     print("\n ---- ")
     param["cpu"] = param["cpu"] if isinstance(param["cpu"], int) and param["cpu"] > 0 else (os.cpu_count() or 1)
@@ -452,6 +471,11 @@ def ensure_example_fastq():
         with gzip.open(path, "wb", compresslevel=6) as f:
             f.write(fq)
     return path
+
+
+def umi_text(codes, length):
+    """the bases of a UMI held as 2-bit codes, base j in bits 2j .. 2j+1 (f2q_umi_pairs)"""
+    return "".join("ACGT"[(codes >> (2 * j)) & 3] for j in range(length))
 
 
 def parse_umi(text):
@@ -493,6 +517,7 @@ def input_parser(argv=None):
     ap.add_argument("--rc2", nargs='?', const=True, help="With --pe: mate 2 is reverse-complemented before its parts are taken")
     ap.add_argument("--umi", help="S,L: every read carries a UMI of L bases (1-16) at position S; Counter mode also reports the distinct UMIs per feature (<name>_umi.csv)")
     ap.add_argument("--mu", help="With --umi: mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")
+    ap.add_argument("--mur", help="With --umi and --mu 1: the rule UMIs are collapsed by, cluster (default) or directional. directional: a UMI absorbs a neighbouring UMI only when it has at least twice its reads minus one (<name>_umi_directional.csv)")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
     if args.v is not None:
@@ -562,6 +587,15 @@ def input_parser(argv=None):
             sys.exit(2)
         if args.mu == "1":
             p['umi_mismatch'] = 1
+    if args.mur is not None:
+        if args.mur not in ("cluster", "directional"):
+            colourful_errors("FATAL", f"--mur {args.mur}: expected cluster or directional.")
+            sys.exit(2)
+        if args.umi is None or args.mu != "1":
+            colourful_errors("FATAL", "--mur only has a meaning with --umi and --mu 1: the rule UMIs one base apart are collapsed by.")
+            sys.exit(2)
+        if args.mur == "directional":
+            p['umi_rule'] = 'directional'
     if args.assign is not None:
         if p['Running Mode'] != "EC":
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
@@ -689,6 +723,8 @@ def run_headers(param):
         lines.append(f"#UMI start position in the read, length: {param['umi'][0]},{param['umi'][1]}")
     if param.get('umi_mismatch'):
         lines.append(f"#UMI mismatches collapsed: {param['umi_mismatch']}")
+    if param.get('umi_rule') == 'directional':
+        lines.append("#UMI collapse rule: directional")
     return lines
 
 
@@ -730,6 +766,10 @@ def compiling(param):
         _, chead, ctable = compile_table(param["umi_collapsed_samples"])
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_umi_collapsed.csv"),
                    [chead] + [[feature] + counts for feature, counts in ctable.items()])
+    if param.get("umi_directional_samples"):         # --mur directional: and again, molecules by the directional rule
+        _, dhead, dtable = compile_table(param["umi_directional_samples"])
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_umi_directional.csv"),
+                   [dhead] + [[feature] + counts for feature, counts in dtable.items()])
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -749,6 +789,8 @@ STATS_HEAD = ["#Sample name", "Running Time", "Running Time unit", "Total number
 UMI_STATS_HEAD = ["#Sample name (UMI)", "Number of aligned reads with a valid UMI", "Number of aligned reads with an invalid UMI"]
 UMI_COLLAPSE_STATS_HEAD = ["#Sample name (UMI collapsed)", "Number of distinct (feature, UMI) pairs", "Number of pairs of them that differ in one base",
                            "Number of molecules"]
+UMI_DIRECTIONAL_STATS_HEAD = ["#Sample name (UMI directional)", "Number of distinct (feature, UMI) pairs", "Number of pairs of them that differ in one base",
+                              "Number of pairs a neighbour absorbs directly", "Number of molecules", "Number of reads of all pairs"]
 
 
 def run_stats(headers, param, compiled, head, ordered):
@@ -764,6 +806,10 @@ def run_stats(headers, param, compiled, head, ordered):
     if param.get("umi_collapsed_samples"):           # --mu 1: pairs, edges and molecules, one line per sample
         global_stat += [UMI_COLLAPSE_STATS_HEAD] + [[s.name, u.stats["umi_pairs"], u.stats["umi_edges"], u.stats["umi_molecules"]]
                                                     for s in ordered for u in [param["umi_collapsed_samples"].get(s.name)] if u is not None]
+    if param.get("umi_directional_samples"):         # --mur directional: sample, pairs, edges, dominated, molecules, reads
+        global_stat += [UMI_DIRECTIONAL_STATS_HEAD] + [[s.name, u.stats["umi_pairs"], u.stats["umi_edges"], u.stats["umi_dominated"], u.stats["umi_molecules"],
+                                                        u.stats["umi_pair_reads"]]
+                                                       for s in ordered for u in [param["umi_directional_samples"].get(s.name)] if u is not None]
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib

@@ -327,7 +327,7 @@ int f2q_read_umis(f2q_ctx *ctx, int64_t *umis, int64_t extra[2]);
  * that graph.  UMIs of different features are never joined.  extra[0] = pairs the set holds (the nodes), extra[1] =
  * joined unordered pairs, each once, over all features (the edges); with no edges molecules[f] == umis[f].  The result
  * depends on the set alone -- not on read order, the set's size or its growth -- so it is exact and reproducible.
- * Count-aware rules ("directional", "adjacency") need reads per pair, which the set does not hold.
+ * The count-aware "directional" rule is f2q_umi_collapse_directional below; "adjacency" is not implemented.
  *
  * dist 1 collapses; dist 0 returns umis[] and 0 edges; anything else is F2Q_EINVAL.  F2Q_ESTATE without f2q_set_umi;
  * F2Q_ENOMEM when the scratch (4 bytes per slot of the set, 8 per feature) cannot be had: the set is intact.  Nothing
@@ -335,6 +335,40 @@ int f2q_read_umis(f2q_ctx *ctx, int64_t *umis, int64_t extra[2]);
  * any number of times, also between counting calls, and changes no state that another call reads.
  * F2Q_TRACE=1 prints one line per call: "[f2q trace] UMI collapse: P pairs, E edges, M molecules, T ms (...)". */
 int f2q_umi_collapse(f2q_ctx *ctx, int32_t dist, int64_t *molecules, int64_t extra[2]);
+
+/* ---- reads per (feature, UMI) pair; the directional rule ---------------------------------------
+ * f2q_set_umi_reads(ctx, on != 0) makes the set keep, next to every pair, the number of reads that brought it: 32 bits
+ * per pair, carried along when the set grows, cleared by f2q_reset_counts.  After f2q_set_umi and before counting:
+ * F2Q_ESTATE without f2q_set_umi or once a counting call has been made.  Counts, the five counters, f2q_read_umis and
+ * f2q_umi_collapse are what the same context gives without the call.
+ *
+ * A pair's count wraps at 2^32.  Every wrap is excluded on the host: f2q_umi_collapse_directional and f2q_umi_pairs
+ * return F2Q_EUNSUPPORTED once the context has counted 2^32 or more reads with a valid UMI (f2q_read_umis' extra[0]);
+ * below that no pair can have wrapped.
+ *
+ * f2q_umi_collapse_directional: the "directional" rule of UMI-tools (its default).  For one feature, with c(x) the reads
+ * of UMI x: a absorbs b when they differ in exactly one base and c(a) >= 2 c(b) - 1; UMI-tools visits the UMIs by
+ * descending count and every UMI not yet reached from an earlier one starts a molecule.  Which UMIs end up together
+ * depends on the order among equal counts, the NUMBER of molecules does not, and molecules[f] is that number:
+ *   #{ v : c(v) >= 2 and no neighbour u has c(u) >= 2 c(v) - 1 }
+ * + #{ connected components of the UMIs with c == 1 in which no member has a neighbour u with c(u) >= 2 }
+ * so that f2q_umi_collapse's molecules[f] <= molecules[f] <= umis[f].  extra[0] = pairs the set holds, extra[1] =
+ * unordered pairs of them one base apart (f2q_umi_collapse's edges), extra[2] = pairs some neighbour absorbs directly,
+ * extra[3] = the sum of the reads of all pairs (f2q_read_umis' extra[0]).  Group membership is not reported.
+ * F2Q_ESTATE unless f2q_set_umi_reads(ctx, 1) came before counting; F2Q_ENOMEM when the scratch (8 bytes per slot of the
+ * set, 8 per feature) cannot be had or the set has more than 2^31 slots: the set is intact.  Nothing counted yet: all
+ * zero.  The call synchronises the stream; either pointer may be NULL; it may come any number of times, also between
+ * counting calls, and changes no state that another call reads.  F2Q_TRACE=1 prints one line per call:
+ * "[f2q trace] UMI collapse directional: P pairs, E edges, D dominated, M molecules, R reads, T ms (...)".
+ *
+ * f2q_umi_pairs: every pair with its reads, sorted by (feature, codes) -- a function of the set, not of read order.
+ * codes holds the UMI's bases as 2-bit codes (A, C, G, T = 0 .. 3), base j in bits 2j .. 2j+1.  *n = pairs held; with
+ * all three arrays NULL that is all (call once for n, then with arrays of cap >= n entries; any of them may be NULL).
+ * F2Q_EINVAL when cap < n; F2Q_ESTATE without reads kept; F2Q_ENOMEM when the host copy of the set (12 bytes per slot)
+ * cannot be had.  Synchronises the stream. */
+int f2q_set_umi_reads(f2q_ctx *ctx, int32_t on);
+int f2q_umi_collapse_directional(f2q_ctx *ctx, int64_t *molecules, int64_t extra[4]);
+int f2q_umi_pairs(f2q_ctx *ctx, uint64_t cap, uint64_t *n, uint32_t *feature, uint32_t *codes, uint32_t *reads);
 
 #ifdef __cplusplus
 }
