@@ -1051,23 +1051,8 @@ struct UmiDev {
     unsigned long long *ctr;         // [F2Q_UMI_CTR_WORDS]
     uint32_t *reads;                 // [slots] reads per pair, parallel to slots[] (f2q_set_umi_reads); null: not kept
 };
-// claims a slot for word k with one CAS: 1 = new, 0 = already there, 2 = no room (probe bound, as ec64_insert_word)
-F2Q_HD uint32_t umi_claim(const UmiDev &u, unsigned long long k)
-{
-    uint32_t s = hash32(k ^ (k >> 29), 32) & u.mask;
-    for (uint32_t guard = 0; guard <= u.mask; guard++) {
-        unsigned long long v = F2Q_LD64(&u.slots[s]);
-        if (v == KEY_EMPTY) {
-            v = ec_cas(&u.slots[s], KEY_EMPTY, k);
-            if (v == KEY_EMPTY) return 1u;
-        }
-        if (v == k) return 0u;
-        s = (s + 1) & u.mask;
-    }
-    F2Q_ST64(&u.ctr[F2Q_UMI_OVERFLOW], 1ull);
-    return 2u;
-}
-// umi_claim that also says where: `slot` is the slot that holds k (new or not); untouched on 2
+// claims a slot for word k with one CAS: 1 = new, 0 = already there, 2 = no room (probe bound, as ec64_insert_word).
+// `slot` is the slot that holds k (new or not), untouched on 2
 F2Q_HD uint32_t umi_claim_at(const UmiDev &u, unsigned long long k, uint32_t &slot)
 {
     uint32_t s = hash32(k ^ (k >> 29), 32) & u.mask;
@@ -1083,6 +1068,12 @@ F2Q_HD uint32_t umi_claim_at(const UmiDev &u, unsigned long long k, uint32_t &sl
     F2Q_ST64(&u.ctr[F2Q_UMI_OVERFLOW], 1ull);
     return 2u;
 }
+// the same with the slot discarded
+F2Q_HD uint32_t umi_claim(const UmiDev &u, unsigned long long k)
+{
+    uint32_t slot = 0;
+    return umi_claim_at(u, k, slot);
+}
 // one read more for the pair in `slot`: relaxed, agent scope, the old value is not asked for (a no-return atomic).  The
 // claimant of a slot and a lane that found the pair there may add in either order: reads[] starts at zero, sums commute
 F2Q_HD void umi_read_add(const UmiDev &u, uint32_t slot)
@@ -1093,32 +1084,31 @@ F2Q_HD void umi_read_add(const UmiDev &u, uint32_t slot)
     u.reads[slot] += 1u;
 #endif
 }
-// the pair (f, codes): 1 when it is new -- the claim adds 1 to umis[f] -- else 0
+// the pair (f, codes): 1 when it is new -- the claim adds 1 to umis[f] -- else 0.  READS (u.reads set): the read also
+// adds 1 to reads[slot of its pair], new or not
+template <bool READS>
 F2Q_HD uint32_t umi_insert(const UmiDev &u, uint32_t f, uint32_t codes)
-{
-    if (umi_claim(u, ((unsigned long long)f << 32) | codes) != 1u) return 0u;
-    acc_add(&u.umis[f], 1ull);
-    return 1u;
-}
-// umi_insert with reads kept (u.reads set): the read also adds 1 to reads[slot of its pair], new or not
-F2Q_HD uint32_t umi_insert_reads(const UmiDev &u, uint32_t f, uint32_t codes)
 {
     uint32_t slot = 0;
     const uint32_t rc = umi_claim_at(u, ((unsigned long long)f << 32) | codes, slot);
-    if (rc == 2u) return 0u;
-    umi_read_add(u, slot);
-    if (rc == 1u) acc_add(&u.umis[f], 1ull);
-    return rc;
+    if (READS && rc != 2u) umi_read_add(u, slot);
+    if (rc != 1u) return 0u;
+    acc_add(&u.umis[f], 1ull);
+    return 1u;
 }
-// k_umi_rehash with reads kept: the word of slot i of `old` into `nw`, its count into the slot it got there.  A plain
+// the word of slot i of `old` into `nw` (empty, with room for every pair of `old`); umis[] and the counters are shared
+// and stay as they are.  READS: nw.reads[] is zeroed, the pair's count goes into the slot it got there.  A plain
 // store: every word is in `old` once, so its slot of `nw` has this one writer
-F2Q_HD void umi_rehash_reads_one(const UmiDev &old, const UmiDev &nw, uint32_t i)
+template <bool READS>
+F2Q_HD void umi_rehash_one(const UmiDev &old, const UmiDev &nw, uint32_t i)
 {
     const unsigned long long k = gp(old.slots)[i];
     if (k == KEY_EMPTY) return;
     uint32_t slot = 0;
-    if (umi_claim_at(nw, k, slot) != 2u) gpw(nw.reads)[slot] = gp(old.reads)[i];
+    if (umi_claim_at(nw, k, slot) != 2u && READS) gpw(nw.reads)[slot] = gp(old.reads)[i];
 }
+// the reads-keeping step by name
+F2Q_HD void umi_rehash_reads_one(const UmiDev &old, const UmiDev &nw, uint32_t i) { umi_rehash_one<true>(old, nw, i); }
 // ---- UMIs at Hamming distance 1 collapsed per feature (f2q_umi_collapse) ----
 // Two pairs of ONE feature are joined when their UMIs differ in exactly one of the L bases (a substitution); the
 // molecules of a feature are the connected components of that graph.  The pass runs over the set after counting: the
@@ -1163,15 +1153,21 @@ F2Q_HD void uf_union(uint32_t *parent, uint32_t a, uint32_t b)
         if (ec_cas32(&parent[hi], hi, lo) == hi) return;
     }
 }
-// neighbour n (0 .. 3L-1) of the pair k in slot i: base n / 3 substituted by XOR with 1 + n % 3 -- the field stays inside
-// the low 32 bits for every L <= 16, the feature half is never touched.  Only the larger word of an edge is looked up,
-// so every edge is found once; a hit joins the two slots.  Returns the edges found (0 / 1)
-F2Q_HD uint32_t umi_link_one(const UmiDev &u, uint32_t *parent, uint32_t i, unsigned long long k, uint32_t n)
+// neighbour n (0 .. 3L-1) of the pair k: base n / 3 substituted by XOR with 1 + n % 3 -- the field stays inside the low
+// 32 bits for every L <= 16, the feature half is never touched.  Only the larger word of an edge is looked up, so every
+// edge is found once.  True: there is an edge to visit from here, `s` is the neighbour's slot
+F2Q_HD bool umi_neighbour(const UmiDev &u, unsigned long long k, uint32_t n, uint32_t &s)
 {
     const unsigned long long kn = k ^ ((unsigned long long)(1u + n % 3u) << (2u * (n / 3u)));
-    if (kn < k) return 0u;
-    const uint32_t s = umi_find(u, kn);
-    if (s == ~0u) return 0u;
+    if (kn < k) return false;
+    s = umi_find(u, kn);
+    return s != ~0u;
+}
+// neighbour n of the pair k in slot i: a hit joins the two slots.  Returns the edges found (0 / 1)
+F2Q_HD uint32_t umi_link_one(const UmiDev &u, uint32_t *parent, uint32_t i, unsigned long long k, uint32_t n)
+{
+    uint32_t s = 0;
+    if (!umi_neighbour(u, k, n, s)) return 0u;
     uf_union(parent, i, s);
     return 1u;
 }
@@ -1187,17 +1183,14 @@ F2Q_HD void umi_root_one(const UmiDev &u, uint32_t *parent, unsigned long long *
 // along such an edge and stay equal only at 1 / 1, so the strongly connected components of the directed graph are every
 // node with c >= 2 alone and the connected components of the Hamming-1 graph among the nodes with c == 1; the molecules
 // are the components no edge enters from outside.  dom[slot] bit 0: an edge from a node with c >= 2 enters
-// this slot (k_umi_link_dir); bit 1, roots of the c == 1 forest only: it enters a member of the tree (k_umi_dir_spread).
+// this slot (k_umi_link<true>); bit 1, roots of the c == 1 forest only: it enters a member of the tree (k_umi_dir_spread).
 //
-// neighbour n of the pair k (c reads) in slot i, as umi_link_one finds it: only the larger word of an edge is looked up,
-// so every edge is visited once, and both directions are decided at that visit.  c + 1 >= 2 c' in 64 bits: no count of
-// 32 bits overflows it
+// neighbour n of the pair k (c reads) in slot i, as umi_link_one finds it: every edge is visited once, and both
+// directions are decided at that visit.  c + 1 >= 2 c' in 64 bits: no count of 32 bits overflows it
 F2Q_HD uint32_t umi_link_dir_one(const UmiDev &u, uint32_t *parent, uint32_t *dom, uint32_t i, unsigned long long k, uint32_t c, uint32_t n)
 {
-    const unsigned long long kn = k ^ ((unsigned long long)(1u + n % 3u) << (2u * (n / 3u)));
-    if (kn < k) return 0u;
-    const uint32_t s = umi_find(u, kn);
-    if (s == ~0u) return 0u;
+    uint32_t s = 0;
+    if (!umi_neighbour(u, k, n, s)) return 0u;
     const uint32_t cs = gp(u.reads)[s];
     if (c == 1u && cs == 1u) uf_union(parent, i, s);
     else {
@@ -1253,28 +1246,19 @@ F2Q_HD bool umi_codes(const UmiDev &u, int thr, P seq, int r, P qual, int qn, ui
 }
 // general_read calls hook.assigned(idx) for a read match_key has given feature idx; the default does nothing
 struct NoReadHook { F2Q_HD void assigned(uint32_t) const {} };
-// ust: thread-local sums -- [0] valid, [1] invalid, [2] new pairs
-template <class P>
+// ust: thread-local sums -- [0] valid, [1] invalid, [2] new pairs.  READS: reads kept per pair (k_count_umi<true>)
+template <class P, bool READS = false>
 struct UmiHook {
     const UmiDev *u; int thr; P seq; int r; P qual; int qn; unsigned long long *ust;
     F2Q_HD void assigned(uint32_t f) const
     {
         uint32_t codes = 0;
-        if (umi_codes(*u, thr, seq, r, qual, qn, codes)) { ust[0]++; ust[2] += umi_insert(*u, f, codes); }
+        if (umi_codes(*u, thr, seq, r, qual, qn, codes)) { ust[0]++; ust[2] += umi_insert<READS>(*u, f, codes); }
         else ust[1]++;
     }
 };
-// the same with reads kept per pair (k_count_umi<true>)
-template <class P>
-struct UmiReadsHook {
-    const UmiDev *u; int thr; P seq; int r; P qual; int qn; unsigned long long *ust;
-    F2Q_HD void assigned(uint32_t f) const
-    {
-        uint32_t codes = 0;
-        if (umi_codes(*u, thr, seq, r, qual, qn, codes)) { ust[0]++; ust[2] += umi_insert_reads(*u, f, codes) == 1u; }
-        else ust[1]++;
-    }
-};
+// the reads-keeping hook by name
+template <class P> using UmiReadsHook = UmiHook<P, true>;
 
 // ---------------------------------------------------------------------------------------------
 // general path: one read given as raw bytes.  st[] = the 5 reference counters (thread-local).

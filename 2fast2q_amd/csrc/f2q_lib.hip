@@ -12,6 +12,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <unordered_map>
@@ -111,13 +112,15 @@ struct f2q_ctx {
     uint64_t ec_gen = 1, asg_gen = 0;    // ec_gen: bumped by every count call, reset and table growth
     // distinct UMIs per feature (f2q_set_umi): the set of (feature, UMI) pairs, umis[n_features] and the counters.  The set
     // outlives the pieces of a file; umi_reserve sizes it before every launch
-    bool umi_on = false;
-    UmiDev umi{};
-    std::vector<void *> umi_set_allocs, umi_fix_allocs;      // the slots / umis[] and the counters
-    uint64_t umi_slots = 0, umi_min_slots = (uint64_t)1 << 16;   // F2Q_UMI_SLOTS: the first set's size (tests: growth from a small one)
-    uint64_t umi_held_ub = 0;            // pairs held, an upper bound: every record launched since the last exact reading taken as new
-    uint64_t umi_rehashes = 0;
-    bool umi_reads_on = false;           // f2q_set_umi_reads: umi.reads[] lives and dies with umi.slots[] (umi_set_allocs)
+    struct {
+        bool on = false;
+        UmiDev dev{};
+        std::vector<void *> set_allocs, fix_allocs;          // the slots / umis[] and the counters
+        uint64_t n_slots = 0, min_slots = (uint64_t)1 << 16;     // F2Q_UMI_SLOTS: the first set's size (tests: growth from a small one)
+        uint64_t held_ub = 0;            // pairs held, an upper bound: every record launched since the last exact reading taken as new
+        uint64_t rehashes = 0;
+        bool reads_on = false;           // f2q_set_umi_reads: dev.reads[] lives and dies with dev.slots[] (set_allocs)
+    } umi;
     bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
     int n_cu = 256;
@@ -400,6 +403,34 @@ extern "C" int f2q_create(const f2q_params *p, f2q_ctx **out)
     return F2Q_OK;
 }
 
+// the (feature, UMI) set given back: f2q_destroy, and a new library (umis[] has a word per feature)
+static void umi_drop(f2q_ctx *c)
+{
+    free_all(c, c->umi.set_allocs); free_all(c, c->umi.fix_allocs);
+    c->umi.dev.slots = nullptr; c->umi.dev.reads = nullptr; c->umi.dev.umis = nullptr; c->umi.dev.ctr = nullptr; c->umi.n_slots = 0; c->umi.held_ub = 0;
+}
+
+// the set, umis[] and the counters cleared (f2q_reset_counts), the set's size kept
+static int umi_clear(f2q_ctx *c)
+{
+    if (c->umi.dev.slots) HIPC(c, hipMemsetAsync(c->umi.dev.slots, 0xFF, c->umi.n_slots * sizeof(unsigned long long), c->stream));
+    if (c->umi.dev.reads) HIPC(c, hipMemsetAsync(c->umi.dev.reads, 0, c->umi.n_slots * sizeof(uint32_t), c->stream));
+    HIPC(c, hipMemsetAsync(c->umi.dev.umis, 0, std::max<uint64_t>(c->lib_h.n_features, 1) * sizeof(unsigned long long), c->stream));
+    HIPC(c, hipMemsetAsync(c->umi.dev.ctr, 0, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), c->stream));
+    c->umi.held_ub = 0;
+    return F2Q_OK;
+}
+
+// the set's counters after everything on the stream (all zero before the first launch); waits for the stream
+static int umi_read_ctr(f2q_ctx *c, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
+{
+    for (int i = 0; i < F2Q_UMI_CTR_WORDS; i++) ctr[i] = 0;
+    if (c->umi.dev.ctr) HIPC(c, hipMemcpyAsync(ctr, c->umi.dev.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+    return F2Q_OK;
+}
+
 extern "C" void f2q_destroy(f2q_ctx *c)
 {
     if (!c) return;
@@ -410,8 +441,8 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
     free_all(c, c->lib_allocs); free_all(c, c->ec_allocs); free_all(c, c->ec_allocs64); free_all(c, c->ec_allocs_ctr); free_all(c, c->hot_allocs);
     free_all(c, c->asg_lib_allocs); free_all(c, c->asg_allocs);
-    if (c->trace && c->umi_on) fprintf(stderr, "[f2q trace] UMI set: %llu slots, %llu rehashes\n", (unsigned long long)c->umi_slots, (unsigned long long)c->umi_rehashes);
-    free_all(c, c->umi_set_allocs); free_all(c, c->umi_fix_allocs);
+    if (c->trace && c->umi.on) fprintf(stderr, "[f2q trace] UMI set: %llu slots, %llu rehashes\n", (unsigned long long)c->umi.n_slots, (unsigned long long)c->umi.rehashes);
+    umi_drop(c);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
@@ -465,10 +496,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (rc) return rc;
     rc = alloc_acc(c, n);
     if (rc) return rc;
-    if (c->umi_on) {                                  // umis[] has a word per feature: a new library starts a new set
-        free_all(c, c->umi_set_allocs); free_all(c, c->umi_fix_allocs);
-        c->umi.slots = nullptr; c->umi.reads = nullptr; c->umi.umis = nullptr; c->umi.ctr = nullptr; c->umi_slots = 0; c->umi_held_ub = 0;
-    }
+    if (c->umi.on) umi_drop(c);                       // a new library starts a new set
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
     // symbol of any feature), every other odd symbol still sends the read to the byte-exact routine
@@ -489,13 +517,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
         free_all(c, c->ec_allocs); free_all(c, c->ec_allocs64); free_all(c, c->ec_allocs_ctr);
         memset(&c->ec, 0, sizeof c->ec); c->ec_slots = 0; c->hot_valid = false; c->ec_learned = 0;
     }
-    if (c->umi_on && c->umi.umis) {
-        if (c->umi.slots) HIPC(c, hipMemsetAsync(c->umi.slots, 0xFF, c->umi_slots * sizeof(unsigned long long), c->stream));
-        if (c->umi.reads) HIPC(c, hipMemsetAsync(c->umi.reads, 0, c->umi_slots * sizeof(uint32_t), c->stream));
-        HIPC(c, hipMemsetAsync(c->umi.umis, 0, std::max<uint64_t>(c->lib_h.n_features, 1) * sizeof(unsigned long long), c->stream));
-        HIPC(c, hipMemsetAsync(c->umi.ctr, 0, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), c->stream));
-        c->umi_held_ub = 0;
-    }
+    if (c->umi.on && c->umi.dev.umis) if (int rc = umi_clear(c)) return rc;
     c->reads_seen = 0;
     c->ec_gen++;
     // no host synchronisation: the clear is ordered on the context's stream like every launch and read-back after it
@@ -534,11 +556,11 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
     if (!c) return F2Q_EINVAL;
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi takes a Counter context: Extract+Count assigns no read to a feature");
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) is not implemented");
-    if (c->umi_on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
+    if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
     if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
         return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
-    c->umi_on = true; c->umi.start = start; c->umi.length = length;
-    { const char *e = getenv("F2Q_UMI_SLOTS"); if (e && atol(e) > 0) { c->umi_min_slots = 2; while (c->umi_min_slots < (uint64_t)atol(e) && c->umi_min_slots < (1ull << 32)) c->umi_min_slots <<= 1; } }
+    c->umi.on = true; c->umi.dev.start = start; c->umi.dev.length = length;
+    { const char *e = getenv("F2Q_UMI_SLOTS"); if (e && atol(e) > 0) { c->umi.min_slots = 2; while (c->umi.min_slots < (uint64_t)atol(e) && c->umi.min_slots < (1ull << 32)) c->umi.min_slots <<= 1; } }
     // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
     c->force_general = true;
     c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
@@ -549,27 +571,25 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
 extern "C" int f2q_set_umi_reads(f2q_ctx *c, int32_t on)
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->umi_on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (!c->umi.on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
     if (c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_reads comes after f2q_set_umi and before counting");
-    c->umi_reads_on = on != 0;
+    c->umi.reads_on = on != 0;
     return F2Q_OK;
 }
 
 extern "C" int f2q_read_umis(f2q_ctx *c, int64_t *umis, int64_t extra[2])
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->umi_on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (!c->umi.on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
     HIPC(c, hipSetDevice(c->device));
     const uint64_t nf = c->lib_h.n_features;
-    std::vector<unsigned long long> h(nf + F2Q_UMI_CTR_WORDS, 0ull);
-    if (c->umi.umis) {                                           // (nothing counted yet: all zero)
-        if (nf) HIPC(c, hipMemcpyAsync(h.data(), c->umi.umis, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipMemcpyAsync(h.data() + nf, c->umi.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (h[nf + F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+    std::vector<unsigned long long> h(nf, 0ull);
+    unsigned long long ctr[F2Q_UMI_CTR_WORDS];
+    if (c->umi.dev.umis && nf)                                   // (nothing counted yet: all zero)
+        HIPC(c, hipMemcpyAsync(h.data(), c->umi.dev.umis, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = umi_read_ctr(c, ctr)) return rc;
     if (umis) for (uint64_t i = 0; i < nf; i++) umis[i] = (int64_t)h[i];
-    if (extra) { extra[0] = (int64_t)h[nf + F2Q_UMI_READS]; extra[1] = (int64_t)h[nf + F2Q_UMI_FAILED]; }
+    if (extra) { extra[0] = (int64_t)ctr[F2Q_UMI_READS]; extra[1] = (int64_t)ctr[F2Q_UMI_FAILED]; }
     return F2Q_OK;
 }
 
@@ -1010,46 +1030,78 @@ static int launch_fixed_v1(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32
 static int umi_reserve(f2q_ctx *c, uint64_t n)
 {
     int rc;
-    if (!c->umi.umis) {
-        UmiDev u = c->umi; std::vector<void *> owner;
+    if (!c->umi.dev.umis) {
+        UmiDev u = c->umi.dev; std::vector<void *> owner;
         if ((rc = dev_alloc(c, (size_t)std::max<uint64_t>(c->lib_h.n_features, 1), &u.umis, owner, 0)) ||
             (rc = dev_alloc(c, (size_t)F2Q_UMI_CTR_WORDS, &u.ctr, owner, 0))) {
             free_all(c, owner);
             return fail(c, F2Q_ENOMEM, "no device memory for the UMI counters: " + c->err);
         }
-        c->umi.umis = u.umis; c->umi.ctr = u.ctr; c->umi_fix_allocs = owner;
+        c->umi.dev.umis = u.umis; c->umi.dev.ctr = u.ctr; c->umi.fix_allocs = owner;
     }
-    if (c->umi.slots && 2 * (c->umi_held_ub + n) <= c->umi_slots) { c->umi_held_ub += n; return F2Q_OK; }
+    if (c->umi.dev.slots && 2 * (c->umi.held_ub + n) <= c->umi.n_slots) { c->umi.held_ub += n; return F2Q_OK; }
     unsigned long long ctr[F2Q_UMI_CTR_WORDS] = {0, 0, 0, 0};
-    if (c->umi.slots) {
-        HIPC(c, hipMemcpyAsync(ctr, c->umi.ctr, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
-        HIPC(c, hipStreamSynchronize(c->stream));
-        if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
-        if (2 * (ctr[F2Q_UMI_HELD] + n) <= c->umi_slots) { c->umi_held_ub = ctr[F2Q_UMI_HELD] + n; return F2Q_OK; }
+    if (c->umi.dev.slots) {
+        if ((rc = umi_read_ctr(c, ctr))) return rc;
+        if (2 * (ctr[F2Q_UMI_HELD] + n) <= c->umi.n_slots) { c->umi.held_ub = ctr[F2Q_UMI_HELD] + n; return F2Q_OK; }
     }
     const uint64_t held = ctr[F2Q_UMI_HELD];
-    uint64_t slots = std::max<uint64_t>(c->umi_min_slots, 2);
+    uint64_t slots = std::max<uint64_t>(c->umi.min_slots, 2);
     while (slots < 2 * (held + n) || slots < 4 * held) slots <<= 1;
     if (slots > (1ull << 32)) return fail(c, F2Q_ENOMEM, "the UMI set would exceed 2^32 slots");
-    UmiDev fresh = c->umi; std::vector<void *> owner;
+    UmiDev fresh = c->umi.dev; std::vector<void *> owner;
     if ((rc = dev_alloc(c, (size_t)slots, &fresh.slots, owner, 0xFF)) ||
-        (c->umi_reads_on && (rc = dev_alloc(c, (size_t)slots, &fresh.reads, owner, 0)))) {
+        (c->umi.reads_on && (rc = dev_alloc(c, (size_t)slots, &fresh.reads, owner, 0)))) {
         free_all(c, owner);
         return fail(c, F2Q_ENOMEM, "no device memory for a UMI set of " + std::to_string(slots) + " slots: " + c->err);
     }
     fresh.mask = (uint32_t)(slots - 1);
-    if (c->umi.slots && held) {
-        if (c->umi.reads) hipLaunchKernelGGL(k_umi_rehash_reads, dim3((unsigned)((c->umi_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi, fresh);
-        else hipLaunchKernelGGL(k_umi_rehash, dim3((unsigned)((c->umi_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi, fresh);
+    if (c->umi.dev.slots && held) {
+        if (c->umi.dev.reads) hipLaunchKernelGGL(k_umi_rehash<true>, dim3((unsigned)((c->umi.n_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi.dev, fresh);
+        else hipLaunchKernelGGL(k_umi_rehash<false>, dim3((unsigned)((c->umi.n_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi.dev, fresh);
         HIPC(c, hipGetLastError());
-        c->umi_rehashes++;
-        if (c->trace) fprintf(stderr, "[f2q trace] UMI set rehash %llu: %llu pairs, %llu -> %llu slots\n", (unsigned long long)c->umi_rehashes,
-                              (unsigned long long)held, (unsigned long long)c->umi_slots, (unsigned long long)slots);
+        c->umi.rehashes++;
+        if (c->trace) fprintf(stderr, "[f2q trace] UMI set rehash %llu: %llu pairs, %llu -> %llu slots\n", (unsigned long long)c->umi.rehashes,
+                              (unsigned long long)held, (unsigned long long)c->umi.n_slots, (unsigned long long)slots);
     }
-    free_all(c, c->umi_set_allocs);                              // (waits for the stream)
-    c->umi_set_allocs = owner;
-    c->umi.slots = fresh.slots; c->umi.reads = fresh.reads; c->umi.mask = fresh.mask; c->umi_slots = slots;
-    c->umi_held_ub = held + n;
+    free_all(c, c->umi.set_allocs);                              // (waits for the stream)
+    c->umi.set_allocs = owner;
+    c->umi.dev.slots = fresh.slots; c->umi.dev.reads = fresh.reads; c->umi.dev.mask = fresh.mask; c->umi.n_slots = slots;
+    c->umi.held_ub = held + n;
+    return F2Q_OK;
+}
+
+// the linking launch (defaults and alternatives: DESIGN.md): threads per workgroup (F2Q_UMI_LINK_WG: whole waves, at most
+// F2Q_UMI_LINK_THREADS), workgroups per CU at most (F2Q_UMI_LINK_GRID: 1 .. 4096), the lane-per-slot layout instead of the
+// wave-cooperative one (F2Q_UMI_LINK=lane: A/B runs); anything else is the default.  g256: the grid of the slot-stride kernels
+struct UmiGeom { uint32_t wg, g256, glink; bool by_lane; };
+static UmiGeom umi_geometry(const f2q_ctx *c, uint64_t slots)
+{
+    uint32_t wg = F2Q_UMI_LINK_WG_DEFAULT, per_cu = F2Q_UMI_LINK_GRID_DEFAULT;
+    { const char *e = getenv("F2Q_UMI_LINK_WG"); if (e && atol(e) >= 64 && atol(e) <= F2Q_UMI_LINK_THREADS && atol(e) % 64 == 0) wg = (uint32_t)atol(e); }
+    { const char *e = getenv("F2Q_UMI_LINK_GRID"); if (e && atol(e) >= 1 && atol(e) <= 4096) per_cu = (uint32_t)atol(e); }
+    const char *e = getenv("F2Q_UMI_LINK");
+    return {wg, (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)c->n_cu * 8u),
+            (uint32_t)std::min<uint64_t>((slots + wg - 1) / wg, (uint64_t)c->n_cu * per_cu), e && !strcmp(e, "lane")};
+}
+
+// The launches of a collapse, one after the other on the context's stream, the kernel boundary the only hand-off between
+// them.  F2Q_TRACE=1: an event around each, ms[i] = the time of stage i once the last has ended (else ms[] stays as it is)
+struct UmiStage { const char *name; std::function<void()> launch; };
+static int umi_run_stages(f2q_ctx *c, const std::vector<UmiStage> &stages, float *ms)
+{
+    struct Events { std::vector<hipEvent_t> e; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
+    if (c->trace) { ev.e.assign(stages.size() + 1, nullptr); for (hipEvent_t &x : ev.e) HIPC(c, hipEventCreate(&x)); }
+    for (size_t i = 0; i < stages.size(); i++) {
+        if (c->trace) HIPC(c, hipEventRecord(ev.e[i], c->stream));
+        stages[i].launch();
+        HIPC(c, hipGetLastError());
+        EC_POINT(c, stages[i].name);
+    }
+    if (!c->trace) return F2Q_OK;
+    HIPC(c, hipEventRecord(ev.e.back(), c->stream));
+    HIPC(c, hipEventSynchronize(ev.e.back()));
+    for (size_t i = 0; i < stages.size(); i++) HIPC(c, hipEventElapsedTime(&ms[i], ev.e[i], ev.e[i + 1]));
     return F2Q_OK;
 }
 
@@ -1059,138 +1111,89 @@ static int umi_reserve(f2q_ctx *c, uint64_t n)
 extern "C" int f2q_umi_collapse(f2q_ctx *c, int32_t dist, int64_t *molecules, int64_t extra[2])
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->umi_on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (!c->umi.on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
     if (dist != 0 && dist != 1) return fail(c, F2Q_EINVAL, "UMIs are collapsed at Hamming distance 1 (or 0: as they are)");
     HIPC(c, hipSetDevice(c->device));
     const double t0 = now_ms();
     const uint64_t nf = c->lib_h.n_features;
-    std::vector<unsigned long long> h(nf + 1 + F2Q_UMI_CTR_WORDS, 0ull);      // molecules, edges, the set's counters
+    std::vector<unsigned long long> h(nf + 1, 0ull);             // molecules, edges
     float ms[3] = {0, 0, 0};
-    // the linking launch (defaults and alternatives: DESIGN.md): threads per workgroup (whole waves, at most F2Q_UMI_LINK_THREADS),
-    // workgroups per CU at most, and the lane-per-slot layout instead of the wave-cooperative one (A/B runs)
-    uint32_t wg = F2Q_UMI_LINK_WG_DEFAULT, per_cu = F2Q_UMI_LINK_GRID_DEFAULT, glink = 0; bool by_lane = false;
-    { const char *e = getenv("F2Q_UMI_LINK_WG"); if (e && atol(e) >= 64 && atol(e) <= F2Q_UMI_LINK_THREADS && atol(e) % 64 == 0) wg = (uint32_t)atol(e); }
-    { const char *e = getenv("F2Q_UMI_LINK_GRID"); if (e && atol(e) >= 1 && atol(e) <= 4096) per_cu = (uint32_t)atol(e); }
-    { const char *e = getenv("F2Q_UMI_LINK"); by_lane = e && !strcmp(e, "lane"); }
+    const UmiGeom g = umi_geometry(c, dist ? c->umi.n_slots : 0);     // (dist 0 launches nothing)
+    const UmiDev &u = c->umi.dev;
     DevScope scratch(c);
-    if (c->umi.umis && c->umi.slots) {                           // (nothing counted yet: all zero)
-        if (dist == 0) {
-            if (nf) HIPC(c, hipMemcpyAsync(h.data(), c->umi.umis, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        } else {
-            if (c->umi_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
-            uint32_t *parent = nullptr; unsigned long long *mol = nullptr;
-            if (dev_alloc(c, (size_t)c->umi_slots, &parent, scratch.v) || dev_alloc(c, (size_t)nf + 1, &mol, scratch.v, 0))
-                return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi_slots) + " slots: " + c->err);
-            struct Events { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } evs;
-            hipEvent_t *ev = evs.e;                              // F2Q_TRACE=1: the time of each launch
-            if (c->trace) for (int i = 0; i < 4; i++) HIPC(c, hipEventCreate(&ev[i]));
-            const uint32_t g256 = (uint32_t)std::min<uint64_t>((c->umi_slots + 255) / 256, (uint64_t)c->n_cu * 8u);
-            glink = (uint32_t)std::min<uint64_t>((c->umi_slots + wg - 1) / wg, (uint64_t)c->n_cu * per_cu);
-            if (ev[0]) HIPC(c, hipEventRecord(ev[0], c->stream));
-            hipLaunchKernelGGL(k_umi_uf_init, dim3(g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi_slots);
-            HIPC(c, hipGetLastError());
-            EC_POINT(c, "k_umi_uf_init");
-            if (ev[1]) HIPC(c, hipEventRecord(ev[1], c->stream));
-            if (by_lane) hipLaunchKernelGGL(k_umi_link_lane, dim3(glink), dim3(wg), 0, c->stream, c->umi, parent, mol + nf);
-            else hipLaunchKernelGGL(k_umi_link, dim3(glink), dim3(wg), 0, c->stream, c->umi, parent, mol + nf);
-            HIPC(c, hipGetLastError());
-            EC_POINT(c, "k_umi_link");
-            if (ev[2]) HIPC(c, hipEventRecord(ev[2], c->stream));
-            hipLaunchKernelGGL(k_umi_roots, dim3(g256), dim3(256), 0, c->stream, c->umi, parent, mol);
-            HIPC(c, hipGetLastError());
-            EC_POINT(c, "k_umi_roots");
-            if (ev[3]) HIPC(c, hipEventRecord(ev[3], c->stream));
-            HIPC(c, hipMemcpyAsync(h.data(), mol, (nf + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-            if (ev[3]) {
-                HIPC(c, hipEventSynchronize(ev[3]));
-                for (int i = 0; i < 3; i++) HIPC(c, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-            }
-        }
-        HIPC(c, hipMemcpyAsync(h.data() + nf + 1, c->umi.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (u.umis && u.slots && dist == 0) {                        // (nothing counted yet: all zero)
+        if (nf) HIPC(c, hipMemcpyAsync(h.data(), u.umis, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    } else if (u.umis && u.slots) {
+        if (c->umi.n_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
+        uint32_t *parent = nullptr; unsigned long long *mol = nullptr;
+        if (dev_alloc(c, (size_t)c->umi.n_slots, &parent, scratch.v) || dev_alloc(c, (size_t)nf + 1, &mol, scratch.v, 0))
+            return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi.n_slots) + " slots: " + c->err);
+        const std::vector<UmiStage> stages = {
+            {"k_umi_uf_init", [&] { hipLaunchKernelGGL(k_umi_uf_init, dim3(g.g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi.n_slots); }},
+            {"k_umi_link", [&] {
+                if (g.by_lane) hipLaunchKernelGGL(k_umi_link_lane, dim3(g.glink), dim3(g.wg), 0, c->stream, u, parent, mol + nf);
+                else hipLaunchKernelGGL(k_umi_link<false>, dim3(g.glink), dim3(g.wg), 0, c->stream, u, parent, (uint32_t *)nullptr, mol + nf); }},
+            {"k_umi_roots", [&] { hipLaunchKernelGGL(k_umi_roots, dim3(g.g256), dim3(256), 0, c->stream, u, parent, mol); }}};
+        if (int rc = umi_run_stages(c, stages, ms)) return rc;
+        HIPC(c, hipMemcpyAsync(h.data(), mol, (nf + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     }
-    HIPC(c, hipStreamSynchronize(c->stream));
-    const unsigned long long *ctr = h.data() + nf + 1;
-    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+    unsigned long long ctr[F2Q_UMI_CTR_WORDS];
+    if (int rc = umi_read_ctr(c, ctr)) return rc;
     unsigned long long total = 0;
     for (uint64_t i = 0; i < nf; i++) { total += h[i]; if (molecules) molecules[i] = (int64_t)h[i]; }
     if (extra) { extra[0] = (int64_t)ctr[F2Q_UMI_HELD]; extra[1] = (int64_t)h[nf]; }
     if (c->trace) fprintf(stderr, "[f2q trace] UMI collapse: %llu pairs, %llu edges, %llu molecules, %.3f ms (union-find init %.3f, link %.3f, roots %.3f; %s, %u x %u)\n",
-                          ctr[F2Q_UMI_HELD], h[nf], total, now_ms() - t0, ms[0], ms[1], ms[2], by_lane ? "lane" : "wave", glink, wg);
+                          ctr[F2Q_UMI_HELD], h[nf], total, now_ms() - t0, ms[0], ms[1], ms[2], g.by_lane ? "lane" : "wave", g.glink, g.wg);
     return F2Q_OK;
 }
 
 // the wrap of a 32-bit count excluded on the host: no pair can have 2^32 reads while the context has counted fewer
 static int umi_reads_ready(f2q_ctx *c, const char *who, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
 {
-    if (!c->umi_on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
-    if (!c->umi_reads_on) return fail(c, F2Q_ESTATE, std::string(who) + " needs the reads per pair: call f2q_set_umi_reads before counting");
+    if (!c->umi.on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (!c->umi.reads_on) return fail(c, F2Q_ESTATE, std::string(who) + " needs the reads per pair: call f2q_set_umi_reads before counting");
     HIPC(c, hipSetDevice(c->device));
-    for (int i = 0; i < F2Q_UMI_CTR_WORDS; i++) ctr[i] = 0;
-    if (c->umi.ctr) HIPC(c, hipMemcpyAsync(ctr, c->umi.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+    if (int rc = umi_read_ctr(c, ctr)) return rc;
     if (ctr[F2Q_UMI_READS] >= (1ull << 32))
         return fail(c, F2Q_EUNSUPPORTED, std::string(who) + ": 2^32 or more reads with a valid UMI -- a pair's 32-bit count may have wrapped");
     return F2Q_OK;
 }
 
 // The directional rule of UMI-tools over the same set (include/f2q.h; the rule as it is computed: DESIGN.md).  Four
-// launches on the context's stream, the kernel boundary the only hand-off; parent[slots], dom[slots], molecules[n_features]
-// and three counters are scratch from the device-memory cache.  The set, reads[], umis[] and the counters are only read.
+// launches; parent[slots], dom[slots], molecules[n_features] and three counters are scratch from the device-memory cache.
+// The set, reads[], umis[] and the counters are only read.
 extern "C" int f2q_umi_collapse_directional(f2q_ctx *c, int64_t *molecules, int64_t extra[4])
 {
     if (!c) return F2Q_EINVAL;
     unsigned long long ctr[F2Q_UMI_CTR_WORDS];
-    int rc = umi_reads_ready(c, "f2q_umi_collapse_directional", ctr);
-    if (rc) return rc;
+    if (int rc = umi_reads_ready(c, "f2q_umi_collapse_directional", ctr)) return rc;
     const double t0 = now_ms();
     const uint64_t nf = c->lib_h.n_features;
     std::vector<unsigned long long> h(nf + 3, 0ull);             // molecules, edges, flagged slots, reads
     float ms[4] = {0, 0, 0, 0};
-    uint32_t wg = F2Q_UMI_LINK_WG_DEFAULT, per_cu = F2Q_UMI_LINK_GRID_DEFAULT, glink = 0;
-    { const char *e = getenv("F2Q_UMI_LINK_WG"); if (e && atol(e) >= 64 && atol(e) <= F2Q_UMI_LINK_THREADS && atol(e) % 64 == 0) wg = (uint32_t)atol(e); }
-    { const char *e = getenv("F2Q_UMI_LINK_GRID"); if (e && atol(e) >= 1 && atol(e) <= 4096) per_cu = (uint32_t)atol(e); }
+    const UmiGeom g = umi_geometry(c, c->umi.n_slots);
+    const UmiDev &u = c->umi.dev;
     DevScope scratch(c);
-    if (c->umi.umis && c->umi.slots && c->umi.reads) {           // (nothing counted yet: all zero)
-        if (c->umi_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
+    if (u.umis && u.slots && u.reads) {                          // (nothing counted yet: all zero)
+        if (c->umi.n_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
         uint32_t *parent = nullptr, *dom = nullptr; unsigned long long *mol = nullptr;
-        if (dev_alloc(c, (size_t)c->umi_slots, &parent, scratch.v) || dev_alloc(c, (size_t)c->umi_slots, &dom, scratch.v, 0) ||
+        if (dev_alloc(c, (size_t)c->umi.n_slots, &parent, scratch.v) || dev_alloc(c, (size_t)c->umi.n_slots, &dom, scratch.v, 0) ||
             dev_alloc(c, (size_t)nf + 3, &mol, scratch.v, 0))
-            return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi_slots) + " slots: " + c->err);
-        struct Events { hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } evs;
-        hipEvent_t *ev = evs.e;                                  // F2Q_TRACE=1: the time of each launch
-        if (c->trace) for (int i = 0; i < 5; i++) HIPC(c, hipEventCreate(&ev[i]));
-        const uint32_t g256 = (uint32_t)std::min<uint64_t>((c->umi_slots + 255) / 256, (uint64_t)c->n_cu * 8u);
-        glink = (uint32_t)std::min<uint64_t>((c->umi_slots + wg - 1) / wg, (uint64_t)c->n_cu * per_cu);
-        if (ev[0]) HIPC(c, hipEventRecord(ev[0], c->stream));
-        hipLaunchKernelGGL(k_umi_uf_init, dim3(g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi_slots);
-        HIPC(c, hipGetLastError());
-        EC_POINT(c, "k_umi_uf_init");
-        if (ev[1]) HIPC(c, hipEventRecord(ev[1], c->stream));
-        hipLaunchKernelGGL(k_umi_link_dir, dim3(glink), dim3(wg), 0, c->stream, c->umi, parent, dom, mol + nf);
-        HIPC(c, hipGetLastError());
-        EC_POINT(c, "k_umi_link_dir");
-        if (ev[2]) HIPC(c, hipEventRecord(ev[2], c->stream));
-        hipLaunchKernelGGL(k_umi_dir_spread, dim3(g256), dim3(256), 0, c->stream, c->umi, (const uint32_t *)parent, dom);
-        HIPC(c, hipGetLastError());
-        EC_POINT(c, "k_umi_dir_spread");
-        if (ev[3]) HIPC(c, hipEventRecord(ev[3], c->stream));
-        hipLaunchKernelGGL(k_umi_dir_roots, dim3(g256), dim3(256), 0, c->stream, c->umi, (const uint32_t *)parent, (const uint32_t *)dom, mol, mol + nf + 1);
-        HIPC(c, hipGetLastError());
-        EC_POINT(c, "k_umi_dir_roots");
-        if (ev[4]) HIPC(c, hipEventRecord(ev[4], c->stream));
+            return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi.n_slots) + " slots: " + c->err);
+        const std::vector<UmiStage> stages = {
+            {"k_umi_uf_init", [&] { hipLaunchKernelGGL(k_umi_uf_init, dim3(g.g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi.n_slots); }},
+            {"k_umi_link_dir", [&] { hipLaunchKernelGGL(k_umi_link<true>, dim3(g.glink), dim3(g.wg), 0, c->stream, u, parent, dom, mol + nf); }},
+            {"k_umi_dir_spread", [&] { hipLaunchKernelGGL(k_umi_dir_spread, dim3(g.g256), dim3(256), 0, c->stream, u, (const uint32_t *)parent, dom); }},
+            {"k_umi_dir_roots", [&] { hipLaunchKernelGGL(k_umi_dir_roots, dim3(g.g256), dim3(256), 0, c->stream, u, (const uint32_t *)parent, (const uint32_t *)dom, mol, mol + nf + 1); }}};
+        if (int rc = umi_run_stages(c, stages, ms)) return rc;
         HIPC(c, hipMemcpyAsync(h.data(), mol, (nf + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        if (ev[4]) {
-            HIPC(c, hipEventSynchronize(ev[4]));
-            for (int i = 0; i < 4; i++) HIPC(c, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-        }
         HIPC(c, hipStreamSynchronize(c->stream));
     }
     unsigned long long total = 0;
     for (uint64_t i = 0; i < nf; i++) { total += h[i]; if (molecules) molecules[i] = (int64_t)h[i]; }
     if (extra) { extra[0] = (int64_t)ctr[F2Q_UMI_HELD]; extra[1] = (int64_t)h[nf]; extra[2] = (int64_t)h[nf + 1]; extra[3] = (int64_t)h[nf + 2]; }
     if (c->trace) fprintf(stderr, "[f2q trace] UMI collapse directional: %llu pairs, %llu edges, %llu dominated, %llu molecules, %llu reads, %.3f ms (union-find init %.3f, link %.3f, spread %.3f, roots %.3f; wave, %u x %u)\n",
-                          ctr[F2Q_UMI_HELD], h[nf], h[nf + 1], total, h[nf + 2], now_ms() - t0, ms[0], ms[1], ms[2], ms[3], glink, wg);
+                          ctr[F2Q_UMI_HELD], h[nf], h[nf + 1], total, h[nf + 2], now_ms() - t0, ms[0], ms[1], ms[2], ms[3], g.glink, g.wg);
     return F2Q_OK;
 }
 
@@ -1199,22 +1202,21 @@ extern "C" int f2q_umi_pairs(f2q_ctx *c, uint64_t cap, uint64_t *n, uint32_t *fe
 {
     if (!c || !n) return F2Q_EINVAL;
     unsigned long long ctr[F2Q_UMI_CTR_WORDS];
-    int rc = umi_reads_ready(c, "f2q_umi_pairs", ctr);
-    if (rc) return rc;
+    if (int rc = umi_reads_ready(c, "f2q_umi_pairs", ctr)) return rc;
     *n = ctr[F2Q_UMI_HELD];
     if (!feature && !codes && !reads) return F2Q_OK;
     if (cap < *n) return fail(c, F2Q_EINVAL, "f2q_umi_pairs: room for " + std::to_string(cap) + " pairs, the set holds " + std::to_string(*n));
-    if (!*n || !c->umi.slots || !c->umi.reads) return F2Q_OK;
+    if (!*n || !c->umi.dev.slots || !c->umi.dev.reads) return F2Q_OK;
     std::vector<unsigned long long> words;                       // 12 bytes per slot on the host: a failure is F2Q_ENOMEM, not an exception
     std::vector<uint32_t> cnt;
     std::vector<std::pair<unsigned long long, uint32_t>> held;
-    try { words.resize(c->umi_slots); cnt.resize(c->umi_slots); held.reserve((size_t)*n); }
-    catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy a UMI set of " + std::to_string(c->umi_slots) + " slots"); }
-    HIPC(c, hipMemcpyAsync(words.data(), c->umi.slots, c->umi_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(cnt.data(), c->umi.reads, c->umi_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    try { words.resize(c->umi.n_slots); cnt.resize(c->umi.n_slots); held.reserve((size_t)*n); }
+    catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy a UMI set of " + std::to_string(c->umi.n_slots) + " slots"); }
+    HIPC(c, hipMemcpyAsync(words.data(), c->umi.dev.slots, c->umi.n_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(cnt.data(), c->umi.dev.reads, c->umi.n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     uint64_t occupied = 0;
-    for (uint64_t i = 0; i < c->umi_slots; i++) if (words[i] != KEY_EMPTY && occupied++ < *n) held.emplace_back(words[i], cnt[i]);      // (never past the reserve)
+    for (uint64_t i = 0; i < c->umi.n_slots; i++) if (words[i] != KEY_EMPTY && occupied++ < *n) held.emplace_back(words[i], cnt[i]);      // (never past the reserve)
     if (occupied != *n) return fail(c, F2Q_EHIP, "the UMI set holds " + std::to_string(occupied) + " pairs, its counter says " + std::to_string(*n));
     std::sort(held.begin(), held.end());                         // the word is (feature << 32) | codes
     for (size_t i = 0; i < held.size(); i++) {
@@ -1246,10 +1248,10 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
     rb.first_index += c->reads_seen;
     const uint64_t wg = (rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
-    if (c->umi_on) {                                             // the same road with the (feature, UMI) set (f2q_set_umi)
+    if (c->umi.on) {                                             // the same road with the (feature, UMI) set (f2q_set_umi)
         if ((rc = umi_reserve(c, rb.n))) return rc;
-        if (c->umi.reads) hipLaunchKernelGGL(k_count_umi<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi);
-        else hipLaunchKernelGGL(k_count_umi<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi);
+        if (c->umi.dev.reads) hipLaunchKernelGGL(k_count_umi<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev);
+        else hipLaunchKernelGGL(k_count_umi<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev);
         HIPC(c, hipGetLastError());
         launches++;
         EC_POINT(c, "k_count_umi");
@@ -1391,7 +1393,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
 {
     if (!k0) { k0 = c->ev_k0; k1 = c->ev_k1; }          // (a queued step brings its own pair)
     if (c->prm.mode == 0 && !c->have_lib) return fail(c, F2Q_ESTATE, "f2q_set_features must be called before counting in Counter mode");
-    if (c->umi_on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
+    if (c->umi.on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
     c->counted = true;
     Accum acc{c->acc_d, c->acc_d + (c->acc_n - 5), nullptr, nullptr, nullptr, nullptr};
 #ifdef F2Q_STAMP
@@ -1863,7 +1865,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
 {
     if (!c) return F2Q_EINVAL;
     if (c->have_lib || c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_mate2 comes once, after f2q_create and before f2q_set_features");
-    if (c->umi_on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only");
+    if (c->umi.on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only");
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
     for (int i = 0; i < n_start2; i++) if (start2[i] < 0) return fail(c, F2Q_EINVAL, "a mate-2 window starts before the mate");
@@ -2534,7 +2536,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
 {
     if (!c || !path || world == 0 || rank >= world) return F2Q_EINVAL;
     if (int rc = single_only(c)) return rc;
-    if (c->umi_on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
+    if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     size_t CH = file_chunk_bytes((size_t)256 << 20);
     TextSource src;
@@ -2818,7 +2820,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
 {
     if (!c || !path || !census || world == 0 || rank >= world || !piece_bytes_ok(piece_bytes)) return F2Q_EINVAL;
     if (int rc = single_only(c)) return rc;
-    if (c->umi_on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
+    if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }

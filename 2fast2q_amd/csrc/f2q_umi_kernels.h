@@ -1,21 +1,21 @@
 // f2q_umi_kernels.h -- distinct UMIs per feature (--umi, f2q_set_umi; included by f2q_lib.hip only).
-//   k_count_umi    Counter mode on raw records, the byte-exact routine, plus the (feature, UMI) set: one pass
+//   k_count_umi<READS>   Counter mode on raw records, the byte-exact routine, plus the (feature, UMI) set: one pass
 //                  (<false>: the set alone; <true>: reads per pair too, f2q_set_umi_reads)
-//   k_umi_rehash / k_umi_rehash_reads   the pairs of a full set into a larger one (the second: with their reads)
-//   k_umi_uf_init / k_umi_link / k_umi_link_lane / k_umi_roots   UMIs at Hamming distance 1 collapsed per feature
+//   k_umi_rehash<READS>  the pairs of a full set into a larger one (<true>: with their reads)
+//   k_umi_uf_init / k_umi_link<false> / k_umi_link_lane / k_umi_roots   UMIs at Hamming distance 1 collapsed per feature
 //                  (f2q_umi_collapse): three launches over the set, the kernel boundary is the only hand-off
-//   k_umi_link_dir / k_umi_dir_spread / k_umi_dir_roots   the directional rule (f2q_umi_collapse_directional), after
+//   k_umi_link<true> / k_umi_dir_spread / k_umi_dir_roots   the directional rule (f2q_umi_collapse_directional), after
 //                  k_umi_uf_init: four launches
-// The per-lane logic (UmiDev, umi_insert, umi_codes, UmiHook, umi_find, uf_find / uf_union, umi_link_one, umi_root_one,
-// umi_insert_reads, UmiReadsHook, umi_link_dir_one, umi_dir_spread_one, umi_dir_root_one) lives in f2q_device.h.
+// The per-lane logic (UmiDev, umi_claim_at, umi_insert, umi_rehash_one, umi_codes, UmiHook, umi_find, uf_find / uf_union,
+// umi_neighbour, umi_link_one, umi_root_one, umi_link_dir_one, umi_dir_spread_one, umi_dir_root_one) lives in f2q_device.h.
 #pragma once
 
 // k_count_general's shape (64-thread workgroups, the record's two lines staged in LDS, a record longer than the staging
 // area walked in global memory); a read the routine assigns to a feature also brings its UMI to the set.  Single-end
 // Counter mode only (f2q_set_umi refuses everything else).  The host has sized the set so that every record of the
 // launch could bring a new pair and it would still be at most half full.
-// READS: every read with a valid UMI also adds 1 to reads[slot of its pair] (UmiReadsHook); false is the kernel as it
-// was, and the only instance launched unless f2q_set_umi_reads asked for reads.
+// READS: every read with a valid UMI also adds 1 to reads[slot of its pair] (UmiHook<P, true>); false is the only
+// instance launched unless f2q_set_umi_reads asked for reads.
 template <bool READS>
 __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi(const RunDev *__restrict__ runp, const LibDev *__restrict__ libp,
                                                                 EcDev ec, RawBlock rb, Accum acc, UmiDev umi)
@@ -38,10 +38,10 @@ __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi(const RunDev *__r
             stage_line(mine + F2Q_GEN_WORDS, raw, qo, qn);
             const uint8_t *sl = reinterpret_cast<const uint8_t *>(mine) + ms;
             const uint8_t *ql = reinterpret_cast<const uint8_t *>(mine + F2Q_GEN_WORDS) + mq;
-            const typename std::conditional<READS, UmiReadsHook<const uint8_t *>, UmiHook<const uint8_t *>>::type hook{&umi, run.thr, sl, r, ql, qn, ust};
+            const UmiHook<const uint8_t *, READS> hook{&umi, run.thr, sl, r, ql, qn, ust};
             general_read<const uint8_t *, true, false>(run, lib, ec, acc, sl, r, ql, qn, gi, st, nullptr, 0, 0, hook);
         } else {
-            const typename std::conditional<READS, UmiReadsHook<gbytes>, UmiHook<gbytes>>::type hook{&umi, run.thr, raw + so, r, raw + qo, qn, ust};
+            const UmiHook<gbytes, READS> hook{&umi, run.thr, raw + so, r, raw + qo, qn, ust};
             general_read<gbytes, true, false>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, nullptr, 0, 0, hook);
         }
     }
@@ -56,20 +56,12 @@ __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi(const RunDev *__r
     flush_stats(acc, st, st_lds, nullptr);
 }
 
-// every pair of `old` into `nw` (empty, with room for them all); umis[] and the counters are shared and stay as they are
+// every pair of `old` into `nw` (umi_rehash_one); READS: with its reads
+template <bool READS>
 __global__ __launch_bounds__(256) void k_umi_rehash(UmiDev old, UmiDev nw)
 {
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > old.mask) return;
-    const unsigned long long k = gp(old.slots)[i];
-    if (k != KEY_EMPTY) (void)umi_claim(nw, k);
-}
-
-// the same with reads kept: nw.reads[] is zeroed, every pair takes its count along
-__global__ __launch_bounds__(256) void k_umi_rehash_reads(UmiDev old, UmiDev nw)
-{
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= old.mask) umi_rehash_reads_one(old, nw, (uint32_t)i);
+    if (i <= old.mask) umi_rehash_one<READS>(old, nw, (uint32_t)i);
 }
 
 // ---- f2q_umi_collapse: a union-find over the slots of the set --------------------------------------------------------
@@ -88,9 +80,15 @@ __global__ __launch_bounds__(256) void k_umi_uf_init(uint32_t *parent, unsigned 
 #define F2Q_UMI_LINK_THREADS 256
 #define F2Q_UMI_LINK_WG_DEFAULT 256
 #define F2Q_UMI_LINK_GRID_DEFAULT 8
-__global__ __launch_bounds__(F2Q_UMI_LINK_THREADS) void k_umi_link(UmiDev u, uint32_t *parent, unsigned long long *edges)
+// DIR: the directional rule (f2q_umi_collapse_directional) -- the pair's reads travel next to its word in the wave's row
+// (cnts; one row in the other instance, never touched) and dom[] (null otherwise) takes the flags.  slots[] and reads[]
+// are written by earlier launches only (plain loads); parent[] is accessed by agent-scope atomics inside uf_union;
+// dom[] is only written here (F2Q_ST32, every writer stores the same 1) and read by the launches after this one.
+template <bool DIR>
+__global__ __launch_bounds__(F2Q_UMI_LINK_THREADS) void k_umi_link(UmiDev u, uint32_t *parent, uint32_t *dom, unsigned long long *edges)
 {
     __shared__ unsigned long long keys[F2Q_UMI_LINK_THREADS / 64][64];
+    __shared__ uint32_t cnts[DIR ? F2Q_UMI_LINK_THREADS / 64 : 1][64];
     __shared__ uint8_t from[F2Q_UMI_LINK_THREADS / 64][64];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
     const uint32_t per = 3u * (uint32_t)u.length, groups = 64u / per;
@@ -104,12 +102,17 @@ __global__ __launch_bounds__(F2Q_UMI_LINK_THREADS) void k_umi_link(UmiDev u, uin
         if (k != KEY_EMPTY) {
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(occ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)occ, 0u));
             keys[wave][rank] = k; from[wave][rank] = (uint8_t)lane;
+            if (DIR) cnts[wave][rank] = gp(u.reads)[base + lane];
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         const uint32_t cnt = (uint32_t)__popcll(occ);
         for (uint32_t t = 0; t < cnt; t += groups) {
             const uint32_t q = t + g;
-            if (g < groups && q < cnt) found += umi_link_one(u, parent, (uint32_t)base + from[wave][q], keys[wave][q], n);
+            if (g < groups && q < cnt) {
+                const uint32_t i = (uint32_t)base + from[wave][q];
+                if (DIR) found += umi_link_dir_one(u, parent, dom, i, keys[wave][q], cnts[wave][q], n);
+                else found += umi_link_one(u, parent, i, keys[wave][q], n);
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
@@ -141,40 +144,7 @@ __global__ __launch_bounds__(256) void k_umi_roots(UmiDev u, uint32_t *parent, u
 }
 
 // ---- f2q_umi_collapse_directional -------------------------------------------------------------------------------------
-// k_umi_link's layout with the pair's reads next to its word in the wave's row.  slots[] and reads[] are written by
-// earlier launches only (plain loads); parent[] is accessed as in k_umi_link (agent-scope atomics inside uf_union);
-// dom[] is only written here (F2Q_ST32, every writer stores the same 1) and read by the launches after this one.
-__global__ __launch_bounds__(F2Q_UMI_LINK_THREADS) void k_umi_link_dir(UmiDev u, uint32_t *parent, uint32_t *dom, unsigned long long *edges)
-{
-    __shared__ unsigned long long keys[F2Q_UMI_LINK_THREADS / 64][64];
-    __shared__ uint32_t cnts[F2Q_UMI_LINK_THREADS / 64][64];
-    __shared__ uint8_t from[F2Q_UMI_LINK_THREADS / 64][64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-    const uint32_t per = 3u * (uint32_t)u.length, groups = 64u / per;
-    const uint32_t g = lane / per, n = lane - g * per;
-    const unsigned long long slots = (unsigned long long)u.mask + 1ull;
-    unsigned long long found = 0;
-    for (unsigned long long base = ((unsigned long long)blockIdx.x * waves + wave) * 64ull; base < slots; base += (unsigned long long)gridDim.x * waves * 64ull) {
-        const unsigned long long k = base + lane < slots ? gp(u.slots)[base + lane] : KEY_EMPTY;
-        const unsigned long long occ = __ballot(k != KEY_EMPTY);
-        if (occ == 0ull) continue;
-        if (k != KEY_EMPTY) {
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(occ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)occ, 0u));
-            keys[wave][rank] = k; cnts[wave][rank] = gp(u.reads)[base + lane]; from[wave][rank] = (uint8_t)lane;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const uint32_t cnt = (uint32_t)__popcll(occ);
-        for (uint32_t t = 0; t < cnt; t += groups) {
-            const uint32_t q = t + g;
-            if (g < groups && q < cnt) found += umi_link_dir_one(u, parent, dom, (uint32_t)base + from[wave][q], keys[wave][q], cnts[wave][q], n);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    }
-    found = wave_sum(found);
-    if (lane == 0 && found) acc_add(edges, found);
-}
-
-// after k_umi_link_dir has ended: parent[] is stable, so is bit 0 of every dom[].  A dominated single-read slot that is
+// after k_umi_link<true> has ended: parent[] is stable, so is bit 0 of every dom[].  A dominated single-read slot that is
 // not its own root ORs bit 1 into dom[root].  Only roots are written and only the flags of slots that are no roots decide
 // anything here, so no lane reads what another lane of this launch writes; k_umi_dir_roots reads the result.
 __global__ __launch_bounds__(256) void k_umi_dir_spread(UmiDev u, const uint32_t *parent, uint32_t *dom)

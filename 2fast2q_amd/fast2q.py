@@ -258,14 +258,16 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             param.setdefault('assigned', {})[raw] = ([int(n) for n in acounts], ctx.ec_assigned())
         if param.get('umi'):                        # distinct UMIs per feature and the two sample-level counters (f2q_read_umis)
             umis, umi_reads, umi_failed = ctx.read_umis()
-            param.setdefault('umi_counted', {})[raw] = ([int(n) for n in umis], umi_reads, umi_failed)
+            # the sample's record: per kind of UMI_TABLES that was computed, a number per feature and the sample-level counters
+            rec = param.setdefault('umi_counted', {})[raw] = {"umis": ([int(n) for n in umis], dict(umi_reads=umi_reads, umi_failed=umi_failed))}
             if param.get('umi_mismatch'):           # --mu 1: UMIs of a feature one base apart joined (f2q_umi_collapse)
                 molecules, pairs, edges = ctx.collapse_umis(param['umi_mismatch'])
-                param.setdefault('umi_collapsed', {})[raw] = ([int(n) for n in molecules], pairs, edges)
+                rec["molecules"] = ([int(n) for n in molecules], dict(umi_pairs=pairs, umi_edges=edges, umi_molecules=int(sum(molecules))))
             if param.get('umi_rule') == 'directional':      # --mur directional: the directional rule on the same set, and its pairs
                 molecules, pairs, edges, dominated, reads = ctx.collapse_umis_directional()
-                table = ctx.umi_pairs() if not param.get("delete", True) else None
-                param.setdefault('umi_directional', {})[raw] = ([int(n) for n in molecules], pairs, edges, dominated, reads, table)
+                rec["directional"] = ([int(n) for n in molecules], dict(umi_pairs=pairs, umi_edges=edges, umi_dominated=dominated,
+                                                                        umi_molecules=int(sum(molecules)), umi_pair_reads=reads))
+                rec["pair_table"] = ctx.umi_pairs() if not param.get("delete", True) else None
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -343,29 +345,18 @@ def aligner(i, raw, features, param, reads_stats):
             csv_writer(os.path.join(param["directory"], sample.name + "_assigned.csv"),
                        [["#key", "reads", "feature_name", "mismatches"]] +
                        [[key, n, names[f] if f >= 0 else "", d] for key, n, _first, f, d in arows])
-    if raw in param.get('umi_counted', {}):          # --umi: the same rows holding distinct UMIs instead of reads
-        umis, umi_reads, umi_failed = param['umi_counted'].pop(raw)
+    if raw in param.get('umi_counted', {}):          # --umi: the same rows once per kind, holding UMIs / molecules instead of reads
+        rec = param['umi_counted'].pop(raw)
+        pair_table = rec.pop("pair_table", None)
         names = [f.name for f in features.values()]
-        param.setdefault("umi_samples", {})[sample.name] = SampleResult(sample.name, value, unit, _sample_rows(zip(names, umis)),
-                                                                        dict(local, umi_reads=umi_reads, umi_failed=umi_failed))
-        molecules = None
-        if raw in param.get('umi_collapsed', {}):    # --mu 1: the same rows again, holding molecules
-            molecules, pairs, edges = param['umi_collapsed'].pop(raw)
-            param.setdefault("umi_collapsed_samples", {})[sample.name] = SampleResult(
-                sample.name, value, unit, _sample_rows(zip(names, molecules)), dict(local, umi_pairs=pairs, umi_edges=edges, umi_molecules=sum(molecules)))
-        directional = pair_table = None
-        if raw in param.get('umi_directional', {}):  # --mur directional: and again, holding molecules by the directional rule
-            directional, pairs, edges, dominated, reads, pair_table = param['umi_directional'].pop(raw)
-            param.setdefault("umi_directional_samples", {})[sample.name] = SampleResult(
-                sample.name, value, unit, _sample_rows(zip(names, directional)),
-                dict(local, umi_pairs=pairs, umi_edges=edges, umi_dominated=dominated, umi_molecules=sum(directional), umi_pair_reads=reads))
+        param.setdefault("umi_samples", {})[sample.name] = {
+            kind: SampleResult(sample.name, value, unit, _sample_rows(zip(names, column)), dict(local, **stats)) for kind, (column, stats) in rec.items()}
         if not param.get("delete", True) and sharding.world().rank == 0:
             os.makedirs(param["directory"], exist_ok=True)
-            cols = [umis] + [c for c in (molecules, directional) if c is not None]
-            both = _sample_rows((f.name, (f.counts,) + tuple(ns)) for f, ns in zip(features.values(), zip(*cols)))      # (the order of `rows`)
+            kinds = [t for t in UMI_TABLES if t[0] in rec]
+            both = _sample_rows((f.name, (f.counts,) + tuple(ns)) for f, ns in zip(features.values(), zip(*(rec[t[0]][0] for t in kinds))))  # (the order of `rows`)
             csv_writer(os.path.join(param["directory"], sample.name + "_umi_reads.csv"),
-                       [["#Feature", "Reads", "UMIs"] + (["Molecules"] if molecules is not None else []) + (["Directional"] if directional is not None else [])] +
-                       [[name, *ns] for name, ns in both])
+                       [["#Feature", "Reads"] + [t[2] for t in kinds]] + [[name, *ns] for name, ns in both])
             if pair_table is not None:               # every (feature, UMI) pair with its reads, in f2q_umi_pairs' order
                 length = param['umi'][1]
                 csv_writer(os.path.join(param["directory"], sample.name + "_umi_pairs.csv"),
@@ -758,18 +749,12 @@ def compiling(param):
         _, ahead, atable = compile_table(param["assign_samples"])
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_features.csv"),
                    [ahead] + [[feature] + counts for feature, counts in atable.items()])
-    if param.get("umi_samples"):                     # --umi: <name>.csv's layout and row order, distinct UMIs instead of reads
-        _, uhead, utable = compile_table(param["umi_samples"])
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_umi.csv"),
-                   [uhead] + [[feature] + counts for feature, counts in utable.items()])
-    if param.get("umi_collapsed_samples"):           # --mu 1: the same table again, holding molecules
-        _, chead, ctable = compile_table(param["umi_collapsed_samples"])
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_umi_collapsed.csv"),
-                   [chead] + [[feature] + counts for feature, counts in ctable.items()])
-    if param.get("umi_directional_samples"):         # --mur directional: and again, molecules by the directional rule
-        _, dhead, dtable = compile_table(param["umi_directional_samples"])
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_umi_directional.csv"),
-                   [dhead] + [[feature] + counts for feature, counts in dtable.items()])
+    for kind, suffix, _, _, _ in UMI_TABLES:         # --umi / --mu 1 / --mur directional: <name>.csv's layout and row order per kind
+        per_sample = {name: rec[kind] for name, rec in param.get("umi_samples", {}).items() if kind in rec}
+        if per_sample:
+            _, uhead, utable = compile_table(per_sample)
+            csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}{suffix}.csv"),
+                       [uhead] + [[feature] + counts for feature, counts in utable.items()])
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -791,6 +776,13 @@ UMI_COLLAPSE_STATS_HEAD = ["#Sample name (UMI collapsed)", "Number of distinct (
                            "Number of molecules"]
 UMI_DIRECTIONAL_STATS_HEAD = ["#Sample name (UMI directional)", "Number of distinct (feature, UMI) pairs", "Number of pairs of them that differ in one base",
                               "Number of pairs a neighbour absorbs directly", "Number of molecules", "Number of reads of all pairs"]
+# what a UMI run reports, one record per sample (param["umi_samples"][name][kind], a SampleResult): kind, suffix of the run's
+# table, column of <sample>_umi_reads.csv, head and counters of its block of <name>_stats.csv.  --umi gives the first,
+# --mu 1 the second, --mur directional the third
+UMI_TABLES = (("umis", "_umi", "UMIs", UMI_STATS_HEAD, ("umi_reads", "umi_failed")),
+              ("molecules", "_umi_collapsed", "Molecules", UMI_COLLAPSE_STATS_HEAD, ("umi_pairs", "umi_edges", "umi_molecules")),
+              ("directional", "_umi_directional", "Directional", UMI_DIRECTIONAL_STATS_HEAD,
+               ("umi_pairs", "umi_edges", "umi_dominated", "umi_molecules", "umi_pair_reads")))
 
 
 def run_stats(headers, param, compiled, head, ordered):
@@ -800,16 +792,10 @@ def run_stats(headers, param, compiled, head, ordered):
              s.stats["perfect_counter"], s.stats["imperfect_counter"], s.stats["non_aligned_counter"],
              s.stats["quality_failed"]] for s in ordered]
     global_stat = [[line] for line in headers] + [STATS_HEAD] + rows
-    if param.get("umi_samples"):                     # --umi: the two sample-level counters, one line per sample
-        global_stat += [UMI_STATS_HEAD] + [[s.name, u.stats["umi_reads"], u.stats["umi_failed"]]
-                                           for s in ordered for u in [param["umi_samples"].get(s.name)] if u is not None]
-    if param.get("umi_collapsed_samples"):           # --mu 1: pairs, edges and molecules, one line per sample
-        global_stat += [UMI_COLLAPSE_STATS_HEAD] + [[s.name, u.stats["umi_pairs"], u.stats["umi_edges"], u.stats["umi_molecules"]]
-                                                    for s in ordered for u in [param["umi_collapsed_samples"].get(s.name)] if u is not None]
-    if param.get("umi_directional_samples"):         # --mur directional: sample, pairs, edges, dominated, molecules, reads
-        global_stat += [UMI_DIRECTIONAL_STATS_HEAD] + [[s.name, u.stats["umi_pairs"], u.stats["umi_edges"], u.stats["umi_dominated"], u.stats["umi_molecules"],
-                                                        u.stats["umi_pair_reads"]]
-                                                       for s in ordered for u in [param["umi_directional_samples"].get(s.name)] if u is not None]
+    umi = param.get("umi_samples", {})
+    for kind, _, _, stats_head, columns in UMI_TABLES:       # per kind: its head, then one line of counters per sample
+        if any(kind in rec for rec in umi.values()):
+            global_stat += [stats_head] + [[s.name] + [umi[s.name][kind].stats[c] for c in columns] for s in ordered if kind in umi.get(s.name, {})]
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib

@@ -1,81 +1,19 @@
-// tests/emu/f2q_umi_dir_emu.cpp -- TEST INFRASTRUCTURE.  The per-lane logic of reads per (feature, UMI) pair and of
-// f2q_umi_collapse_directional (umi_claim_at / umi_read_add / umi_insert_reads / UmiReadsHook, umi_rehash_reads_one,
-// umi_link_dir_one, umi_dir_spread_one, umi_dir_root_one of 2fast2q_amd/csrc/f2q_device.h) compiled with g++ and run over
-// the emulated set of f2q_umi_emu.cpp (included through f2q_umi_collapse_emu.cpp, whose cluster pass serves the
-// comparisons): what k_count_umi<true>, k_umi_rehash_reads, k_umi_link_dir, k_umi_dir_spread and k_umi_dir_roots do, one
-// lane at a time, with umi_reserve's rule for reads[] (allocated zeroed with the set, filled by the rehash).  The product
-// never uses this file.
+// tests/emu/f2q_umi_dir_emu.cpp -- TEST INFRASTRUCTURE.  The per-lane logic of f2q_umi_collapse_directional
+// (umi_link_dir_one, umi_dir_spread_one, umi_dir_root_one of 2fast2q_amd/csrc/f2q_device.h) compiled with g++ and run over
+// the emulated set of f2q_umi_emu.cpp with reads kept (included through f2q_umi_collapse_emu.cpp, whose cluster pass
+// serves the comparisons): what k_umi_link<true>, k_umi_dir_spread and k_umi_dir_roots do, one lane at a time.  The
+// product never uses this file.
 // -DF2Q_UMI_DIR_EMU_MAIN: a stand-alone program over known answers (for -fsanitize=address,undefined builds).
 #include "f2q_umi_collapse_emu.cpp"
 
-struct DEmu {
-    UEmu *x = nullptr;
-    std::vector<uint32_t> reads;
-};
-
-// uemu_reserve with reads kept: the new reads[] zeroed, every pair of the old set takes its count along
-static void demu_reserve(DEmu *d, uint64_t n)
-{
-    UEmu *x = d->x;
-    const uint64_t held = x->ctr[F2Q_UMI_HELD];
-    if (!x->slots.empty() && 2 * (held + n) <= x->slots.size()) return;
-    uint64_t slots = std::max<uint64_t>(x->min_slots, 2);
-    while (slots < 2 * (held + n) || slots < 4 * held) slots <<= 1;
-    std::vector<unsigned long long> fresh(slots, KEY_EMPTY);
-    std::vector<uint32_t> fresh_reads(slots, 0u);
-    UmiDev nw = x->u; nw.slots = fresh.data(); nw.reads = fresh_reads.data(); nw.mask = (uint32_t)(slots - 1);
-    if (held) {
-        for (uint32_t i = 0; i < (uint32_t)x->slots.size(); i++) umi_rehash_reads_one(x->u, nw, i);
-        x->rehashes++;
-    }
-    x->slots.swap(fresh); d->reads.swap(fresh_reads);
-    x->u.slots = x->slots.data(); x->u.reads = d->reads.data(); x->u.mask = nw.mask;
-}
-
 extern "C" {
 
+// uemu_create with reads kept per pair (f2q_set_umi_reads); every uemu_* call takes the handle
 void *demu_create(const f2q_params *p, int32_t start, int32_t length, uint64_t min_slots)
 {
     UEmu *x = (UEmu *)uemu_create(p, start, length, min_slots);
-    if (!x) return nullptr;
-    DEmu *d = new DEmu();
-    d->x = x;
-    return d;
-}
-void demu_destroy(void *h) { DEmu *d = (DEmu *)h; uemu_destroy(d->x); delete d; }
-void *demu_set(void *h) { return ((DEmu *)h)->x; }                   // the UEmu inside, for uemu_read / uemu_collapse / uemu_set_info
-
-void demu_set_features(void *h, const char *seqs, const uint32_t *offs, uint32_t n)
-{
-    DEmu *d = (DEmu *)h;
-    uemu_set_features(d->x, seqs, offs, n);
-    d->reads.clear(); d->x->u.reads = nullptr;
-}
-
-// every record through the byte-exact routine with the reads-keeping hook (what a lane of k_count_umi<true> does)
-size_t demu_count_block(void *h, const uint8_t *buf, size_t n)
-{
-    DEmu *d = (DEmu *)h; UEmu *x = d->x; Emu *e = x->e;
-    std::vector<Rec> recs;
-    const size_t used = frame_fastq(buf, n, recs);
-    demu_reserve(d, recs.size());
-    Accum acc{e->acc.data(), e->acc.data() + e->ix.n_features, nullptr, nullptr, nullptr, nullptr};
-    for (size_t i = 0; i < recs.size(); i++) {
-        unsigned long long ust[3] = {0, 0, 0};
-        const UmiReadsHook<const uint8_t *> hook{&x->u, e->run.thr, recs[i].seq, (int)recs[i].len, recs[i].qual, (int)recs[i].qlen, ust};
-        general_read<const uint8_t *, true, false>(e->run, e->lib, e->ec, acc, recs[i].seq, (int)recs[i].len, recs[i].qual, (int)recs[i].qlen,
-                                                   e->reads_seen + i, acc.stats, nullptr, 0, 0, hook);
-        x->ctr[F2Q_UMI_READS] += ust[0]; x->ctr[F2Q_UMI_FAILED] += ust[1]; x->ctr[F2Q_UMI_HELD] += ust[2];
-    }
-    e->reads_seen += recs.size(); e->general += recs.size();
-    return used;
-}
-
-void demu_reset(void *h)
-{
-    DEmu *d = (DEmu *)h;
-    uemu_reset(d->x);
-    std::fill(d->reads.begin(), d->reads.end(), 0u);
+    if (x) x->keep_reads = true;
+    return x;
 }
 
 // molecules[n_features], extra[4] = pairs held, unordered Hamming-1 pairs, slots the link flagged, sum of reads.  order
@@ -83,7 +21,7 @@ void demu_reset(void *h)
 // (the result does not depend on it).  0, or -2 when the forest's invariant is broken
 int demu_directional(void *h, int32_t order, int64_t *molecules, int64_t *extra)
 {
-    DEmu *d = (DEmu *)h; UEmu *x = d->x;
+    UEmu *x = (UEmu *)h;
     const uint32_t nf = x->e->ix.n_features;
     for (uint32_t f = 0; f < nf; f++) molecules[f] = 0;
     extra[0] = (int64_t)x->ctr[F2Q_UMI_HELD]; extra[1] = extra[2] = extra[3] = 0;
@@ -99,7 +37,7 @@ int demu_directional(void *h, int32_t order, int64_t *molecules, int64_t *extra)
     for (uint32_t i : visit) {
         const unsigned long long k = x->slots[i];
         if (k == KEY_EMPTY) continue;
-        for (uint32_t n = 0; n < per; n++) extra[1] += umi_link_dir_one(x->u, parent.data(), dom.data(), i, k, d->reads[i], n);
+        for (uint32_t n = 0; n < per; n++) extra[1] += umi_link_dir_one(x->u, parent.data(), dom.data(), i, k, x->reads[i], n);
     }
     for (uint32_t i = 0; i < slots; i++) if (parent[i] > i) return -2;
     for (uint32_t i : visit) umi_dir_spread_one(x->u, parent.data(), dom.data(), i);
@@ -113,13 +51,13 @@ int demu_directional(void *h, int32_t order, int64_t *molecules, int64_t *extra)
 // the pairs with their reads sorted by (feature, codes), and the slot each sits in; returns how many (arrays may be null)
 uint64_t demu_pairs(void *h, uint64_t cap, uint32_t *feature, uint32_t *codes, uint32_t *reads, uint32_t *slot)
 {
-    DEmu *d = (DEmu *)h; UEmu *x = d->x;
+    UEmu *x = (UEmu *)h;
     std::vector<std::pair<unsigned long long, uint32_t>> held;
     for (uint32_t i = 0; i < (uint32_t)x->slots.size(); i++) if (x->slots[i] != KEY_EMPTY) held.emplace_back(x->slots[i], i);
     std::sort(held.begin(), held.end());
     if (feature) for (size_t i = 0; i < held.size() && i < cap; i++) {
         feature[i] = (uint32_t)(held[i].first >> 32); codes[i] = (uint32_t)held[i].first;
-        reads[i] = d->reads[held[i].second]; slot[i] = held[i].second;
+        reads[i] = x->reads[held[i].second]; slot[i] = held[i].second;
     }
     return held.size();
 }
@@ -149,7 +87,7 @@ int main()
     for (size_t i = reads.size() - 1; i > 0; i--) std::swap(reads[i], reads[rnd() % (i + 1)]);
     void *h = demu_create(&p, GL, 4, 8);
     if (!h) return 2;
-    demu_set_features(h, seqs.data(), offs.data(), NG);
+    uemu_set_features(h, seqs.data(), offs.data(), NG);
     std::vector<int64_t> mol(NG, -1), cl(NG, -1); int64_t extra[4], ce[2];
     if (demu_directional(h, 0, mol.data(), extra) != 0) return 3;                 // nothing counted yet
     bool ok = extra[0] == 0 && extra[1] == 0 && extra[2] == 0 && extra[3] == 0;
@@ -160,24 +98,24 @@ int main()
             const std::string s = seqs.substr((size_t)reads[i].first * GL, GL) + reads[i].second + "ACGTACGTAC";
             fq += "@r\n" + s + "\n+\n" + std::string(s.size(), 'I') + "\n";
         }
-        if (demu_count_block(h, (const uint8_t *)fq.data(), fq.size()) != fq.size()) return 4;
+        if (uemu_count_block(h, (const uint8_t *)fq.data(), fq.size()) != fq.size()) return 4;
     }
     for (int order = 0; order < 4; order++) {
         if (demu_directional(h, order, mol.data(), extra) != 0) return 5;
-        if (uemu_collapse(demu_set(h), 1, 0, cl.data(), ce) != 0) return 6;
+        if (uemu_collapse(h, 1, 0, cl.data(), ce) != 0) return 6;
         for (int g = 0; g < NG; g++) ok = ok && mol[g] == want[g] && cl[g] == want_cluster[g];
         ok = ok && extra[0] == 17 && extra[1] == ce[1] && extra[2] == 4 && extra[3] == total && ce[0] == 17;
         printf("order %d: molecules %lld %lld %lld %lld %lld %lld %lld, pairs %lld, edges %lld, dominated %lld, reads %lld, rehashes %llu\n", order,
                (long long)mol[0], (long long)mol[1], (long long)mol[2], (long long)mol[3], (long long)mol[4], (long long)mol[5], (long long)mol[6],
-               (long long)extra[0], (long long)extra[1], (long long)extra[2], (long long)extra[3], (unsigned long long)((UEmu *)demu_set(h))->rehashes);
+               (long long)extra[0], (long long)extra[1], (long long)extra[2], (long long)extra[3], (unsigned long long)((UEmu *)h)->rehashes);
     }
-    ok = ok && ((UEmu *)demu_set(h))->rehashes >= 1;
+    ok = ok && ((UEmu *)h)->rehashes >= 1;
     std::vector<uint32_t> f(17), c(17), r(17), s(17);
     ok = ok && demu_pairs(h, 17, f.data(), c.data(), r.data(), s.data()) == 17 && f[0] == 0 && c[0] == 0 && r[0] == 10;
-    demu_reset(h);
+    uemu_reset(h);
     if (demu_directional(h, 0, mol.data(), extra) != 0) return 7;
     ok = ok && extra[0] == 0 && extra[3] == 0;
-    demu_destroy(h);
+    uemu_destroy(h);
     return ok ? 0 : 1;
 }
 #endif

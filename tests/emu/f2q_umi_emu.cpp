@@ -1,8 +1,9 @@
 // tests/emu/f2q_umi_emu.cpp -- TEST INFRASTRUCTURE.  The per-lane logic of k_count_umi (general_read with a UmiHook,
 // umi_codes / umi_insert / umi_claim of 2fast2q_amd/csrc/f2q_device.h) compiled with g++ and run record by record over
 // the existing emulation (f2q_emu.cpp, included whole), with the host's sizing rule (umi_reserve of f2q_lib.hip: at most
-// half full after a block in which every record brings a new pair; growth re-inserts the pairs, as k_umi_rehash does),
-// so the CPU suite can check it against the oracle.  The product never uses this file.
+// half full after a block in which every record brings a new pair; growth is umi_rehash_one over every slot, as in
+// k_umi_rehash; with reads kept, reads[] is allocated zeroed with the set and filled by the rehash), so the CPU suite can
+// check it against the oracle.  The product never uses this file.
 // -DF2Q_UMI_EMU_MAIN: a stand-alone program over a built-in sample (for -fsanitize=address,undefined builds).
 #include "f2q_emu.cpp"
 
@@ -10,6 +11,8 @@ struct UEmu {
     Emu *e = nullptr;
     UmiDev u{};
     std::vector<unsigned long long> slots, umis, ctr;
+    std::vector<uint32_t> reads;                                     // keep_reads: parallel to slots (k_count_umi<true>)
+    bool keep_reads = false;
     uint64_t min_slots = 1u << 16, rehashes = 0;
 };
 
@@ -17,8 +20,8 @@ static void uemu_bind(UEmu *x)
 {
     x->umis.assign(std::max<size_t>(x->e->ix.n_features, 1), 0ull);
     x->ctr.assign(F2Q_UMI_CTR_WORDS, 0ull);
-    x->slots.clear();
-    x->u.slots = nullptr; x->u.mask = 0; x->u.umis = x->umis.data(); x->u.ctr = x->ctr.data();
+    x->slots.clear(); x->reads.clear();
+    x->u.slots = nullptr; x->u.reads = nullptr; x->u.mask = 0; x->u.umis = x->umis.data(); x->u.ctr = x->ctr.data();
 }
 
 // room for n more pairs at a load of at most one half
@@ -29,13 +32,34 @@ static void uemu_reserve(UEmu *x, uint64_t n)
     uint64_t slots = std::max<uint64_t>(x->min_slots, 2);
     while (slots < 2 * (held + n) || slots < 4 * held) slots <<= 1;
     std::vector<unsigned long long> fresh(slots, KEY_EMPTY);
-    UmiDev nw = x->u; nw.slots = fresh.data(); nw.mask = (uint32_t)(slots - 1);
+    std::vector<uint32_t> fresh_reads(x->keep_reads ? slots : 0, 0u);
+    UmiDev nw = x->u; nw.slots = fresh.data(); nw.reads = x->keep_reads ? fresh_reads.data() : nullptr; nw.mask = (uint32_t)(slots - 1);
     if (held) {
-        for (unsigned long long k : x->slots) if (k != KEY_EMPTY) (void)umi_claim(nw, k);
+        for (uint32_t i = 0; i < (uint32_t)x->slots.size(); i++) { if (x->keep_reads) umi_rehash_one<true>(x->u, nw, i); else umi_rehash_one<false>(x->u, nw, i); }
         x->rehashes++;
     }
-    x->slots.swap(fresh);
-    x->u.slots = x->slots.data(); x->u.mask = nw.mask;
+    x->slots.swap(fresh); x->reads.swap(fresh_reads);
+    x->u.slots = x->slots.data(); x->u.reads = x->keep_reads ? x->reads.data() : nullptr; x->u.mask = nw.mask;
+}
+
+// every record through the byte-exact routine with the UMI hook (what a lane of k_count_umi<READS> does)
+template <bool READS>
+static size_t uemu_count(UEmu *x, const uint8_t *buf, size_t n)
+{
+    Emu *e = x->e;
+    std::vector<Rec> recs;
+    const size_t used = frame_fastq(buf, n, recs);
+    uemu_reserve(x, recs.size());
+    Accum acc{e->acc.data(), e->acc.data() + e->ix.n_features, nullptr, nullptr, nullptr, nullptr};
+    for (size_t i = 0; i < recs.size(); i++) {
+        unsigned long long ust[3] = {0, 0, 0};
+        const UmiHook<const uint8_t *, READS> hook{&x->u, e->run.thr, recs[i].seq, (int)recs[i].len, recs[i].qual, (int)recs[i].qlen, ust};
+        general_read<const uint8_t *, true, false>(e->run, e->lib, e->ec, acc, recs[i].seq, (int)recs[i].len, recs[i].qual, (int)recs[i].qlen,
+                                                   e->reads_seen + i, acc.stats, nullptr, 0, 0, hook);
+        x->ctr[F2Q_UMI_READS] += ust[0]; x->ctr[F2Q_UMI_FAILED] += ust[1]; x->ctr[F2Q_UMI_HELD] += ust[2];
+    }
+    e->reads_seen += recs.size(); e->general += recs.size();
+    return used;
 }
 
 extern "C" {
@@ -60,23 +84,10 @@ void uemu_set_features(void *h, const char *seqs, const uint32_t *offs, uint32_t
     uemu_bind(x);
 }
 
-// every record through the byte-exact routine with the UMI hook (what a lane of k_count_umi does)
 size_t uemu_count_block(void *h, const uint8_t *buf, size_t n)
 {
-    UEmu *x = (UEmu *)h; Emu *e = x->e;
-    std::vector<Rec> recs;
-    const size_t used = frame_fastq(buf, n, recs);
-    uemu_reserve(x, recs.size());
-    Accum acc{e->acc.data(), e->acc.data() + e->ix.n_features, nullptr, nullptr, nullptr, nullptr};
-    for (size_t i = 0; i < recs.size(); i++) {
-        unsigned long long ust[3] = {0, 0, 0};
-        const UmiHook<const uint8_t *> hook{&x->u, e->run.thr, recs[i].seq, (int)recs[i].len, recs[i].qual, (int)recs[i].qlen, ust};
-        general_read<const uint8_t *, true, false>(e->run, e->lib, e->ec, acc, recs[i].seq, (int)recs[i].len, recs[i].qual, (int)recs[i].qlen,
-                                                   e->reads_seen + i, acc.stats, nullptr, 0, 0, hook);
-        x->ctr[F2Q_UMI_READS] += ust[0]; x->ctr[F2Q_UMI_FAILED] += ust[1]; x->ctr[F2Q_UMI_HELD] += ust[2];
-    }
-    e->reads_seen += recs.size(); e->general += recs.size();
-    return used;
+    UEmu *x = (UEmu *)h;
+    return x->keep_reads ? uemu_count<true>(x, buf, n) : uemu_count<false>(x, buf, n);
 }
 
 // counts[n], stats[5], umis[n], extra[2]; returns the rehashes so far, -1 when the overflow flag is set
@@ -101,6 +112,7 @@ void uemu_reset(void *h)
     UEmu *x = (UEmu *)h;
     emu_reset(x->e);
     std::fill(x->slots.begin(), x->slots.end(), KEY_EMPTY);
+    std::fill(x->reads.begin(), x->reads.end(), 0u);
     std::fill(x->umis.begin(), x->umis.end(), 0ull);
     std::fill(x->ctr.begin(), x->ctr.end(), 0ull);
 }

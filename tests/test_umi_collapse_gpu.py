@@ -65,6 +65,49 @@ def test_sixteen_base_umis_next_to_wide_feature_indices(P):
     assert sum(got[0][:512]) == 0 and got[2] > 0 and any(m < n for m, n in zip(got[0], umis))
 
 
+# F2Q_UMI_LINK_WG, F2Q_UMI_LINK_GRID -> the workgroup size the linking launch must take (None: unset; 96 is no whole
+# number of waves and 0 no grid: the default for both)
+GEOMETRIES = [(None, None, 256), ("64", "1", 64), ("128", "2", 128), ("96", "0", 256)]
+
+
+def set_geometry(monkeypatch, wg, grid):
+    monkeypatch.setenv("F2Q_TRACE", "1")
+    for key, value in (("F2Q_UMI_LINK_WG", wg), ("F2Q_UMI_LINK_GRID", grid)):
+        if value is None:
+            monkeypatch.delenv(key, raising=False)
+        else:
+            monkeypatch.setenv(key, value)
+
+
+@pytest.mark.parametrize("wg,grid,used", GEOMETRIES)
+@pytest.mark.parametrize("name", ["short1", "wide"])
+def test_launch_geometry(P, monkeypatch, capfd, name, wg, grid, used):
+    """the linking launch under every geometry the switches can give, on the shapes that bound 3L: one-base UMIs (3L = 3:
+    21 groups a round, lane 63 idle) and sixteen-base ones (3L = 48: one group, 16 lanes idle).  The first set has
+    65 536 slots: 64 x 1 strides over it many times (at most 1 024 workgroups of one wave would cover it once, and the
+    grid is one per CU)"""
+    set_geometry(monkeypatch, wg, grid)
+    got, _ = collapsed(P, name)
+    assert got == CC.expected(name)
+    tails = re.findall(r"\[f2q trace\] UMI collapse: (\d+) pairs, (\d+) edges, (\d+) molecules, [\d.]+ ms \([^;]*; wave, (\d+) x (\d+)\)", capfd.readouterr().err)
+    assert len(tails) == 3 and tails[2][3:] == ("0", str(used))      # (the third call is the identity case: no launch)
+    for pairs, edges, molecules, glink, wgsize in tails[:2]:
+        assert (int(pairs), int(edges), int(molecules), int(wgsize)) == (got[1], got[2], sum(got[0]), used)
+        assert 1 <= int(glink) and int(glink) * used <= 65536 and (int(glink) * used < 65536) == (wg == "64")
+
+
+def test_a_set_smaller_than_one_wave(P, monkeypatch, capfd):
+    """a dozen records from a first set of 2 slots leave 32 slots: `base + lane < slots` cuts the one wave that has work,
+    the other waves of the workgroup find none"""
+    monkeypatch.setenv("F2Q_TRACE", "1")
+    monkeypatch.setenv("F2Q_UMI_SLOTS", "2")
+    got, umis = collapsed(P, "tiny")
+    assert got == CC.TINY_WANT == CC.expected("tiny") and umis == [3, 2]
+    said = capfd.readouterr().err
+    assert re.findall(r"\[f2q trace\] UMI set: (\d+) slots, (\d+) rehashes", said) == [("32", "0")], said      # the smallest power of two >= 2 x 11
+    assert re.findall(r"; wave, (\d+) x (\d+)\)", said)[:2] == [("1", "256")] * 2
+
+
 @pytest.mark.parametrize("layout", ["first_set", "rehashed", "lane_per_slot"])
 def test_contention(P, monkeypatch, capfd, layout):
     """every union of feature 7 lands in one tree; 'rehashed': a first set of 64 slots fed in pieces of 30 records"""

@@ -1,5 +1,5 @@
 """--mur directional without a GPU: the lane logic of reads per (feature, UMI) pair and of f2q_umi_collapse_directional
-(umi_claim_at / umi_insert_reads / UmiReadsHook, umi_rehash_reads_one, umi_link_dir_one, umi_dir_spread_one,
+(umi_claim_at / umi_insert<true> / UmiHook<P, true>, umi_rehash_one<true>, umi_link_dir_one, umi_dir_spread_one,
 umi_dir_root_one of f2q_device.h) compiled for the host by tests/emu/f2q_umi_dir_emu.cpp and run over the emulated set,
 against the literal restatement of UMI-tools in tests/umi_dir_cases.py under three tie orders -- the shapes of
 tests/test_umi_dir_gpu.py; the command line's flag and refusals; the header against the binding's export list."""
@@ -38,19 +38,18 @@ def _lib():
     vp, i64p, u32p = C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint32)
     L.demu_create.restype = vp
     L.demu_create.argtypes = [C.POINTER(binding.Params), C.c_int32, C.c_int32, C.c_uint64]
-    L.demu_destroy.argtypes = [vp]
-    L.demu_set.restype = vp
-    L.demu_set.argtypes = [vp]
-    L.demu_set_features.argtypes = [vp, C.c_char_p, u32p, C.c_uint32]
-    L.demu_count_block.restype = C.c_size_t
-    L.demu_count_block.argtypes = [vp, C.c_char_p, C.c_size_t]
-    L.demu_reset.argtypes = [vp]
+    L.uemu_destroy.argtypes = [vp]
+    L.uemu_set_features.argtypes = [vp, C.c_char_p, u32p, C.c_uint32]
+    L.uemu_count_block.restype = C.c_size_t
+    L.uemu_count_block.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.uemu_reset.argtypes = [vp]
     L.demu_directional.argtypes = [vp, C.c_int32, i64p, i64p]
     L.demu_pairs.restype = C.c_uint64
     L.demu_pairs.argtypes = [vp, C.c_uint64, u32p, u32p, u32p, u32p]
     L.uemu_read.restype = C.c_longlong
     L.uemu_read.argtypes = [vp, i64p, i64p, i64p, i64p]
     L.uemu_collapse.argtypes = [vp, C.c_int32, C.c_int32, i64p, i64p]
+    L.uemu_set_info.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
     _L.append(L)
     return L
 
@@ -66,14 +65,14 @@ class DEmu:
         p, self._keep = binding.make_params(mode="C", **run)
         self.h = C.c_void_p(self.L.demu_create(C.byref(p), umi[0], umi[1], slots))
         assert self.h
-        self.set = C.c_void_p(self.L.demu_set(self.h))
+        self.set = self.h                                            # one handle: the set with its reads
         enc = [s.encode() for s in lib]
         offs = np.zeros(len(enc) + 1, dtype=np.uint32)
         offs[1:] = np.cumsum([len(b) for b in enc])
-        self.L.demu_set_features(self.h, b"".join(enc), offs.ctypes.data_as(C.POINTER(C.c_uint32)), len(enc))
+        self.L.uemu_set_features(self.h, b"".join(enc), offs.ctypes.data_as(C.POINTER(C.c_uint32)), len(enc))
 
     def count(self, fq):
-        assert self.L.demu_count_block(self.h, fq, len(fq)) == len(fq)
+        assert self.L.uemu_count_block(self.h, fq, len(fq)) == len(fq)
 
     def state(self):
         """counts, stats, umis, valid, invalid, rehashes"""
@@ -101,11 +100,17 @@ class DEmu:
         f, c, r, s = (list(a)[:n] for a in arrs)
         return list(zip(f, c, r)), s
 
+    def set_info(self):
+        """pairs held (the counter), occupied slots, slots"""
+        held, occupied, slots = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self.L.uemu_set_info(self.h, C.byref(held), C.byref(occupied), C.byref(slots))
+        return held.value, occupied.value, slots.value
+
     def reset(self):
-        self.L.demu_reset(self.h)
+        self.L.uemu_reset(self.h)
 
     def close(self):
-        self.L.demu_destroy(self.h)
+        self.L.uemu_destroy(self.h)
 
 
 def counted(name, slots=0, per=0):
@@ -158,6 +163,16 @@ def test_one_base_umis():
 def test_sixteen_base_umis_next_to_wide_feature_indices():
     e, got, _, _ = checked("wide")
     assert sum(got[0][:512]) == 0 and got[2] > 0
+    e.close()
+
+
+def test_a_set_smaller_than_one_wave():
+    """a dozen records from a first set of 2 slots: the answers by hand, and the 32 slots the sizing rule gives"""
+    e, got, before, (table, _) = checked("tiny", slots=2)
+    assert got == DC.TINY_WANT and e.cluster() == CC.TINY_WANT and before[2] == DC.TINY_UMIS
+    assert len(UC.records(DC.shape("tiny")[1])) == CC.TINY_RECORDS <= 12
+    assert e.set_info() == (5, 5, 32) and before[5] == 0              # the smallest power of two >= 2 x 11; one block: no rehash
+    assert table == [(0, 0, 5), (0, 1 << 6, 1), (0, 1 << 4 | 1 << 6, 1), (1, 0, 2), (1, 1 << 6, 2)]      # AAAA, AAAC, AACC; AAAA, AAAC
     e.close()
 
 

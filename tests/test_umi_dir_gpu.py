@@ -1,5 +1,5 @@
-"""--mur directional on the device: reads per (feature, UMI) pair (f2q_set_umi_reads: k_count_umi<true>, k_umi_rehash_reads,
-f2q_umi_pairs) and f2q_umi_collapse_directional (k_umi_uf_init / k_umi_link_dir / k_umi_dir_spread / k_umi_dir_roots)
+"""--mur directional on the device: reads per (feature, UMI) pair (f2q_set_umi_reads: k_count_umi<true>, k_umi_rehash<true>,
+f2q_umi_pairs) and f2q_umi_collapse_directional (k_umi_uf_init / k_umi_link<true> / k_umi_dir_spread / k_umi_dir_roots)
 against the literal restatement of UMI-tools in tests/umi_dir_cases.py, computed under three tie orders; what the calls
 leave untouched, their state errors, and the command line's outputs."""
 import collections
@@ -93,6 +93,52 @@ def test_one_base_umis(P):
 def test_sixteen_base_umis_next_to_wide_feature_indices(P):
     got, _ = checked(P, "wide")
     assert sum(got[0][:512]) == 0 and got[2] > 0
+
+
+# F2Q_UMI_LINK_WG, F2Q_UMI_LINK_GRID -> the workgroup size the linking launch must take (None: unset; 96 is no whole
+# number of waves and 0 no grid: the default for both)
+GEOMETRIES = [(None, None, 256), ("64", "1", 64), ("128", "2", 128), ("96", "0", 256)]
+
+
+def set_geometry(monkeypatch, wg, grid):
+    monkeypatch.setenv("F2Q_TRACE", "1")
+    for key, value in (("F2Q_UMI_LINK_WG", wg), ("F2Q_UMI_LINK_GRID", grid)):
+        if value is None:
+            monkeypatch.delenv(key, raising=False)
+        else:
+            monkeypatch.setenv(key, value)
+
+
+@pytest.mark.parametrize("wg,grid,used", GEOMETRIES)
+@pytest.mark.parametrize("name", ["known1", "wide"])
+def test_launch_geometry(P, monkeypatch, capfd, name, wg, grid, used):
+    """both linking launches under every geometry the switches can give, on the shapes that bound 3L: one-base UMIs (3L = 3:
+    21 groups a round, lane 63 idle) and sixteen-base ones (3L = 48: one group, 16 lanes idle).  The first set has
+    65 536 slots: 64 x 1 strides over it many times"""
+    set_geometry(monkeypatch, wg, grid)
+    got, before = checked(P, name)                                   # (asserts the expectation of both rules)
+    said = capfd.readouterr().err
+    tails = re.findall(r"\[f2q trace\] UMI collapse directional: (\d+) pairs, (\d+) edges, (\d+) dominated, (\d+) molecules, (\d+) reads, [\d.]+ ms "
+                       r"\([^;]*; wave, (\d+) x (\d+)\)", said)
+    assert tails and all(tuple(map(int, t[:5])) == (got[1], got[2], got[3], sum(got[0]), got[4]) for t in tails)
+    cl = before[5]
+    ctails = re.findall(r"\[f2q trace\] UMI collapse: (\d+) pairs, (\d+) edges, (\d+) molecules, [\d.]+ ms \([^;]*; wave, (\d+) x (\d+)\)", said)
+    assert ctails and all(tuple(map(int, t[:3])) == (cl[1], cl[2], sum(cl[0])) for t in ctails)
+    for t in tails + ctails:
+        glink, wgsize = int(t[-2]), int(t[-1])
+        assert wgsize == used and 1 <= glink and glink * used <= 65536 and (glink * used < 65536) == (wg == "64")
+
+
+def test_a_set_smaller_than_one_wave(P, monkeypatch, capfd):
+    """a dozen records from a first set of 2 slots leave 32 slots: `base + lane < slots` cuts the one wave that has work,
+    the other waves of the workgroup find none; the two rules give different answers on these records"""
+    monkeypatch.setenv("F2Q_TRACE", "1")
+    monkeypatch.setenv("F2Q_UMI_SLOTS", "2")
+    got, before = checked(P, "tiny")
+    assert got == DC.TINY_WANT and before[5] == CC.TINY_WANT and before[2] == DC.TINY_UMIS
+    said = capfd.readouterr().err
+    assert re.findall(r"\[f2q trace\] UMI set: (\d+) slots, (\d+) rehashes", said) == [("32", "0")], said      # the smallest power of two >= 2 x 11
+    assert set(re.findall(r"; wave, (\d+) x (\d+)\)", said)) == {("1", "256")}
 
 
 @pytest.mark.parametrize("layout", ["first_set", "rehashed"])

@@ -92,6 +92,24 @@ def short(length):
     return lib, UC.fastq_of(reads_of(lib, pairs, 20, rng)), dict(RUN), (20, length)
 
 
+TINY_RECORDS = 11
+TINY_WANT = ([1, 1], 5, 3)                                           # molecules, pairs, edges
+
+
+@functools.lru_cache(maxsize=None)
+def tiny():
+    """UMI 20,4, two features, eleven records: feature 0 AAAA x 5 - AAAC x 1 - AACC x 1 (a chain), feature 1 AAAA x 2 - AAAC
+    x 2.  From a first set of 2 slots one block of them gives a set of 32 slots (the host's rule: the smallest power of two
+    >= 2 x 11 records): less than one wave of the linking kernels, a quarter of a 256-thread workgroup of the others.
+    The reads per pair are chosen for tests/umi_dir_cases.py: the directional rule keeps the two UMIs of feature 1 apart"""
+    rng = random.Random(0xC015)
+    lib = UC.library()[:2]
+    pairs = [(0, b"AAAA")] * 5 + [(0, b"AAAC"), (0, b"AACC")] + [(1, b"AAAA"), (1, b"AAAC")] * 2
+    assert len(pairs) == TINY_RECORDS
+    rng.shuffle(pairs)
+    return lib, UC.fastq_of(reads_of(lib, pairs, 20, rng)), dict(RUN), (20, 4), TINY_WANT
+
+
 def gray(n, digits=8):
     """code n of the base-4 reflected Gray code, digit i in bits 2i .. 2i+1"""
     code = 0
@@ -131,11 +149,12 @@ def contention():
 
 
 def shape(name):
-    """(lib, fq, run, umi) of 'known', 'short1', 'short2', 'wide' (with --m 1, as tests/test_umi_*.py run it), 'contention'"""
+    """(lib, fq, run, umi) of 'known', 'short1', 'short2', 'wide' (with --m 1, as tests/test_umi_*.py run it), 'contention',
+    'tiny'"""
     if name == "wide":
         lib, fq, run, umi = UC.wide()
         return lib, fq, dict(run, miss=1), umi
-    return {"known": known, "short1": lambda: short(1), "short2": lambda: short(2), "contention": contention}[name]()[:4]
+    return {"known": known, "short1": lambda: short(1), "short2": lambda: short(2), "contention": contention, "tiny": tiny}[name]()[:4]
 
 
 @functools.lru_cache(maxsize=None)

@@ -146,6 +146,9 @@ def known1():
     return lib, _fastq(lib, counted, 0xD103), dict(RUN), (20, 1), ([1, 4] + pad, [1, 1] + pad, [4, 4] + pad)
 
 
+TINY_WANT = ([1, 2], 5, 3, 1, 11)                                    # umi_collapse_cases.tiny: molecules, pairs, edges, dominated, reads
+TINY_UMIS = [3, 2]
+
 GRAY_N, GRAY_FEATURE = CC.GRAY_N, CC.GRAY_FEATURE
 SKEW = (1, 1, 1, 1, 2, 2, 3, 5, 12)
 
@@ -176,12 +179,13 @@ def contention(twice):
 
 def shape(name):
     """(lib, fq, run, umi) of 'known', 'known1', 'ones', 'twice' (the two contention inputs), 'wide' (umi_cases.wide with
-    --m 1 and every third record read three more times: sixteen-base UMIs with skewed reads)"""
+    --m 1 and every third record read three more times: sixteen-base UMIs with skewed reads), 'tiny' (umi_collapse_cases.tiny:
+    5/1/1 on a chain -- one molecule by either rule -- and 2/2 neighbours -- one by the cluster rule, two by this one)"""
     if name == "wide":
         lib, fq, run, umi = UC.wide()
         recs = UC.records(fq)
         return lib, UC.fastq_of(recs + [r for i, r in enumerate(recs) if i % 3 == 0] * 3), dict(run, miss=1), umi
-    return {"known": known, "known1": known1, "ones": lambda: contention(False), "twice": lambda: contention(True)}[name]()[:4]
+    return {"known": known, "known1": known1, "ones": lambda: contention(False), "twice": lambda: contention(True), "tiny": CC.tiny}[name]()[:4]
 
 
 @functools.lru_cache(maxsize=None)
