@@ -128,7 +128,8 @@ struct Crc32 {
 };
 
 struct Inflater {
-    enum Status { OUT_FULL = 0, DONE = 1, ERR = 2, BOUNDARY = 3 };     // BOUNDARY: stopped in front of a block header at or past stop_bit
+    // BOUNDARY: stopped in front of a block header at or past stop_bit; LIMIT: SpecInflater::run_spec reached its symbol cap (f2q_pargz.h)
+    enum Status { OUT_FULL = 0, DONE = 1, ERR = 2, BOUNDARY = 3, LIMIT = 4 };
 
     static constexpr int LT_BITS = 11, DT_BITS = 8;
     static constexpr uint32_t LT_CAP = 2048 + 2400, DT_CAP = 256 + 800;
@@ -373,7 +374,11 @@ struct Inflater {
                     bb = 0; bc = 0;
                     size_t n = stored_left;
                     if (n > (size_t)(out_end - out)) n = (size_t)(out_end - out);
-                    if (n > (size_t)(in_end - in)) { st = S_ERR; break; }
+                    if (n > (size_t)(in_end - in)) {                   // cut off inside the block: the bytes that are there count (zlib delivers them)
+                        n = (size_t)(in_end - in);
+                        memcpy(out, in, n); in += n; out += n; stored_left -= (uint32_t)n;
+                        st = S_ERR; break;
+                    }
                     memcpy(out, in, n); in += n; out += n; stored_left -= (uint32_t)n;
                 }
                 if (stored_left) { rc = OUT_FULL; break; }

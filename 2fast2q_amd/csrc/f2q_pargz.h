@@ -13,7 +13,9 @@
 //      Inflater); the window is handed from chunk to chunk by resolving just the last 32 KiB of each; then all chunks
 //      are resolved to bytes in parallel (a table look-up per marker).
 // A start that was guessed wrong (a false positive of the search) breaks the chain: the chunks behind it are thrown
-// away and the next round starts at the true boundary the last valid chunk reached.  A damaged stream delivers the text
+// away and the next round starts at the true boundary the last valid chunk reached.  A speculative chunk that reaches
+// its symbol cap (a memory bound; text that inflates more than 64 : 1) is thrown away in the same way: the next round's
+// first chunk decodes that stretch with the plain decoder, which has no cap.  A damaged stream delivers the text
 // decoded before the damage, exactly as the sequential decoder does.  CRC-32 / ISIZE are checked by the caller on the
 // text it is handed, as for a sequential read.
 #pragma once
@@ -59,8 +61,10 @@ struct SpecInflater : Inflater {
     static constexpr uint16_t MARK = 0x8000u;
 
     // Decodes blocks from the current position (set with reset_at) into `out` (appended) until a block header at a bit
-    // offset >= stop_bit (BOUNDARY), the end of the final block (DONE), an invalid stream or more than `limit` symbols
-    // (ERR).  *blocks = blocks completed.  `max_blocks`: stop (BOUNDARY) after that many blocks (the search's test run).
+    // offset >= stop_bit (BOUNDARY), the end of the final block (DONE), an invalid stream (ERR) or the symbol cap (LIMIT:
+    // the next stored block or the next stretch of Huffman symbols would pass `limit`; the stream may be sound, `out` then
+    // ends inside a block and holds at most limit + 64 * 264 symbols).  *blocks = blocks completed.  `max_blocks`: stop
+    // (BOUNDARY) after that many blocks (the search's test run).
     Status run_spec(RawBuf<uint16_t> &out, size_t limit, uint32_t max_blocks, uint32_t *blocks)
     {
         size_t o = out.size();
@@ -78,13 +82,18 @@ struct SpecInflater : Inflater {
                 if (!need(32)) break;
                 const uint32_t len = take(16), nlen = take(16);
                 if ((len ^ nlen) != 0xFFFFu) break;
-                if (o + len > limit) break;
+                if (o + len > limit) { rc = LIMIT; break; }
                 room(len);
                 uint32_t left = len;
                 while (left && bc >= 8) { out.p[o++] = (uint16_t)take(8); left--; }
                 if (left) {
                     bb = 0; bc = 0;
-                    if ((size_t)(in_end - in) < left) break;
+                    if ((size_t)(in_end - in) < left) {                // cut off inside the block: the bytes that are there count, as in Inflater::run
+                        const size_t k = (size_t)(in_end - in);
+                        for (size_t i = 0; i < k; i++) out.p[o + i] = in[i];
+                        in += k; o += k;
+                        break;
+                    }
                     for (uint32_t i = 0; i < left; i++) out.p[o + i] = in[i];
                     in += left; o += left;
                 }
@@ -96,10 +105,10 @@ struct SpecInflater : Inflater {
             else break;
             bool err = false, eob = false;
             while (!eob) {
-                if (o + 64 * 264 > limit) { err = true; break; }
+                if (o + 64 * 264 > limit) { rc = LIMIT; err = true; break; }
                 room(64 * 264);                                        // a stretch: at least 64 symbols of at most 258 + 7 (copy overshoot) each
                 uint16_t *const ob = out.data();
-                uint16_t *op = ob + o, *const op_stop = ob + out.cap - 272;
+                uint16_t *op = ob + o, *const op_stop = ob + std::min(out.cap, limit + 64 * 264) - 272;    // (a stretch ends within a match of op_stop)
                 // fast loop (the shape of Inflater::run's): 8 readable input bytes, room for the longest match
                 bool have_e = false; uint32_t e = 0;
                 while (op < op_stop && in_end - in >= 8) {
@@ -272,7 +281,7 @@ inline uint64_t find_block_start(const uint8_t *p, size_t n, uint64_t from_bit, 
         scratch.clear();
         uint32_t nb = 0;
         const Inflater::Status r = probe.run_spec(scratch, (size_t)64 << 20, 2, &nb);
-        if (r == Inflater::ERR || nb < 2) continue;
+        if (r == Inflater::ERR || r == Inflater::LIMIT || nb < 2) continue;
         if (r == Inflater::BOUNDARY) {                                 // a third header must be there (type 3 is reserved)
             const uint64_t nx = probe.bit_pos();
             if ((nx >> 3) + 1 >= n) continue;
@@ -295,7 +304,9 @@ struct ParGunzip {
     uint64_t end_bit = 0;                                  // finished: the bit behind the final block
     int n_threads = 1;
     size_t chunk_bytes = (size_t)2 << 20;                  // compressed bytes per chunk (F2Q_GZ_CHUNK_KB)
-    uint64_t rounds = 0, chunks_ok = 0, chunks_dropped = 0;   // diagnostics
+    static constexpr size_t SYM_LIMIT_AUTO = ~(size_t)0;
+    size_t sym_limit = SYM_LIMIT_AUTO;                     // symbols a speculative chunk may emit (F2Q_GZ_SYM_KB, in Ki); auto: max(64 Mi, chunk_bytes * 64)
+    uint64_t rounds = 0, chunks_ok = 0, chunks_dropped = 0, chunks_capped = 0;   // diagnostics (capped: stopped at sym_limit, decoded again by a later round)
     double ratio = 6.0;                                    // text bytes per compressed byte in the last round (first guess: FASTQ)
     double lead_ratio = 0.0;                               // extra input (in chunks) the first chunk of a round takes, see round()
     Inflater first;                                        // the first chunk of a round: known window, plain decoder
@@ -311,6 +322,7 @@ struct ParGunzip {
         crc = 0; total = 0;
         n_threads = std::max(1, threads);
         { const char *e = getenv("F2Q_GZ_CHUNK_KB"); if (e && atol(e) >= 64) chunk_bytes = (size_t)atol(e) << 10; }
+        { const char *e = getenv("F2Q_GZ_SYM_KB"); if (e && *e) sym_limit = (size_t)std::min(std::max(0l, atol(e)), 1l << 40) << 10; }      // (0: every speculative chunk stops at once)
     }
     // first compressed byte behind the member's final block (valid once finished)
     const uint8_t *input_end() const { return base + ((end_bit + 7) >> 3); }
@@ -377,7 +389,9 @@ private:
         // ---- 1 + 2. every worker finds where its chunk starts, then decodes it up to the start behind it ------------
         std::vector<uint64_t> stop((size_t)T, ~0ull);
         std::atomic<int> found{1};                              // starts known so far (chunk 0's is)
-        const size_t sym_limit = std::max<size_t>((size_t)64 << 20, chunk_bytes * 64);
+        // a memory bound (2 bytes per symbol and worker), not a verdict on the stream: text that inflates more than
+        // 64 : 1 is legal; a chunk that reaches the cap is left to chunk 0 of a later round, which has no cap
+        const size_t sym_cap = sym_limit != SYM_LIMIT_AUTO ? sym_limit : std::max<size_t>((size_t)64 << 20, chunk_bytes * 64);
         double t_1 = t_0;
         std::vector<double> spent((size_t)T, 0.0);
         auto work = [&](int i) {
@@ -415,8 +429,8 @@ private:
             if (!d.reset_at(base, len, c.start, nullptr, 0)) { c.rc = Inflater::ERR; return; }
             d.stop_bit = stop_at;
             sym[(size_t)i]->clear();
-            sym[(size_t)i]->reserve(chunk_bytes * 5);
-            c.rc = d.run_spec(*sym[(size_t)i], sym_limit, ~0u, nullptr);
+            sym[(size_t)i]->reserve(std::min(chunk_bytes * 5, sym_cap + 64 * 264));
+            c.rc = d.run_spec(*sym[(size_t)i], sym_cap, ~0u, nullptr);
             c.n_out = sym[(size_t)i]->size(); c.end = d.bit_pos();
         };
         {
@@ -430,7 +444,7 @@ private:
             // bytes of input per second: the plain decoder of chunk 0 against the mean of the speculative ones (search included)
             double rs = 0; int ns = 0;
             for (int i = 1; i < T; i++)
-                if (ch[(size_t)i].start != ~0ull && ch[(size_t)i].end > ch[(size_t)i].start && spent[(size_t)i] > 0 && ch[(size_t)i].rc != Inflater::ERR) { rs += (double)(ch[(size_t)i].end - ch[(size_t)i].start) / spent[(size_t)i]; ns++; }
+                if (ch[(size_t)i].start != ~0ull && ch[(size_t)i].end > ch[(size_t)i].start && spent[(size_t)i] > 0 && ch[(size_t)i].rc != Inflater::ERR && ch[(size_t)i].rc != Inflater::LIMIT) { rs += (double)(ch[(size_t)i].end - ch[(size_t)i].start) / spent[(size_t)i]; ns++; }
             if (ns) {
                 const double r0 = (double)(ch[0].end - ch[0].start) / spent[0];
                 const double want = std::min(3.0, std::max(0.0, r0 / (rs / ns) - 1.0));
@@ -443,10 +457,12 @@ private:
         for (int i = 1; i < T && !ended; i++) {
             if (ch[(size_t)i].start == ~0ull) continue;                              // nothing found there: the chunk before ran through
             if (ch[(size_t)i].start != ch[(size_t)last].end) break;                  // guessed wrong (or not reached): everything from here is dropped
+            if (ch[(size_t)i].rc == Inflater::LIMIT) break;                          // stopped at the cap, inside a block: dropped like a wrong guess, the next
+                                                                                     // round's chunk 0 (plain decoder, no cap) starts where this chunk started
             last = i;
             ended = ch[(size_t)i].rc != Inflater::BOUNDARY;
         }
-        for (int i = 0; i < T; i++) if (ch[(size_t)i].start != ~0ull) { if (i <= last) chunks_ok++; else chunks_dropped++; }
+        for (int i = 0; i < T; i++) if (ch[(size_t)i].start != ~0ull) { if (i <= last) chunks_ok++; else if (ch[(size_t)i].rc == Inflater::LIMIT) chunks_capped++; else chunks_dropped++; }
         // ---- 4. windows, then bytes --------------------------------------------------------------------------
         std::vector<int> keep;
         for (int i = 0; i <= last; i++) if (i == 0 || ch[(size_t)i].start != ~0ull) keep.push_back(i);
@@ -502,7 +518,7 @@ private:
         if (trace) {
             fprintf(stderr, "[pargz] round %llu: search %.1f ms, decode %.1f ms, resolve %.1f ms; kept %zu of %d chunks, %zu bytes;", (unsigned long long)rounds,
                     (t_1 - t_0) * 1e3, (t_2 - t_1) * 1e3, (now_s() - t_2) * 1e3, keep.size(), T, off.back());
-            for (int i = 0; i < T; i++) fprintf(stderr, " [%d: %s start %lld end %lld out %zu]", i, ch[(size_t)i].rc == Inflater::BOUNDARY ? "B" : ch[(size_t)i].rc == Inflater::DONE ? "D" : "E",
+            for (int i = 0; i < T; i++) fprintf(stderr, " [%d: %s start %lld end %lld out %zu]", i, ch[(size_t)i].rc == Inflater::BOUNDARY ? "B" : ch[(size_t)i].rc == Inflater::DONE ? "D" : ch[(size_t)i].rc == Inflater::LIMIT ? "L" : "E",
                                                 ch[(size_t)i].start == ~0ull ? -1ll : (long long)(ch[(size_t)i].start - pos_bit), (long long)(ch[(size_t)i].end - pos_bit), ch[(size_t)i].n_out);
             fprintf(stderr, "\n");
         }

@@ -3,7 +3,10 @@
 // pattern, decoded with 1..5 threads in chunks of a few KiB (many chunks, rounds, guessed starts) and handed out in
 // pieces of random size; then damaged copies (bit flips, cut-offs): never a crash or an out-of-range access (build with
 // -fsanitize=address,undefined; inputs are exact-size heap blocks), the same accept / reject verdict as zlib, and
-// the bytes delivered before an error are the bytes zlib delivers.  usage: pargz_fuzz <iterations> [seed]
+// the bytes delivered before an error are the bytes zlib delivers.  Two kinds of data deflate 100 : 1 and more, and the
+// symbol cap of a speculative chunk (ParGunzip::sym_limit) is drawn from {0, 1000, 17000, 100000, default}: a chunk that
+// reaches it is decoded again by a later round, never reported as damage (random data, emitted as stored blocks, under
+// the small caps covers the stored-block side of that test).  usage: pargz_fuzz <iterations> [seed]
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -31,6 +34,26 @@ static std::vector<uint8_t> make(int kind, size_t n)
             if (i < n) d[i++] = '\n';
         }
     } break;
+    case 6: { size_t i = 0; while (i < n) { const uint8_t c = "ACGTNI#\n"[rnd() & 7]; for (size_t L = 1 + rnd() % 400000; L && i < n; L--) d[i++] = c; } } break;   // runs of one byte
+    case 7: {   // a few records, each repeated many times
+        char rec[4][400]; size_t rl[4];
+        for (int r = 0; r < 4; r++) {
+            const size_t L = 50 + rnd() % 100; size_t k = (size_t)snprintf(rec[r], 64, "@amplicon:%d\n", r);
+            for (size_t j = 0; j < L; j++) rec[r][k++] = "ACGT"[rnd() & 3];
+            rec[r][k++] = '\n'; rec[r][k++] = '+'; rec[r][k++] = '\n';
+            for (size_t j = 0; j < L; j++) rec[r][k++] = 'I';
+            rec[r][k++] = '\n'; rl[r] = k;
+        }
+        size_t i = 0;
+        while (i < n) { const int r = rnd() & 3; for (size_t rep = 1 + rnd() % 2000; rep && i < n; rep--) for (size_t j = 0; j < rl[r] && i < n; j++) d[i++] = (uint8_t)rec[r][j]; }
+    } break;
+    case 8: {   // stretches of the other kinds in one stream: the ratio steps up and down, stored blocks behind Huffman ones
+        size_t i = 0;
+        while (i < n) {
+            const std::vector<uint8_t> part = make((int)(rnd() % 8), std::min<size_t>(n - i, 1 + rnd() % 60000));
+            memcpy(d.data() + i, part.data(), part.size()); i += part.size();
+        }
+    } break;
     default: for (size_t i = 0; i < n; i++) d[i] = (uint8_t)((i * 2654435761u) >> (rnd() % 3 ? 24 : 28)); break;
     }
     return d;
@@ -56,23 +79,33 @@ int main(int argc, char **argv)
     f2qz::ParGunzip *pg = new f2qz::ParGunzip();
     long ok = 0, damaged_ok = 0, damaged_err = 0; unsigned long long dropped = 0, kept = 0;
     for (int it = 0; it < iters; it++) {
-        const int kind = rnd() % 6;
+        const int kind = (int[]){0, 1, 2, 3, 4, 5, 6, 7, 8, 8, 8, 9}[rnd() % 12];
         const size_t n = (rnd() % 10 == 0) ? rnd() % 50 : (rnd() % 3 == 0 ? 200000 + rnd() % 1500000 : rnd() % 120000);
         std::vector<uint8_t> data = make(kind, n);
         const int level = rnd() % 10, strat = (int[]){Z_DEFAULT_STRATEGY, Z_FILTERED, Z_HUFFMAN_ONLY, Z_RLE, Z_FIXED}[rnd() % 5];
         const int memlevel = 1 + rnd() % 9;
-        std::vector<uint8_t> comp(n + n / 4 + 70000);
+        std::vector<uint8_t> comp(n + n / 2 + 70000);
         z_stream zs = {}; if (deflateInit2(&zs, level, Z_DEFLATED, -15, memlevel, strat) != Z_OK) return 1;
         zs.next_in = data.data(); zs.avail_in = n; zs.next_out = comp.data(); zs.avail_out = comp.size();
-        if (n > 10 && rnd() % 3 == 0) { zs.avail_in = n / 3; deflate(&zs, (rnd() & 1) ? Z_FULL_FLUSH : Z_SYNC_FLUSH); zs.avail_in = n - n / 3; }
+        const uint32_t shape = rnd() % 3;
+        if (n > 10 && shape == 0) { zs.avail_in = n / 3; deflate(&zs, (rnd() & 1) ? Z_FULL_FLUSH : Z_SYNC_FLUSH); zs.avail_in = n - n / 3; }
+        if (n > 64 && shape == 1) {          // the level steps between 0 and 1..9 seven times: runs of stored blocks behind Huffman blocks whatever the data
+            for (int k = 0; k < 7; k++) {
+                zs.avail_in = n / 8;
+                if (deflate(&zs, Z_BLOCK) != Z_OK || zs.avail_in || deflateParams(&zs, (k & 1) ? (level ? level : 6) : 0, strat) != Z_OK) return 1;
+            }
+            zs.avail_in = n - 7 * (n / 8);
+        }
         if (deflate(&zs, Z_FINISH) != Z_STREAM_END) return 1;
         const size_t clen = zs.total_out; deflateEnd(&zs);
         const size_t tail = rnd() % 3 ? 8 + rnd() % 40 : 0;                       // what follows the member in a file: trailer, more members
         uint8_t *cin = (uint8_t *)malloc(clen + tail ? clen + tail : 1); memcpy(cin, comp.data(), clen);
         for (size_t i = 0; i < tail; i++) cin[clen + i] = (uint8_t)rnd();
         const int threads = 1 + rnd() % 5;
+        const size_t cap = (size_t[]){0, 1000, 17000, 100000, f2qz::ParGunzip::SYM_LIMIT_AUTO}[rnd() % 5];
         pg->start(cin, clen + tail, threads);
         pg->chunk_bytes = (size_t[]){700, 3000, 16000, 70000, 1u << 20}[rnd() % 5];
+        pg->sym_limit = cap;
         std::vector<uint8_t> out;
         const f2qz::Inflater::Status r = drain(*pg, out, n + 10);
         const uint32_t want_crc = (uint32_t)crc32(0, data.data(), (uInt)n);
@@ -91,6 +124,7 @@ int main(int argc, char **argv)
             const int zr = inflate(&zi, Z_FINISH); const size_t zn = zi.total_out, zused = zi.total_in; inflateEnd(&zi);
             pg->start(bad, dl, 1 + rnd() % 4);
             pg->chunk_bytes = (size_t[]){700, 3000, 16000, 70000}[rnd() % 4];
+            pg->sym_limit = cap;
             std::vector<uint8_t> mo;
             const f2qz::Inflater::Status mr = drain(*pg, mo, n + 70000);
             if (zr == Z_STREAM_END) {
@@ -108,5 +142,5 @@ int main(int argc, char **argv)
         dropped += pg->chunks_dropped; kept += pg->chunks_ok;
         free(cin);
     }
-    printf("ok %ld, damaged accepted-by-both %ld, rejected-by-both %ld (chunks kept %llu, dropped %llu in the last runs)\n", ok, damaged_ok, damaged_err, kept, dropped);
+    printf("ok %ld, damaged accepted-by-both %ld, rejected-by-both %ld (chunks kept %llu, dropped %llu in the last runs), chunks capped in all %llu\n", ok, damaged_ok, damaged_err, kept, dropped, (unsigned long long)pg->chunks_capped);
 }

@@ -1,6 +1,7 @@
 """The DEFLATE decoder of the file reader (2fast2q_amd/csrc/f2q_inflate.h) against zlib, under ASan + UBSan.
 Host only; the checker is tests/emu/inflate_fuzz.cpp."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -42,9 +43,11 @@ def pargz_bin():
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_parallel_gunzip_agrees_with_zlib(pargz_bin, seed):
-    """f2q_pargz.h (block search, decoding with an unknown window, chained resolution, 1..5 threads, chunks of 700 B ... 1 MiB)
-    against zlib on intact and damaged streams, under ASan + UBSan"""
+    """f2q_pargz.h (block search, decoding with an unknown window, chained resolution, 1..5 threads, chunks of 700 B ... 1 MiB,
+    symbol caps of 0 ... 100000 and the default, data up to 1000 : 1) against zlib on intact and damaged streams, under ASan + UBSan"""
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
     res = subprocess.run([pargz_bin, "40", str(seed)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:]
     assert res.stdout.startswith("ok 40,"), res.stdout
+    capped = re.search(r"chunks capped in all (\d+)", res.stdout)          # the symbol cap of a speculative chunk was reached: that road is covered
+    assert capped and int(capped.group(1)) > 0, res.stdout

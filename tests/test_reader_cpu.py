@@ -291,3 +291,140 @@ def test_gzip_parallel_wrong_crc_is_truncation(tmp_path, par_payload, par_env):
     z = tmp_path / "w.fastq.gz"; z.write_bytes(bytes(raw))
     got = read_file(z, 1 << 20, 4, out_cap=1 << 25)
     assert got[0] == par_payload and got[1] is True
+
+
+# ---- low-complexity text: a speculative chunk reaches its symbol cap (F2Q_GZ_SYM_KB) ----------------------------------
+# Every test here asserts from the F2Q_GZ_TRACE lines that a chunk was in fact stopped at the cap ("L").
+import low_complexity_cases as lc
+
+
+def read_traced(capfd, path, piece, threads, out_cap):
+    """read_file plus the number of chunks its trace shows as capped"""
+    capfd.readouterr()
+    got = read_file(path, piece, threads, out_cap=out_cap)
+    return got, lc.capped_chunks(capfd.readouterr().err)
+
+
+@pytest.fixture()
+def cap_env(par_env):
+    par_env.setenv("F2Q_GZ_TRACE", "1")
+    return par_env
+
+
+def test_gzip_parallel_default_cap_is_not_damage(tmp_path, cap_env, capfd):
+    """Runs of one byte, 1000 : 1, in chunks of 128 KiB: the chunk behind the first inflates to more than the default cap
+    of 64 Mi symbols.  A valid archive: the whole text comes back.  (Before the cap had a status of its own this read
+    delivered 202 873 612 of the 224 000 000 bytes and reported truncation.)"""
+    cap_env.setenv("F2Q_GZ_CHUNK_KB", "128")
+    data = lc.byte_runs(224_000_000, 3)
+    z = tmp_path / "runs.fastq.gz"; z.write_bytes(lc.gz_member(data))
+    assert z.stat().st_size > (128 << 10) + (64 << 20) // 1032          # a second chunk, and more than the cap behind its start
+    for threads in (2, 4):
+        (got, tr, kind), capped = read_traced(capfd, z, 1 << 24, threads, 1 << 28)
+        assert (len(got), tr, kind) == (len(data), False, "gzip")
+        assert got == data
+        assert capped >= 1
+        del got
+
+
+@pytest.mark.parametrize("sym_kb", [0, 16, 17, 64, 1024])
+@pytest.mark.parametrize("level", [1, 6, 9])
+def test_gzip_parallel_small_cap_ordinary_text(tmp_path, par_payload, cap_env, capfd, level, sym_kb):
+    """ordinary text under a cap of a few Ki symbols (16 and 17 Ki lie on either side of the 64 * 264 symbols a Huffman
+    stretch asks for): at 0 and 16 Ki every speculative chunk stops at once and chunk 0 alone advances the stream.
+    A chunk of 64 KiB of this text holds 0.2 .. 0.4 Mi symbols, so a cap of 1024 Ki is out of its reach: that cap is
+    read with chunks of 64 KiB (nothing capped, the text must still be whole) and of 512 KiB (about 1.8 Mi symbols)"""
+    cap_env.setenv("F2Q_GZ_SYM_KB", str(sym_kb))
+    z = tmp_path / "a.fastq.gz"
+    with gzip.open(z, "wb", compresslevel=level) as f: f.write(par_payload)
+    for chunk_kb in (64, 512) if sym_kb == 1024 else (64,):
+        cap_env.setenv("F2Q_GZ_CHUNK_KB", str(chunk_kb))
+        for threads in (2, 3, 8):
+            for piece in (1 << 16, 1 << 20, 1 << 24):
+                got, capped = read_traced(capfd, z, piece, threads, 1 << 25)
+                assert got == (par_payload, False, "gzip"), (chunk_kb, threads, piece)
+                assert (capped >= 1) == (sym_kb < 1024 or chunk_kb == 512), (chunk_kb, threads, piece, capped)
+
+
+@pytest.fixture(scope="module")
+def steps_text():
+    return lc.ratio_steps()
+
+
+@pytest.fixture(scope="module")
+def steps_gz(steps_text):
+    return lc.gz_member(steps_text)
+
+
+@pytest.mark.parametrize("sym_kb", [None, 17, 64, 192])
+def test_gzip_parallel_ratio_steps(tmp_path, steps_text, steps_gz, cap_env, capfd, sym_kb):
+    """one member whose ratio goes 4 -> 150 -> 4 -> 1 (stored blocks) -> 150 -> 4: the running estimate that sizes chunk
+    0's buffer and the room test of read() is stale in both directions.  None: the default cap, never reached here.
+    17 and 64 Ki: every chunk of 64 KiB holds more.  192 Ki: more than 64 KiB of this ordinary text hold (2.8 : 1), so
+    the chunk that starts in the text in front of the random bytes gets past its Huffman blocks; no dynamic block starts
+    among the stored ones, so it runs through them to the end of the round's stretch and, with 12 or 16 chunks in a
+    round, stops at a stored block.  Whether that chunk and the few chunks of the 150 : 1 stretches (10 Mi symbols each)
+    are speculative ones depends on where the rounds fall, so that cap is asserted over the reads together"""
+    if sym_kb is not None: cap_env.setenv("F2Q_GZ_SYM_KB", str(sym_kb))
+    z = tmp_path / "s.fastq.gz"; z.write_bytes(steps_gz)
+    total = 0
+    for threads, piece in ((2, 1 << 16), (4, 1 << 20), (8, 1 << 22), (3, 1 << 25), (12, 1 << 18), (16, 1 << 20)):
+        got, capped = read_traced(capfd, z, piece, threads, 1 << 26)
+        assert (got[0] == steps_text, got[1], got[2]) == (True, False, "gzip"), (threads, piece)
+        if sym_kb in (17, 64): assert capped >= 1, (threads, piece)
+        total += capped
+    assert (total >= 1) == (sym_kb is not None)
+
+
+@pytest.mark.parametrize("sym_kb", [None, 64])
+def test_gzip_parallel_high_ratio_member_between_ordinary_ones(tmp_path, par_payload, cap_env, capfd, sym_kb):
+    if sym_kb is not None: cap_env.setenv("F2Q_GZ_SYM_KB", str(sym_kb))
+    third = len(par_payload) // 3
+    hot = lc.few_records(20 << 20, 21)
+    want = par_payload[:third] + hot + par_payload[third:]
+    z = tmp_path / "m.fastq.gz"
+    z.write_bytes(lc.gz_member(par_payload[:third], 1) + lc.gz_member(hot, 6) + lc.gz_member(b"") + lc.gz_member(par_payload[third:], 9))
+    assert gzip.open(z).read() == want
+    for threads, piece in ((2, 1 << 18), (5, 1 << 22)):
+        got, capped = read_traced(capfd, z, piece, threads, 1 << 26)
+        assert (got[0] == want, got[1], got[2]) == (True, False, "gzip"), (threads, piece)
+        assert (capped >= 1) == (sym_kb is not None), (threads, piece, capped)
+
+
+def damaged(raw, how):
+    if how == "flip":
+        bad = bytearray(raw); bad[len(raw) // 2] ^= 0x55
+        return bytes(bad)
+    return raw[: int(len(raw) * how)]
+
+
+@pytest.mark.parametrize("how", [0.13, 0.5, 0.97, "flip"])
+def test_gzip_parallel_damage_while_capped(tmp_path, steps_text, steps_gz, cap_env, capfd, how):
+    """damage stays damage: with chunks being capped all along, a cut-off or corrupted archive delivers the bytes the
+    sequential decoder delivers, which are zlib's, and reports truncation"""
+    cap_env.setenv("F2Q_GZ_SYM_KB", "64")
+    raw = damaged(steps_gz, how)
+    z = tmp_path / "d.fastq.gz"; z.write_bytes(raw)
+    got, capped = read_traced(capfd, z, 1 << 18, 4, 1 << 26)
+    cap_env.setenv("F2Q_GZ_PAR", "0")
+    seq = read_file(z, 1 << 18, 4, out_cap=1 << 26)
+    assert got[1] is True and seq[1] is True and got[0] == seq[0]
+    ref = lc.zlib_prefix(raw)
+    print("damage %s: reader %d bytes, zlib %d bytes" % (how, len(got[0]), len(ref)))
+    if how == "flip":
+        # a flipped byte decodes to other bytes until a code turns out invalid (with zlib too): the text stands up to the
+        # flipped byte, and what follows is what zlib delivers (fed in pieces, it loses the piece the error is found in)
+        before = lc.zlib_prefix(raw[: len(raw) // 2])
+        assert steps_text.startswith(before) and got[0].startswith(before) and got[0].startswith(ref) and len(ref) >= len(before)
+    else:
+        assert got[0] == ref and steps_text.startswith(got[0]) and len(got[0]) < len(steps_text)
+    assert capped >= 1
+
+
+def test_gzip_parallel_wrong_crc_while_capped(tmp_path, steps_text, steps_gz, cap_env, capfd):
+    raw = bytearray(steps_gz); raw[-6] ^= 1                   # the CRC-32 in the trailer
+    z = tmp_path / "w.fastq.gz"; z.write_bytes(bytes(raw))
+    cap_env.setenv("F2Q_GZ_SYM_KB", "64")
+    got, capped = read_traced(capfd, z, 1 << 20, 4, 1 << 26)
+    assert got[0] == steps_text and got[1] is True
+    assert capped >= 1
