@@ -129,7 +129,7 @@ struct f2q_ctx {
     bool force_general = false;           // F2Q_FORCE_GENERAL=1: every read through the byte-exact general kernel (cross-checks)
     bool force_v1 = false;                // F2Q_FORCE_V1=1: keep the one-read-per-lane kernel (A/B runs)
     bool no_lt = false;                   // F2Q_NO_LT=1: never the LDS-table kernel (A/B runs, cross-checks)
-    uint32_t lt_max_wgs = 0;              // F2Q_LT_WGS=n: at most n workgroups of the kernels that count in u16 LDS counters -- k_count_fixed4_lds, k_count_anchor_lt, k_count_anchor_pairs (tests: many reads per histogram)
+    uint32_t lt_max_wgs = 0;              // F2Q_LT_WGS=n: at most n workgroups of the kernels that count in u16 LDS counters -- k_count_fixed4_lds, k_count_anchor_lt, k_count_anchor_pairs (tests: many reads per histogram) -- and of k_part_scatter, k_count_fixed4, k_count_multi4 (tests: several tiles per wave on a small block)
     bool no_pt = false;                   // F2Q_NO_PT=1: never the partitioned-table kernels (A/B runs, cross-checks)
     uint64_t pt_chunk_reads = (uint64_t)1 << 28;   // F2Q_PT_CHUNK: most reads per scatter/count round of the partitioned path (1.7 GB of streams per 200 M reads; 400 M reads in two rounds run 8 % faster than in six)
     uint64_t pt_min_reads = (uint64_t)1 << 21;     // F2Q_PT_MIN_READS: smaller blocks keep the packed-table kernel (three launches and the
@@ -880,7 +880,8 @@ static int launch_multi(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t 
     const uint32_t nf = c->lib_h.n_features;
     const bool lds = nf <= F2Q_HIST_MAX;
     const uint32_t wgs = (pb.n_tiles + F2Q_V2_WAVES - 1) / F2Q_V2_WAVES;
-    const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 2u);
+    uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 2u);
+    if (c->lt_max_wgs) grid = std::min<uint32_t>(grid, c->lt_max_wgs);
     const size_t shmem = (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 12 + (lds ? (size_t)nf * 4 : 0);
     int rc = slab_rows(c, lds ? grid : 0u, grid, acc);
     if (rc) return rc;
@@ -903,7 +904,8 @@ static int launch_part(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &
     const uint32_t max_tiles = (uint32_t)std::max<uint64_t>(chunk_reads / F2Q_TILE, 1);
     const uint32_t n_rounds = std::max<uint32_t>(1u, (pb.n_tiles + max_tiles - 1) / max_tiles);
     const uint32_t chunk_tiles = std::max<uint32_t>(1u, (pb.n_tiles + n_rounds - 1) / n_rounds);
-    const uint32_t grid1 = std::min<uint32_t>((uint32_t)c->n_cu, (chunk_tiles + pw - 1) / pw);
+    uint32_t grid1 = std::min<uint32_t>((uint32_t)c->n_cu, (chunk_tiles + pw - 1) / pw);
+    if (c->lt_max_wgs) grid1 = std::min<uint32_t>(grid1, c->lt_max_wgs);                    // (before the stream capacity is derived from it)
     const uint32_t tiles_per_wg = (chunk_tiles + grid1 - 1) / grid1 + (uint32_t)pw;          // (waves take tiles round robin)
     // entries per stream: what a workgroup can produce, in whole steps of the count pass, plus 11 x 256 bytes: the streams
     // grow at the same pace, and at a power-of-two distance their write positions would share memory channels
@@ -979,7 +981,8 @@ static int launch_fixed_packed(f2q_ctx *c, const PackedBlock &pb, Accum &acc, ui
     const uint32_t nf = c->lib_h.n_features;
     const bool lds = nf <= F2Q_HIST_MAX;
     const uint32_t wgs = (pb.n_tiles + F2Q_V2_WAVES - 1) / F2Q_V2_WAVES;
-    const uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 2u);
+    uint32_t grid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu * 2u);
+    if (c->lt_max_wgs) grid = std::min<uint32_t>(grid, c->lt_max_wgs);
     const size_t shmem = (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 12 + (lds ? (size_t)nf * 4 : (size_t)F2Q_V2_WAVES * F2Q_V2_QCAP * 4);
     const bool spec52 = fixed_variant(c, fixed_geom(c->run_h)) != FV_GENERIC;      // (no a20 instance: spec52 serves it)
     auto kern = lds ? (spec52 ? k_count_fixed4<true, 5, 2> : k_count_fixed4<true, 0, 0>)

@@ -142,12 +142,18 @@ def test_counter_bookkeeping(P, LIB):
 
 @pytest.mark.parametrize("miss", [1, 0], ids=["m1", "m0"])
 def test_other_instantiations(P, LIB, miss):
-    """the two-window (MW) instance, and <5, 2, ., false>: a 20-base window that starts at 3"""
+    """the two-window (MW) instance; a 20-base window that starts at 3: six quality rows (nq = 6), the generic instance
+    <0, 0, ., false>; and one that starts at 4: five quality rows, two base rows, no 16-aligned start: <5, 2, ., false>"""
     from test_lane_logic_cpu import multi_window_uniform_case
     lib2, fq2 = multi_window_uniform_case("0,20", 10, 40, n_feat=1500, n_reads=N17, seed=11)
     _check(P, lib2, dict(miss=miss, length=10, start="0,20"), fq2, all_fast=False, path=PATH_MULTI_LDS)
     kw = dict(miss=miss, phred=30, length=20, start="3")
     with P.Counter(features=LIB, **kw) as c:
         fq = bytes(c.synth_fastq(seed=33, n_reads=N17, read_len=150, start=3))
+    _, stats = _check(P, LIB, kw, fq)
+    assert stats[1] > 0
+    kw = dict(miss=miss, phred=30, length=20, start="4")
+    with P.Counter(features=LIB, **kw) as c:
+        fq = bytes(c.synth_fastq(seed=34, n_reads=N17, read_len=150, start=4))
     _, stats = _check(P, LIB, kw, fq)
     assert stats[1] > 0
