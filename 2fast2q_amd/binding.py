@@ -24,6 +24,7 @@ EXPORTS = (
     "f2q_set_assign_library", "f2q_ec_assign", "f2q_ec_fetch_assigned",
     "f2q_set_umi", "f2q_read_umis", "f2q_umi_collapse",
     "f2q_set_umi_reads", "f2q_umi_collapse_directional", "f2q_umi_pairs",
+    "f2q_set_umi_paired",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
@@ -174,6 +175,7 @@ def load(path=None):
     L.f2q_ec_assign.argtypes = [vp, i64p, i64p, C.POINTER(Timing)]
     L.f2q_ec_fetch_assigned.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.f2q_set_umi.argtypes = [vp, C.c_int32, C.c_int32]
+    L.f2q_set_umi_paired.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.f2q_read_umis.argtypes = [vp, i64p, i64p]
     L.f2q_umi_collapse.argtypes = [vp, C.c_int32, i64p, i64p]
     L.f2q_set_umi_reads.argtypes = [vp, C.c_int32]
@@ -256,9 +258,12 @@ class Counter:
 
     ``start2`` ("b[,b...]" or a list) makes it a paired context (f2q_set_mate2): ``start`` names the windows in mate 1,
     ``start2`` those in mate 2, ``rc2`` takes mate 2 reverse-complemented; such a context counts with the *_paired calls.
+    ``umi_paired=((S1, L1) or None, (S2, L2) or None)`` makes a paired context a UMI context (f2q_set_umi_paired): the UMI
+    is mate 1's [S1, S1 + L1) followed by [S2, S2 + L2) of mate 2 as sequenced, whatever ``rc2`` says; ``umi_length`` is
+    the total number of bases, and everything ``umi=`` offers works on it (``umi=`` itself stays single-read only).
     """
 
-    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, **params):
+    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -271,12 +276,16 @@ class Counter:
         self.n_assign = 0
         self.paired = False
         self.umi = None
+        self.umi_paired = None
+        self.umi_length = 0              # bases of a UMI (set_umi / set_umi_paired), 0: no UMI context
         self.umi_reads = False
         try:
             if start2 is not None:
                 self.set_mate2(start2, rc2)
             if umi is not None:
                 self.set_umi(*umi)
+            if umi_paired is not None:
+                self.set_umi_paired(*umi_paired)
             if umi_reads:
                 self.set_umi_reads(True)
         except BaseException:
@@ -338,6 +347,15 @@ class Counter:
         """the UMI window of every read (f2q_set_umi); before counting"""
         self._check(self._L.f2q_set_umi(self._h, int(start), int(length)))
         self.umi = (int(start), int(length))
+        self.umi_length = int(length)
+
+    def set_umi_paired(self, part1, part2):
+        """the UMI of every pair (f2q_set_umi_paired): part1 = (S1, L1) in mate 1 or None, part2 = (S2, L2) in mate 2 as
+        sequenced or None; after set_mate2, before counting"""
+        p1, p2 = [(0, 0) if p is None else (int(p[0]), int(p[1])) for p in (part1, part2)]
+        self._check(self._L.f2q_set_umi_paired(self._h, p1[0], p1[1], p2[0], p2[1]))
+        self.umi_paired = (p1 if p1[1] else None, p2 if p2[1] else None)
+        self.umi_length = p1[1] + p2[1]
 
     def set_umi_reads(self, on=True):
         """keep the reads of every (feature, UMI) pair (f2q_set_umi_reads); after set_umi, before counting"""

@@ -1050,6 +1050,10 @@ struct UmiDev {
     unsigned long long *umis;        // [n_features] distinct UMIs seen per feature
     unsigned long long *ctr;         // [F2Q_UMI_CTR_WORDS]
     uint32_t *reads;                 // [slots] reads per pair, parallel to slots[] (f2q_set_umi_reads); null: not kept
+    // a paired context (f2q_set_umi_paired): part 1 = [start1, start1 + len1) of mate 1, part 2 = [start2, start2 + len2) of
+    // mate 2 AS SEQUENCED (a length of 0: no part in that mate), length = len1 + len2; rc2: the merged record holds mate 2
+    // reversed and complemented.  All zero on a single-end context: start / length above are its window
+    int32_t start1, len1, start2, len2, rc2;
 };
 // claims a slot for word k with one CAS: 1 = new, 0 = already there, 2 = no room (probe bound, as ec64_insert_word).
 // `slot` is the slot that holds k (new or not), untouched on 2
@@ -1259,6 +1263,54 @@ struct UmiHook {
 };
 // the reads-keeping hook by name
 template <class P> using UmiReadsHook = UmiHook<P, true>;
+
+// ---- the UMI of a pair (f2q_set_umi_paired): one or two parts, found in the merged record ----
+// The record is mate 1 (r1 bases) then mate 2 as the run takes it (r - r1 bases), the quality line likewise (qn1, qn - qn1
+// bytes).  Part 1 is the single-end rule on mate 1's share.  Part 2 is named in mate 2 as the sequencer wrote it: without
+// rc2 base j is merged position r1 + j; under rc2 the share is that text reversed and complemented by comp8 -- which
+// leaves every byte that is not ACGT / acgt alone, so a base is valid there exactly when it was -- and base j sits at
+// r1 + len2 - 1 - j with code 3 - code, its quality byte at qn1 + qlen2 - 1 - j: each line mirrored by ITS OWN length.
+// The codes are part 1 followed by part 2, base j of the concatenation in bits 2j .. 2j+1; false: a present part is invalid
+template <class P>
+F2Q_HD bool umi_codes_paired(const UmiDev &u, int thr, P seq, int r, int r1, P qual, int qn, int qn1, uint32_t &codes)
+{
+    uint32_t w = 0;
+    if (u.len1) {
+        const int a = u.start1, b = u.start1 + u.len1;
+        if (b > r1 || b > qn1) return false;
+        if (qual_range_fails(qual, a, b, thr)) return false;
+        for (int j = a; j < b; j++) {
+            const uint32_t c = base_code(up8(seq[j]));
+            if (c > 3u) return false;
+            w |= c << (2 * (j - a));
+        }
+    }
+    if (u.len2) {
+        const int len2 = r - r1, qlen2 = qn - qn1;
+        const int a = u.start2, b = u.start2 + u.len2;
+        if (b > len2 || b > qlen2) return false;
+        if (u.rc2 ? qual_range_fails(qual, qn1 + qlen2 - b, qn1 + qlen2 - a, thr) : qual_range_fails(qual, qn1 + a, qn1 + b, thr)) return false;
+        for (int j = a; j < b; j++) {
+            uint32_t c = base_code(up8(seq[u.rc2 ? r1 + len2 - 1 - j : r1 + j]));
+            if (c > 3u) return false;
+            if (u.rc2) c = 3u - c;
+            w |= c << (2 * (u.len1 + j - a));
+        }
+    }
+    codes = w;
+    return true;
+}
+// UmiHook for a merged pair: r1 / qn1 = the split general_read<.., PAIRED> receives
+template <class P, bool READS = false>
+struct UmiPairHook {
+    const UmiDev *u; int thr; P seq; int r, r1; P qual; int qn, qn1; unsigned long long *ust;
+    F2Q_HD void assigned(uint32_t f) const
+    {
+        uint32_t codes = 0;
+        if (umi_codes_paired(*u, thr, seq, r, r1, qual, qn, qn1, codes)) { ust[0]++; ust[2] += umi_insert<READS>(*u, f, codes); }
+        else ust[1]++;
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // general path: one read given as raw bytes.  st[] = the 5 reference counters (thread-local).

@@ -120,6 +120,7 @@ struct f2q_ctx {
         uint64_t held_ub = 0;            // pairs held, an upper bound: every record launched since the last exact reading taken as new
         uint64_t rehashes = 0;
         bool reads_on = false;           // f2q_set_umi_reads: dev.reads[] lives and dies with dev.slots[] (set_allocs)
+        bool pair_stage = false;         // f2q_set_umi_paired: k_count_umi_pair<.., true> (F2Q_UMI_PAIR_STAGE)
     } umi;
     bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
@@ -551,20 +552,47 @@ extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 }
 
 // ---- distinct UMIs per feature: the ABI ---------------------------------------------------------------------------
-extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
+// what f2q_set_umi and f2q_set_umi_paired share once the window is in umi.dev
+static void umi_enable(f2q_ctx *c)
 {
-    if (!c) return F2Q_EINVAL;
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi takes a Counter context: Extract+Count assigns no read to a feature");
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) is not implemented");
-    if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
-    if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
-        return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
-    c->umi.on = true; c->umi.dev.start = start; c->umi.dev.length = length;
+    c->umi.on = true;
     { const char *e = getenv("F2Q_UMI_SLOTS"); if (e && atol(e) > 0) { c->umi.min_slots = 2; while (c->umi.min_slots < (uint64_t)atol(e) && c->umi.min_slots < (1ull << 32)) c->umi.min_slots <<= 1; } }
     // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
     c->force_general = true;
     c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
     c->plan.inband_n = false; c->plan.n_only = false;
+}
+extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi takes a Counter context: Extract+Count assigns no read to a feature");
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) takes f2q_set_umi_paired");
+    if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
+    if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
+        return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
+    c->umi.dev.start = start; c->umi.dev.length = length;
+    umi_enable(c);
+    return F2Q_OK;
+}
+
+// The UMI of a pair: [start1, start1 + length1) of mate 1 followed by [start2, start2 + length2) of mate 2 as sequenced
+// (include/f2q.h).  The context stays paired in every other respect: the ingest kernels see a plan without fast paths, so
+// read_is_clean is false for every pair and all of them travel as merged raw records to k_count_umi_pair.
+extern "C" int f2q_set_umi_paired(f2q_ctx *c, int32_t start1, int32_t length1, int32_t start2, int32_t length2)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a Counter context: Extract+Count assigns no pair to a feature");
+    if (!c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a paired context: call f2q_set_mate2 first (single reads: f2q_set_umi)");
+    if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired comes once, after f2q_set_mate2 and before counting");
+    if (start1 < 0 || start1 > 0x3FFFFFFF || start2 < 0 || start2 > 0x3FFFFFFF || length1 < 0 || length2 < 0 ||
+        length1 > F2Q_UMI_MAXLEN || length2 > F2Q_UMI_MAXLEN || length1 + length2 < 1 || length1 + length2 > F2Q_UMI_MAXLEN)
+        return fail(c, F2Q_EINVAL, "the UMI parts need starts >= 0 and lengths >= 0 that add up to 1 .. 16 bases");
+    UmiDev &u = c->umi.dev;
+    u.start = 0; u.length = length1 + length2;
+    u.start1 = length1 ? start1 : 0; u.len1 = length1; u.start2 = length2 ? start2 : 0; u.len2 = length2; u.rc2 = c->rc2 ? 1 : 0;
+    // F2Q_UMI_PAIR_STAGE=1 / 0: the merged lines staged in LDS / read from global memory (A/B runs; the default: DESIGN.md)
+    { const char *e = getenv("F2Q_UMI_PAIR_STAGE"); c->umi.pair_stage = e && (e[0] == '0' || e[0] == '1') && !e[1] ? e[0] == '1' : F2Q_UMI_PAIR_STAGE_DEFAULT; }
+    umi_enable(c);
     return F2Q_OK;
 }
 
@@ -1253,11 +1281,19 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
     const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
     if (c->umi.on) {                                             // the same road with the (feature, UMI) set (f2q_set_umi)
         if ((rc = umi_reserve(c, rb.n))) return rc;
-        if (c->umi.dev.reads) hipLaunchKernelGGL(k_count_umi<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev);
+        if (rb.len1) {                                           // merged pairs (f2q_set_umi_paired): a pair is one record
+            if (!c->umi.dev.len1 && !c->umi.dev.len2) return fail(c, F2Q_ESTATE, "a block of pairs on a single-read UMI context");
+            const bool keep = c->umi.dev.reads != nullptr;
+#define F2Q_LAUNCH_UMI_PAIR(R, S) hipLaunchKernelGGL((k_count_umi_pair<R, S>), dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev)
+            if (c->umi.pair_stage) { if (keep) F2Q_LAUNCH_UMI_PAIR(true, true); else F2Q_LAUNCH_UMI_PAIR(false, true); }
+            else { if (keep) F2Q_LAUNCH_UMI_PAIR(true, false); else F2Q_LAUNCH_UMI_PAIR(false, false); }
+#undef F2Q_LAUNCH_UMI_PAIR
+        }
+        else if (c->umi.dev.reads) hipLaunchKernelGGL(k_count_umi<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev);
         else hipLaunchKernelGGL(k_count_umi<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev);
         HIPC(c, hipGetLastError());
         launches++;
-        EC_POINT(c, "k_count_umi");
+        EC_POINT(c, rb.len1 ? "k_count_umi_pair" : "k_count_umi");
         return F2Q_OK;
     }
     if (rb.len1) hipLaunchKernelGGL(k_count_general<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
@@ -1868,7 +1904,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
 {
     if (!c) return F2Q_EINVAL;
     if (c->have_lib || c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_mate2 comes once, after f2q_create and before f2q_set_features");
-    if (c->umi.on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only");
+    if (c->umi.on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only: f2q_set_mate2 comes first, then f2q_set_umi_paired");
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
     for (int i = 0; i < n_start2; i++) if (start2[i] < 0) return fail(c, F2Q_EINVAL, "a mate-2 window starts before the mate");
@@ -1918,6 +1954,8 @@ static int block_from_pairs_device(f2q_ctx *c, const uint8_t *fq1, size_t n1, co
     HIPC(c, hipGetLastError());
     if ((rc = exclusive_scan(c, ing.clean, d_before, n_rec + 1u, tmp.v))) return rc;
     if ((rc = exclusive_scan(c, ing.raw_bytes, d_raw_before, n_rec + 1u, tmp.v))) return rc;
+    // 32-bit sizes with EVERY pair raw (a paired UMI context): a merged record holds only bytes of its four lines, each text
+    // is below 1 GiB, so raw_total and every prefix of raw_bytes stay below 2^30 + 2^30 = 2^31 < 2^32; n_rec < 2^28 (a record has 4 newlines)
     uint32_t n_clean = 0, rmax_in = 0, raw_total = 0;
     HIPC(c, hipMemcpyAsync(&n_clean, d_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipMemcpyAsync(&raw_total, d_raw_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));

@@ -1,12 +1,14 @@
 // f2q_umi_kernels.h -- distinct UMIs per feature (--umi, f2q_set_umi; included by f2q_lib.hip only).
 //   k_count_umi<READS>   Counter mode on raw records, the byte-exact routine, plus the (feature, UMI) set: one pass
 //                  (<false>: the set alone; <true>: reads per pair too, f2q_set_umi_reads)
+//   k_count_umi_pair<READS, STAGE>   the same on the merged records of a paired context (f2q_set_umi_paired): the UMI in
+//                  one mate or split over both (UmiPairHook); STAGE: its own, wider staging area, or none
 //   k_umi_rehash<READS>  the pairs of a full set into a larger one (<true>: with their reads)
 //   k_umi_uf_init / k_umi_link<false> / k_umi_link_lane / k_umi_roots   UMIs at Hamming distance 1 collapsed per feature
 //                  (f2q_umi_collapse): three launches over the set, the kernel boundary is the only hand-off
 //   k_umi_link<true> / k_umi_dir_spread / k_umi_dir_roots   the directional rule (f2q_umi_collapse_directional), after
 //                  k_umi_uf_init: four launches
-// The per-lane logic (UmiDev, umi_claim_at, umi_insert, umi_rehash_one, umi_codes, UmiHook, umi_find, uf_find / uf_union,
+// The per-lane logic (UmiDev, umi_claim_at, umi_insert, umi_rehash_one, umi_codes, UmiHook, umi_codes_paired, UmiPairHook, umi_find, uf_find / uf_union,
 // umi_neighbour, umi_link_one, umi_root_one, umi_link_dir_one, umi_dir_spread_one, umi_dir_root_one) lives in f2q_device.h.
 #pragma once
 
@@ -43,6 +45,59 @@ __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi(const RunDev *__r
         } else {
             const UmiHook<gbytes, READS> hook{&umi, run.thr, raw + so, r, raw + qo, qn, ust};
             general_read<gbytes, true, false>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, nullptr, 0, 0, hook);
+        }
+    }
+    // one wave per workgroup: at most one atomic per counter
+    const unsigned long long ok = wave_sum(ust[0]), bad = wave_sum(ust[1]), fresh = wave_sum(ust[2]);
+    if (threadIdx.x == 0) {
+        if (ok) acc_add(&umi.ctr[F2Q_UMI_READS], ok);
+        if (bad) acc_add(&umi.ctr[F2Q_UMI_FAILED], bad);
+        if (fresh) acc_add(&umi.ctr[F2Q_UMI_HELD], fresh);
+    }
+    __shared__ unsigned long long st_lds[8];
+    flush_stats(acc, st, st_lds, nullptr);
+}
+
+// The paired instance (f2q_set_umi_paired): the records are merged pairs (RawBlock::len1 / qlen1 set), every pair of the
+// sample comes here (the context clears its plan's fast-path flags), and the routine is general_read<.., PAIRED> with a
+// UmiPairHook.  A paired context has fixed windows only, so a pair touches its windows and its UMI parts: a few dozen
+// bytes of a merged record of about 600.  k_count_umi's own staging area (192 bytes per line) would send every 2 x 150
+// pair down the global-memory walk, so the layout is this kernel's own, and an A/B switch (F2Q_UMI_PAIR_STAGE):
+//   STAGE  the two merged lines staged in an area of F2Q_UMI_PAIR_WORDS words each (304 bytes: 2 x 150 bases at any
+//          misalignment), odd word stride per lane; a longer line is walked in global memory
+//   !STAGE no staging area at all: the touched bytes are read from global memory
+// (which one is the default, and the measured rates: DESIGN.md).  k_count_umi itself is not touched by any of this.
+#define F2Q_UMI_PAIR_WORDS 76u
+#define F2Q_UMI_PAIR_STAGE_DEFAULT false
+#define F2Q_UMI_PAIR_STRIDE (2u * F2Q_UMI_PAIR_WORDS + 1u)
+template <bool READS, bool STAGE>
+__global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi_pair(const RunDev *__restrict__ runp, const LibDev *__restrict__ libp,
+                                                                     EcDev ec, RawBlock rb, Accum acc, UmiDev umi)
+{
+    __shared__ uint32_t stage[STAGE ? F2Q_GEN_THREADS * F2Q_UMI_PAIR_STRIDE : 1u];
+    const RunDev &run = *runp;
+    const LibDev &lib = *libp;
+    unsigned long long st[5] = {0, 0, 0, 0, 0};
+    unsigned long long ust[3] = {0, 0, 0};
+    const auto raw = gp(rb.raw);
+    uint32_t *mine = stage + (STAGE ? threadIdx.x * F2Q_UMI_PAIR_STRIDE : 0u);
+    for (uint64_t i = (uint64_t)blockIdx.x * F2Q_GEN_THREADS + threadIdx.x; i < rb.n; i += (uint64_t)gridDim.x * F2Q_GEN_THREADS) {
+        const unsigned long long so = gp(rb.off)[i];
+        const int r = (int)gp(rb.len)[i], qn = (int)gp(rb.qlen)[i];
+        const unsigned long long qo = rb.qoff ? gp(rb.qoff)[i] : so + (unsigned long long)r;
+        const unsigned long long gi = rb.first_index + (rb.index ? gp(rb.index)[i] : i);
+        const int r1 = (int)gp(rb.len1)[i], qn1 = (int)gp(rb.qlen1)[i];
+        const uint32_t ms = (uint32_t)so & 3u, mq = (uint32_t)qo & 3u;
+        if (STAGE && r >= 0 && qn >= 0 && ms + (uint32_t)r <= 4u * F2Q_UMI_PAIR_WORDS && mq + (uint32_t)qn <= 4u * F2Q_UMI_PAIR_WORDS) {
+            stage_line(mine, raw, so, r);
+            stage_line(mine + F2Q_UMI_PAIR_WORDS, raw, qo, qn);
+            const uint8_t *sl = reinterpret_cast<const uint8_t *>(mine) + ms;
+            const uint8_t *ql = reinterpret_cast<const uint8_t *>(mine + F2Q_UMI_PAIR_WORDS) + mq;
+            const UmiPairHook<const uint8_t *, READS> hook{&umi, run.thr, sl, r, r1, ql, qn, qn1, ust};
+            general_read<const uint8_t *, true, true>(run, lib, ec, acc, sl, r, ql, qn, gi, st, nullptr, r1, qn1, hook);
+        } else {
+            const UmiPairHook<gbytes, READS> hook{&umi, run.thr, raw + so, r, r1, raw + qo, qn, qn1, ust};
+            general_read<gbytes, true, true>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, nullptr, r1, qn1, hook);
         }
     }
     // one wave per workgroup: at most one atomic per counter

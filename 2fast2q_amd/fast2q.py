@@ -104,7 +104,12 @@ def features_loader(guides):
 def _counter_kwargs(param):
     if param.get('paired'):                         # a paired context: the windows of mate 2 and its direction (f2q_set_mate2)
         plain = {k: v for k, v in param.items() if k != 'paired'}
-        return dict(_counter_kwargs(plain), start2=param['start2'], rc2=bool(param.get('rc2')))
+        kwargs = dict(_counter_kwargs(plain), start2=param['start2'], rc2=bool(param.get('rc2')))
+        if param.get('umi_paired'):                 # --umi1 / --umi2: a paired UMI context (f2q_set_umi_paired), part of the key too
+            kwargs['umi_paired'] = tuple(param['umi_paired'])
+            if param.get('umi_rule') == 'directional':
+                kwargs['umi_reads'] = True
+        return kwargs
     kwargs = dict(mode=param['Running Mode'], miss=param['miss'], phred=param['phred'], length=param['length'],
                   start=param['start'], upstream=param['upstream'], downstream=param['downstream'],
                   miss_search_up=param['miss_search_up'], miss_search_down=param['miss_search_down'],
@@ -229,6 +234,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         raise RuntimeError("--as: assignments are not merged across several ranks; run one process")
     if param.get('umi') and sharding.world().size > 1:
         raise RuntimeError("--umi: the UMI sets are not merged across several ranks; run one process")
+    if param.get('umi_paired') and sharding.world().size > 1:
+        raise RuntimeError("--umi1 / --umi2: the UMI sets are not merged across several ranks; run one process")
     ctx = _context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
@@ -256,7 +263,7 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             # every key's feature (f2q_ec_assign)
             acounts, stats = ctx.ec_assign()
             param.setdefault('assigned', {})[raw] = ([int(n) for n in acounts], ctx.ec_assigned())
-        if param.get('umi'):                        # distinct UMIs per feature and the two sample-level counters (f2q_read_umis)
+        if umi_length(param):                       # distinct UMIs per feature and the two sample-level counters (f2q_read_umis)
             umis, umi_reads, umi_failed = ctx.read_umis()
             # the sample's record: per kind of UMI_TABLES that was computed, a number per feature and the sample-level counters
             rec = param.setdefault('umi_counted', {})[raw] = {"umis": ([int(n) for n in umis], dict(umi_reads=umi_reads, umi_failed=umi_failed))}
@@ -358,7 +365,7 @@ def aligner(i, raw, features, param, reads_stats):
             csv_writer(os.path.join(param["directory"], sample.name + "_umi_reads.csv"),
                        [["#Feature", "Reads"] + [t[2] for t in kinds]] + [[name, *ns] for name, ns in both])
             if pair_table is not None:               # every (feature, UMI) pair with its reads, in f2q_umi_pairs' order
-                length = param['umi'][1]
+                length = umi_length(param)          # (--umi1 + --umi2: the concatenation as sequenced)
                 csv_writer(os.path.join(param["directory"], sample.name + "_umi_pairs.csv"),
                            [["#Feature", "UMI", "Reads"]] + [[names[f], umi_text(int(c), length), int(n)] for f, c, n in zip(*pair_table)])
     if not param['Progress bar']:
@@ -425,6 +432,9 @@ def initializer(cmd):
         print(f" Paired-end: mate 2 start position: {param['start2']}" + (" (mate 2 reverse-complemented)" if param['rc2'] else ""))
     if param.get('umi'):
         print(f" Distinct UMIs are counted per feature: UMI start position in the read: {param['umi'][0]}, length: {param['umi'][1]}bp")
+    for mate, part in enumerate(param.get('umi_paired') or (), 1):
+        if part:
+            print(f" Distinct UMIs are counted per feature: UMI part in mate {mate}, start position: {part[0]}, length: {part[1]}bp")
     if param.get('umi_mismatch'):
         print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
     if param.get('umi_rule') == 'directional':
@@ -469,6 +479,13 @@ def umi_text(codes, length):
     return "".join("ACGT"[(codes >> (2 * j)) & 3] for j in range(length))
 
 
+def umi_length(param):
+    """bases of the run's UMI (--umi, or --umi1 and --umi2 together), 0 without one"""
+    if param.get('umi'):
+        return param['umi'][1]
+    return sum(part[1] for part in param.get('umi_paired') or () if part)
+
+
 def parse_umi(text):
     """(S, L) of a --umi value, None for a malformed or out-of-range one"""
     m = re.fullmatch(r"\s*(\d+)\s*,\s*(\d+)\s*", str(text))
@@ -507,7 +524,9 @@ def input_parser(argv=None):
     ap.add_argument("--st2", help="With --pe: the start position(s) of the feature part(s) within mate 2")
     ap.add_argument("--rc2", nargs='?', const=True, help="With --pe: mate 2 is reverse-complemented before its parts are taken")
     ap.add_argument("--umi", help="S,L: every read carries a UMI of L bases (1-16) at position S; Counter mode also reports the distinct UMIs per feature (<name>_umi.csv)")
-    ap.add_argument("--mu", help="With --umi: mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")
+    ap.add_argument("--umi1", help="With --pe, S,L: the UMI (or its first part) is L bases at position S of mate 1")
+    ap.add_argument("--umi2", help="With --pe, S,L: the UMI (or its second part) is L bases at position S of mate 2 as sequenced (whatever --rc2 says); --umi1 and --umi2 together hold 16 bases at most")
+    ap.add_argument("--mu", help="With --umi (or --umi1 / --umi2): mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")
     ap.add_argument("--mur", help="With --umi and --mu 1: the rule UMIs are collapsed by, cluster (default) or directional. directional: a UMI absorbs a neighbouring UMI only when it has at least twice its reads minus one (<name>_umi_directional.csv)")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
@@ -563,14 +582,36 @@ def input_parser(argv=None):
             colourful_errors("FATAL", "--umi only has a meaning in Counter mode: it cannot be combined with --mo EC.")
             sys.exit(2)
         if args.pe is not None:
-            colourful_errors("FATAL", "--umi takes single reads: it cannot be combined with --pe.")
+            colourful_errors("FATAL", "--umi takes single reads: it cannot be combined with --pe. The UMI of a pair is named per mate with --umi1 S,L and / or --umi2 S,L.")
             sys.exit(2)
         p['umi'] = parse_umi(args.umi)
         if p['umi'] is None:
             colourful_errors("FATAL", f"--umi {args.umi}: expected S,L with a start S >= 0 and a length 1 <= L <= 16.")
             sys.exit(2)
+    if args.umi1 is not None or args.umi2 is not None:
+        given = " / ".join(f for f, v in (("--umi1", args.umi1), ("--umi2", args.umi2)) if v is not None)
+        if args.pe is None:
+            colourful_errors("FATAL", f"{given} only has a meaning with --pe: the UMI part of one mate of a pair (single reads: --umi).")
+            sys.exit(2)
+        if args.umi is not None:
+            colourful_errors("FATAL", f"{given} cannot be combined with --umi: --umi names the UMI of single reads.")
+            sys.exit(2)
+        if p['Running Mode'] != "C":
+            colourful_errors("FATAL", f"{given} only has a meaning in Counter mode: it cannot be combined with --mo EC.")
+            sys.exit(2)
+        parts = []
+        for flag, value in (("--umi1", args.umi1), ("--umi2", args.umi2)):
+            parts.append(None if value is None else parse_umi(value))
+            if value is not None and parts[-1] is None:
+                colourful_errors("FATAL", f"{flag} {value}: expected S,L with a start S >= 0 and a length 1 <= L <= 16.")
+                sys.exit(2)
+        if sum(part[1] for part in parts if part) > 16:
+            colourful_errors("FATAL", f"--umi1 {args.umi1} --umi2 {args.umi2}: the two parts together hold 16 bases at most.")
+            sys.exit(2)
+        p['umi_paired'] = tuple(parts)
+    any_umi = args.umi is not None or args.umi1 is not None or args.umi2 is not None
     if args.mu is not None:
-        if args.umi is None:
+        if not any_umi:
             colourful_errors("FATAL", "--mu only has a meaning with --umi: the mismatches allowed between two UMIs of one feature.")
             sys.exit(2)
         if args.mu not in ("0", "1"):
@@ -582,7 +623,7 @@ def input_parser(argv=None):
         if args.mur not in ("cluster", "directional"):
             colourful_errors("FATAL", f"--mur {args.mur}: expected cluster or directional.")
             sys.exit(2)
-        if args.umi is None or args.mu != "1":
+        if not any_umi or args.mu != "1":
             colourful_errors("FATAL", "--mur only has a meaning with --umi and --mu 1: the rule UMIs one base apart are collapsed by.")
             sys.exit(2)
         if args.mur == "directional":
@@ -614,6 +655,9 @@ def file_sizer_split(param):
         param["sequencing_files"] = {"len_files": 1, "preprocess_files": [param["seq_files"]], "files": [param["seq_files"]]}
         return param
     files = [p[0] for p in path_parser(param["seq_files"], ["*.gz", "*.fastq"])]
+    if param.get('umi_paired') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--umi1 / --umi2: the UMI sets are not merged across several ranks; run one process.")
+        sys.exit(2)
     if param.get('paired'):                                      # one sample per pair, named after its R1 file
         if sharding.world().size > 1:
             colourful_errors("FATAL", "--pe: paired files are not shared out over several ranks; run one process.")
@@ -712,6 +756,9 @@ def run_headers(param):
                   f"#Mate 2 reverse-complemented: {'yes' if param['rc2'] else 'no'}"]
     if param.get('umi'):
         lines.append(f"#UMI start position in the read, length: {param['umi'][0]},{param['umi'][1]}")
+    for mate, part in enumerate(param.get('umi_paired') or (), 1):
+        if part:
+            lines.append(f"#UMI in mate {mate}, start, length: {part[0]},{part[1]}")
     if param.get('umi_mismatch'):
         lines.append(f"#UMI mismatches collapsed: {param['umi_mismatch']}")
     if param.get('umi_rule') == 'directional':

@@ -370,6 +370,36 @@ int f2q_set_umi_reads(f2q_ctx *ctx, int32_t on);
 int f2q_umi_collapse_directional(f2q_ctx *ctx, int64_t *molecules, int64_t extra[4]);
 int f2q_umi_pairs(f2q_ctx *ctx, uint64_t cap, uint64_t *n, uint32_t *feature, uint32_t *codes, uint32_t *reads);
 
+/* ---- UMIs on paired-end samples ----------------------------------------------------------------
+ * Libraries with the feature at a fixed place in one mate and the UMI at the 5' end of the other, or split over both.
+ * f2q_set_umi_paired makes a paired Counter context (f2q_set_mate2, fixed windows) keep the same (feature, UMI) set:
+ * f2q_read_umis, f2q_umi_collapse, f2q_set_umi_reads, f2q_umi_collapse_directional, f2q_umi_pairs, the growth of the set
+ * and f2q_reset_counts work on it unchanged, through f2q_count_block_paired, f2q_block_from_fastq_paired +
+ * f2q_count_resident and f2q_count_file_paired (the set lives across the pieces of the files).
+ *
+ * The UMI of a pair has one or two parts.  Part 1 is [start1, start1 + length1) of mate 1, part 2 is
+ * [start2, start2 + length2) of mate 2; a length of 0 means no part in that mate.  Positions in mate 2 are positions in
+ * its own text AS SEQUENCED, whatever f2q_set_mate2's revcomp says: revcomp concerns the feature parts only, the UMI
+ * text is never complemented or reversed.  At least one part is present, length1 + length2 <= 16, each present part
+ * has a start >= 0 and a length >= 1.  The UMI is part 1 followed by part 2; in the set's 2-bit codes base j of that
+ * concatenation sits in bits 2j .. 2j+1 (f2q_umi_pairs' layout with length1 + length2 bases).
+ *
+ * A part is valid by f2q_set_umi's rule applied to its own mate, the per-mate rule the feature parts follow: all its
+ * bases lie inside that mate's rstrip()-ed sequence line, each is A/C/G/T (lower case counts), and the same positions
+ * of that mate's rstrip()-ed quality line are complete and pass --ph.  The UMI is valid when every present part is.
+ * A pair is decided exactly as without the call: an assigned pair with a valid UMI brings (feature, UMI), any other
+ * assigned pair counts as one with an invalid UMI -- counts, the five counters and every other output are unchanged,
+ * and f2q_read_umis' extra[0] + extra[1] == F2Q_PERFECT + F2Q_IMPERFECT.  The collapse rules see the concatenation as
+ * one string of length1 + length2 bases: a substitution in either part is one edge.
+ *
+ * The call comes once, after f2q_set_mate2 and before counting.  F2Q_ESTATE on a context that is not paired, on an
+ * Extract+Count context, on one that is a UMI context already, or after a counting call; F2Q_EINVAL when both lengths
+ * are 0, a start or a length is negative, a start is above 0x3FFFFFFF, or length1 + length2 > 16.  F2Q_UMI_SLOTS is
+ * honoured as by f2q_set_umi; f2q_set_umi_reads may follow.  f2q_set_umi on a paired context and f2q_set_mate2 on a UMI
+ * context stay F2Q_ESTATE, and so do the sharded calls with world > 1.  Every pair of the context takes the merged-record
+ * road (k_count_umi_pair); F2Q_UMI_PAIR_STAGE=0 / 1 picks that kernel's layout for A/B runs. */
+int f2q_set_umi_paired(f2q_ctx *ctx, int32_t start1, int32_t length1, int32_t start2, int32_t length2);
+
 #ifdef __cplusplus
 }
 #endif
