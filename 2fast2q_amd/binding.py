@@ -24,7 +24,7 @@ EXPORTS = (
     "f2q_set_assign_library", "f2q_ec_assign", "f2q_ec_fetch_assigned",
     "f2q_set_umi", "f2q_read_umis", "f2q_umi_collapse",
     "f2q_set_umi_reads", "f2q_umi_collapse_directional", "f2q_umi_pairs",
-    "f2q_set_umi_paired",
+    "f2q_set_umi_paired", "f2q_set_umi_header",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
@@ -176,6 +176,7 @@ def load(path=None):
     L.f2q_ec_fetch_assigned.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.f2q_set_umi.argtypes = [vp, C.c_int32, C.c_int32]
     L.f2q_set_umi_paired.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.f2q_set_umi_header.argtypes = [vp, C.c_int32, C.c_int32]
     L.f2q_read_umis.argtypes = [vp, i64p, i64p]
     L.f2q_umi_collapse.argtypes = [vp, C.c_int32, i64p, i64p]
     L.f2q_set_umi_reads.argtypes = [vp, C.c_int32]
@@ -261,9 +262,11 @@ class Counter:
     ``umi_paired=((S1, L1) or None, (S2, L2) or None)`` makes a paired context a UMI context (f2q_set_umi_paired): the UMI
     is mate 1's [S1, S1 + L1) followed by [S2, S2 + L2) of mate 2 as sequenced, whatever ``rc2`` says; ``umi_length`` is
     the total number of bases, and everything ``umi=`` offers works on it (``umi=`` itself stays single-read only).
+    ``umi_header=(sep, L)`` takes the UMI from the read header instead (f2q_set_umi_header): the L bases behind the last
+    ``sep`` (one character, or its byte value) of the read id, mate 1's on a paired context; ``umi_length`` answers L.
     """
 
-    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, **params):
+    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, umi_header=None, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -277,6 +280,7 @@ class Counter:
         self.paired = False
         self.umi = None
         self.umi_paired = None
+        self.umi_header = None
         self.umi_length = 0              # bases of a UMI (set_umi / set_umi_paired), 0: no UMI context
         self.umi_reads = False
         try:
@@ -286,6 +290,8 @@ class Counter:
                 self.set_umi(*umi)
             if umi_paired is not None:
                 self.set_umi_paired(*umi_paired)
+            if umi_header is not None:
+                self.set_umi_header(*umi_header)
             if umi_reads:
                 self.set_umi_reads(True)
         except BaseException:
@@ -356,6 +362,17 @@ class Counter:
         self._check(self._L.f2q_set_umi_paired(self._h, p1[0], p1[1], p2[0], p2[1]))
         self.umi_paired = (p1 if p1[1] else None, p2 if p2[1] else None)
         self.umi_length = p1[1] + p2[1]
+
+    def set_umi_header(self, sep, length):
+        """the UMI of every read (pair: of mate 1) is in its header (f2q_set_umi_header): ``length`` bases behind the last
+        ``sep`` of the read id; in place of set_umi / set_umi_paired, before counting"""
+        if isinstance(sep, (bytes, str)):
+            if len(sep) != 1:
+                raise ValueError(f"the header UMI separator is one character, not {sep!r}")
+            sep = ord(sep)
+        self._check(self._L.f2q_set_umi_header(self._h, int(sep), int(length)))
+        self.umi_header = (chr(int(sep)), int(length))
+        self.umi_length = int(length)
 
     def set_umi_reads(self, on=True):
         """keep the reads of every (feature, UMI) pair (f2q_set_umi_reads); after set_umi, before counting"""

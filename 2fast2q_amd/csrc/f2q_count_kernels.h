@@ -1871,6 +1871,8 @@ struct RawBlock {
     const unsigned long long *qoff;        // offset of the quality line, or nullptr: it follows the sequence
     const uint32_t *len, *qlen, *index;    // index: position inside the block (nullptr: == record id)
     const uint32_t *len1, *qlen1;          // paired-end blocks: the records are merged pairs, mate 1's share of len / qlen (else nullptr)
+    const unsigned long long *hdr_umi;    // a header-UMI context (f2q_set_umi_header): per record of the BLOCK (position index[i], or i), the
+                                           // codes of its header's UMI | F2Q_UMI_HDR_VALID, 0: invalid; the block owns it (else nullptr)
 };
 
 // One read per lane, byte-exact routine.  The routine walks the record byte by byte with dependent loads, so each lane

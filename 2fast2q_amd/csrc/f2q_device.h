@@ -1312,6 +1312,54 @@ struct UmiPairHook {
     }
 };
 
+// ---- the UMI in a read's header (f2q_set_umi_header): umi_tools extract / fastp ids, Illumina's last colon field ----
+// line = record line 0 without its '\n', n bytes.  The line is rstrip()-ed as the other three are, the read id ends before
+// the first space or tab, the tail is what follows the LAST `sep` of the id.  At most one '+' in the tail is skipped (a dual
+// UMI), wherever it stands; what is left must be exactly `length` bases A/C/G/T (lower case counts).  There is no quality
+// to test and a leading '@' is not asked for.  base j of the tail (the '+' not counted) goes to bits 2j .. 2j+1.
+// One forward pass: a tail that grows past length + 1 bytes can only be saved by a later separator.
+#define F2Q_UMI_HDR_VALID (1ull << 32)   // an entry of RawBlock::hdr_umi: the codes in bits 0 .. 31, this mark above them
+template <class P>
+F2Q_HD bool header_umi_codes(P line, uint32_t n, uint32_t sep, uint32_t length, uint32_t &codes)
+{
+    while (n > 0) {
+        const uint8_t c = line[n - 1];
+        if (c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == 0x0b || c == 0x0c) n--; else break;
+    }
+    bool seen = false, bad = false;
+    uint32_t w = 0, bases = 0, plus = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t c = line[i];
+        if (c == ' ' || c == '\t') break;
+        if (c == sep) { seen = true; bad = false; w = 0; bases = 0; plus = 0; continue; }
+        if (!seen || bad) continue;
+        if (c == '+') { if (++plus > 1u) bad = true; continue; }
+        const uint32_t b = base_code(up8(c));
+        if (b > 3u || bases >= length) { bad = true; continue; }
+        w |= b << (2u * bases++);
+    }
+    if (!seen || bad || bases != length) return false;
+    codes = w;
+    return true;
+}
+// the entry of one record: header_umi_codes' verdict as RawBlock::hdr_umi holds it (0: invalid)
+template <class P>
+F2Q_HD unsigned long long header_umi_entry(P line, uint32_t n, uint32_t sep, uint32_t length)
+{
+    uint32_t codes = 0;
+    return header_umi_codes(line, n, sep, length, codes) ? F2Q_UMI_HDR_VALID | codes : 0ull;
+}
+// UmiHook for a header UMI: the entry was decided at ingest (k_header_umi or the host packer), nothing is decoded here
+template <bool READS = false>
+struct UmiHeaderHook {
+    const UmiDev *u; unsigned long long entry; unsigned long long *ust;
+    F2Q_HD void assigned(uint32_t f) const
+    {
+        if (entry & F2Q_UMI_HDR_VALID) { ust[0]++; ust[2] += umi_insert<READS>(*u, f, (uint32_t)entry); }
+        else ust[1]++;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------
 // general path: one read given as raw bytes.  st[] = the 5 reference counters (thread-local).
 // ---------------------------------------------------------------------------------------------

@@ -471,7 +471,14 @@ inline void build_index(HostIndex &ix, const char *seqs, const uint32_t *offs, u
 // ---------------------------------------------------------------------------------------------
 // FASTQ framing (fastq_parser :324-328): '\n'-separated lines, rstrip(), 4 lines per record
 // ---------------------------------------------------------------------------------------------
-typedef RecT<const uint8_t *> Rec;
+// a framed record: the sequence and quality lines as the packers take them, and the span of the header line (line 0,
+// rstrip()-ed like the others) for a header-UMI context (f2q_set_umi_header); nothing else looks at it
+struct Rec : RecT<const uint8_t *> {
+    const uint8_t *hdr; uint32_t hlen;
+    Rec() : RecT<const uint8_t *>{nullptr, nullptr, 0, 0}, hdr(nullptr), hlen(0) {}
+    Rec(const uint8_t *s, const uint8_t *q, uint32_t l, uint32_t ql, const uint8_t *h = nullptr, uint32_t hl = 0)
+        : RecT<const uint8_t *>{s, q, l, ql}, hdr(h), hlen(hl) {}
+};
 
 inline uint32_t rstrip_len(const uint8_t *p, size_t n)
 {
@@ -492,7 +499,7 @@ inline size_t frame_fastq(const uint8_t *buf, size_t nbytes, std::vector<Rec> &o
         size_t eol = nl ? (size_t)(nl - buf) : nbytes;
         ln[k] = buf + pos; ll[k] = rstrip_len(buf + pos, eol - pos); k++;
         pos = nl ? eol + 1 : nbytes;
-        if (k == 4) { out.push_back(Rec{ln[1], ln[3], ll[1], ll[3]}); k = 0; consumed = pos; }
+        if (k == 4) { out.push_back(Rec{ln[1], ln[3], ll[1], ll[3], ln[0], ll[0]}); k = 0; consumed = pos; }
     }
     return consumed;
 }
@@ -556,6 +563,7 @@ struct HostPacked {
     std::vector<unsigned long long> g_off;     // per record: offset of seq in raw (qual follows at +len)
     std::vector<uint32_t> g_len, g_qlen, g_index;
     std::vector<uint32_t> g_len1, g_qlen1;     // paired-end: the record is a merged pair, these are mate 1's share of g_len / g_qlen
+    std::vector<unsigned long long> hdr_umi;   // a header-UMI context: per record of the block (header_umis), what k_header_umi writes
 };
 
 struct HostSink {
@@ -607,6 +615,13 @@ inline void pack_records(const PackPlan &pl, const std::vector<Rec> &recs, HostP
         }
     }
     pack_clean(pl, clean, rmax, [&](uint32_t i) -> const Rec & { return recs[i]; }, hp);
+}
+
+// The host twin of k_header_umi: the entry of each of the first n records (a pair: mate 1's), by the same function.
+inline void header_umis(const std::vector<Rec> &recs, size_t n, uint32_t sep, uint32_t length, std::vector<unsigned long long> &out)
+{
+    out.resize(n);
+    for (size_t i = 0; i < n; i++) out[i] = header_umi_entry<const uint8_t *>(recs[i].hdr, recs[i].hlen, sep, length);
 }
 
 // mate 2 as the run takes it: the line reversed, the sequence line complemented too (rc2), else as read

@@ -121,6 +121,7 @@ struct f2q_ctx {
         uint64_t rehashes = 0;
         bool reads_on = false;           // f2q_set_umi_reads: dev.reads[] lives and dies with dev.slots[] (set_allocs)
         bool pair_stage = false;         // f2q_set_umi_paired: k_count_umi_pair<.., true> (F2Q_UMI_PAIR_STAGE)
+        int32_t hdr_sep = 0;             // f2q_set_umi_header: the separator byte (0: the UMI is not in the header); the length is dev.length
     } umi;
     bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
@@ -571,6 +572,24 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
     if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
         return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
     c->umi.dev.start = start; c->umi.dev.length = length;
+    umi_enable(c);
+    return F2Q_OK;
+}
+
+// The UMI in the read header (include/f2q.h): the last `sep`-separated field of the read id, `length` bases.  On a paired
+// context the header is mate 1's.  The ingest drivers run k_header_umi on the framed text (the host twin: header_umis) and
+// the block carries the result; the counting kernels are the HDR instances of k_count_umi / k_count_umi_pair.
+extern "C" int f2q_set_umi_header(f2q_ctx *c, int32_t sep, int32_t length)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_header takes a Counter context: Extract+Count assigns no read to a feature");
+    if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_header comes once, in place of f2q_set_umi / f2q_set_umi_paired and before counting");
+    const bool alnum = (sep >= '0' && sep <= '9') || (sep >= 'A' && sep <= 'Z') || (sep >= 'a' && sep <= 'z');
+    if (sep < 33 || sep > 126 || alnum || sep == '+' || length < 1 || length > F2Q_UMI_MAXLEN)
+        return fail(c, F2Q_EINVAL, "the header UMI needs a separator that is one printable ASCII byte (33 .. 126), not alphanumeric and not '+', and a length of 1 .. 16 bases");
+    UmiDev &u = c->umi.dev;
+    u.start = 0; u.length = length; u.start1 = u.len1 = u.start2 = u.len2 = 0; u.rc2 = c->rc2 ? 1 : 0;
+    c->umi.hdr_sep = sep;
     umi_enable(c);
     return F2Q_OK;
 }
@@ -1281,7 +1300,16 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
     const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
     if (c->umi.on) {                                             // the same road with the (feature, UMI) set (f2q_set_umi)
         if ((rc = umi_reserve(c, rb.n))) return rc;
-        if (rb.len1) {                                           // merged pairs (f2q_set_umi_paired): a pair is one record
+        if (c->umi.hdr_sep) {                                    // the UMI comes from the header (f2q_set_umi_header): rb.hdr_umi
+            if (!rb.hdr_umi) return fail(c, F2Q_ESTATE, "a block without header UMIs on a header-UMI context");
+            const bool keep = c->umi.dev.reads != nullptr;
+#define F2Q_LAUNCH_UMI_HDR(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev)
+            if (!rb.len1) { if (keep) F2Q_LAUNCH_UMI_HDR(k_count_umi<true, true>); else F2Q_LAUNCH_UMI_HDR(k_count_umi<false, true>); }
+            else if (keep) F2Q_LAUNCH_UMI_HDR(k_count_umi_pair<true, F2Q_UMI_PAIR_STAGE_DEFAULT, true>);
+            else F2Q_LAUNCH_UMI_HDR(k_count_umi_pair<false, F2Q_UMI_PAIR_STAGE_DEFAULT, true>);
+#undef F2Q_LAUNCH_UMI_HDR
+        }
+        else if (rb.len1) {                                      // merged pairs (f2q_set_umi_paired): a pair is one record
             if (!c->umi.dev.len1 && !c->umi.dev.len2) return fail(c, F2Q_ESTATE, "a block of pairs on a single-read UMI context");
             const bool keep = c->umi.dev.reads != nullptr;
 #define F2Q_LAUNCH_UMI_PAIR(R, S) hipLaunchKernelGGL((k_count_umi_pair<R, S>), dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev)
@@ -1293,7 +1321,7 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
         else hipLaunchKernelGGL(k_count_umi<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev);
         HIPC(c, hipGetLastError());
         launches++;
-        EC_POINT(c, rb.len1 ? "k_count_umi_pair" : "k_count_umi");
+        EC_POINT(c, c->umi.hdr_sep ? (rb.len1 ? "k_count_umi_pair (header)" : "k_count_umi (header)") : rb.len1 ? "k_count_umi_pair" : "k_count_umi");
         return F2Q_OK;
     }
     if (rb.len1) hipLaunchKernelGGL(k_count_general<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
@@ -1433,6 +1461,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
     if (!k0) { k0 = c->ev_k0; k1 = c->ev_k1; }          // (a queued step brings its own pair)
     if (c->prm.mode == 0 && !c->have_lib) return fail(c, F2Q_ESTATE, "f2q_set_features must be called before counting in Counter mode");
     if (c->umi.on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
+    if (c->umi.hdr_sep && b->rb.n && !b->rb.hdr_umi) return fail(c, F2Q_ESTATE, "the block was made before f2q_set_umi_header (or without headers): its records carry no header UMI");
     c->counted = true;
     Accum acc{c->acc_d, c->acc_d + (c->acc_n - 5), nullptr, nullptr, nullptr, nullptr};
 #ifdef F2Q_STAMP
@@ -1674,6 +1703,12 @@ static int block_from_packed(f2q_ctx *c, const HostPacked &hp, uint64_t n_reads,
                 if ((rc = dev_upload(c, hp.g_qlen1.data(), hp.g_qlen1.size(), &dq1, b->allocs))) break;
                 b->rb.len1 = dl1; b->rb.qlen1 = dq1;
             }
+            if (!hp.hdr_umi.empty()) {                   // a header-UMI context: one entry per record of the block
+                unsigned long long *dh;
+                if ((rc = dev_upload(c, hp.hdr_umi.data(), hp.hdr_umi.size(), &dh, b->allocs))) break;
+                b->rb.hdr_umi = dh;
+                b->dev_bytes += hp.hdr_umi.size() * 8;
+            }
             b->dev_bytes += hp.raw.size() + hp.g_len.size() * 20;
             b->raw_key_bytes = hp.raw.size();
         }
@@ -1689,6 +1724,7 @@ static int block_from_records(f2q_ctx *c, const std::vector<Rec> &recs, f2q_bloc
 {
     HostPacked hp;
     pack_records(c->plan, recs, hp);
+    if (c->umi.hdr_sep) header_umis(recs, recs.size(), (uint32_t)c->umi.hdr_sep, (uint32_t)c->umi.dev.length, hp.hdr_umi);
     return block_from_packed(c, hp, recs.size(), out);
 }
 
@@ -1781,6 +1817,39 @@ static int alloc_tile_planes(f2q_ctx *c, f2q_block *b, std::vector<void *> &own,
     return F2Q_OK;
 }
 
+// ---- the UMI in the read header (f2q_set_umi_header) ----------------------------------------------------------------
+// The array a header-UMI context's raw records take their UMI from (RawBlock::hdr_umi): one entry per record of the text,
+// written by k_header_umi on the stream, owned by the block (`own`).  Nothing is launched on any other context.
+static int header_umis_device(f2q_ctx *c, const FramedText &ft, uint32_t n_rec, std::vector<void *> &own, unsigned long long **out)
+{
+    *out = nullptr;
+    if (!c->umi.hdr_sep) return F2Q_OK;
+    HeaderUmiDev d{};
+    d.text = ft.text; d.line_start = ft.ls; d.n_records = n_rec; d.sep = (uint32_t)c->umi.hdr_sep; d.length = (uint32_t)c->umi.dev.length;
+    if (int rc = dev_alloc(c, (size_t)n_rec, &d.out, own)) return rc;
+    hipLaunchKernelGGL(k_header_umi, dim3((n_rec + F2Q_ING_THREADS - 1u) / F2Q_ING_THREADS), dim3(F2Q_ING_THREADS), 0, c->stream, d);
+    HIPC(c, hipGetLastError());
+    EC_POINT(c, "k_header_umi");
+    *out = d.out;
+    return F2Q_OK;
+}
+// F2Q_TRACE=1: HIP-event times of the ingest kernels of one text (k_classify, k_header_umi, k_pack), printed once the block
+// is made; without it nothing is created or recorded
+struct IngestTrace {
+    f2q_ctx *c; hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    explicit IngestTrace(f2q_ctx *ctx) : c(ctx) { if (c->trace) for (hipEvent_t &e : ev) if (hipEventCreate(&e) != hipSuccess) e = nullptr; }
+    ~IngestTrace() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    void mark(int i) { if (ev[i]) (void)hipEventRecord(ev[i], c->stream); }
+    void print(uint32_t n_rec, bool header)             // after the stream has been waited for
+    {
+        if (!ev[0]) return;
+        float ms[3] = {0, 0, 0};
+        for (int k = 0; k < 3; k++) if (k != 1 || header) (void)hipEventElapsedTime(&ms[k], ev[2 * k], ev[2 * k + 1]);
+        fprintf(stderr, "[f2q trace] ingest kernels: %u records, k_classify %.4f ms, k_header_umi %.4f ms, k_pack %.4f ms\n", n_rec, ms[0], ms[1], ms[2]);
+    }
+    IngestTrace(const IngestTrace &) = delete;
+};
+
 // Both device ingest drivers keep their scratch in `tmp` and what the block will own in `own` until they hand the block
 // out: any return before that waits for the stream and frees both.
 static int block_from_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbytes, size_t *consumed, f2q_block **out,
@@ -1808,8 +1877,15 @@ static int block_from_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbyte
     if ((rc = dev_alloc(c, (size_t)n_rec + 1, &d_before, tmp.v))) return rc;
     if ((rc = dev_alloc(c, (size_t)4, &ing.meta, tmp.v, 0))) return rc;
     const unsigned igrid = (unsigned)((n_rec + F2Q_ING_THREADS - 1u) / F2Q_ING_THREADS);
+    IngestTrace trace(c);
+    trace.mark(0);
     hipLaunchKernelGGL(k_classify, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan);
     HIPC(c, hipGetLastError());
+    trace.mark(1);
+    unsigned long long *d_hdr;
+    trace.mark(2);
+    if ((rc = header_umis_device(c, ft, n_rec, own.v, &d_hdr))) return rc;
+    trace.mark(3);
     if ((rc = exclusive_scan(c, ing.clean, d_before, n_rec + 1u, tmp.v))) return rc;
     uint32_t n_clean = 0, rmax_in = 0;
     HIPC(c, hipMemcpyAsync(&n_clean, d_before + n_rec, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1826,14 +1902,17 @@ static int block_from_text_device(f2q_ctx *c, const uint8_t *fastq, size_t nbyte
         for (uint32_t **p : {&o.g_len, &o.g_qlen, &o.g_index})
             if ((rc = dev_alloc(c, (size_t)n_dirty, p, own.v))) return rc;
         b->rb.n = n_dirty; b->rb.raw = ft.text; b->rb.off = o.g_off; b->rb.qoff = o.g_qoff; b->rb.len = o.g_len;
-        b->rb.qlen = o.g_qlen; b->rb.index = o.g_index;
-        b->dev_bytes += nbytes;
+        b->rb.qlen = o.g_qlen; b->rb.index = o.g_index; b->rb.hdr_umi = d_hdr;
+        b->dev_bytes += nbytes + (d_hdr ? (uint64_t)n_rec * 8 : 0);
         b->raw_key_bytes = nbytes;                    // the records point into the text: no key is longer than its record
     }
     b->n_general = n_dirty;
+    trace.mark(4);
     hipLaunchKernelGGL(k_pack, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan, d_before, o);
     HIPC(c, hipGetLastError());
+    trace.mark(5);
     HIPC(c, hipStreamSynchronize(c->stream));         // scratch dies with this frame
+    trace.print(n_rec, d_hdr != nullptr);
     b->allocs.swap(own.v); *out = b.release();
     return F2Q_OK;
 }
@@ -1952,6 +2031,8 @@ static int block_from_pairs_device(f2q_ctx *c, const uint8_t *fq1, size_t n1, co
     const unsigned igrid = (unsigned)((n_rec + F2Q_ING_THREADS - 1u) / F2Q_ING_THREADS);
     hipLaunchKernelGGL(k_classify_paired, dim3(igrid), dim3(F2Q_ING_THREADS), 0, c->stream, ing, c->plan);
     HIPC(c, hipGetLastError());
+    unsigned long long *d_hdr;                       // the UMI of a pair is the one in mate 1's header
+    if ((rc = header_umis_device(c, t1, n_rec, own.v, &d_hdr))) return rc;
     if ((rc = exclusive_scan(c, ing.clean, d_before, n_rec + 1u, tmp.v))) return rc;
     if ((rc = exclusive_scan(c, ing.raw_bytes, d_raw_before, n_rec + 1u, tmp.v))) return rc;
     // 32-bit sizes with EVERY pair raw (a paired UMI context): a merged record holds only bytes of its four lines, each text
@@ -1971,8 +2052,8 @@ static int block_from_pairs_device(f2q_ctx *c, const uint8_t *fq1, size_t n1, co
         for (uint32_t **p : {&o.g_len, &o.g_qlen, &o.g_len1, &o.g_qlen1, &o.g_index})
             if ((rc = dev_alloc(c, (size_t)n_dirty, p, own.v))) return rc;
         b->rb.n = n_dirty; b->rb.raw = o.raw; b->rb.off = o.g_off; b->rb.len = o.g_len; b->rb.qlen = o.g_qlen;
-        b->rb.len1 = o.g_len1; b->rb.qlen1 = o.g_qlen1; b->rb.index = o.g_index;
-        b->dev_bytes += (uint64_t)raw_total + (uint64_t)n_dirty * 28;
+        b->rb.len1 = o.g_len1; b->rb.qlen1 = o.g_qlen1; b->rb.index = o.g_index; b->rb.hdr_umi = d_hdr;
+        b->dev_bytes += (uint64_t)raw_total + (uint64_t)n_dirty * 28 + (d_hdr ? (uint64_t)n_rec * 8 : 0);
         b->raw_key_bytes = raw_total;                // no key is longer than its merged record
     }
     b->n_general = n_dirty;
@@ -2008,6 +2089,7 @@ static int pair_block(f2q_ctx *c, const uint8_t *fq1, size_t n1, const uint8_t *
     *used1 = skip_lines(fq1, n1, 0, 4 * (uint64_t)n).pos; *used2 = skip_lines(fq2, n2, 0, 4 * (uint64_t)n).pos;
     HostPacked hp;
     pack_pairs(c->plan, r1, r2, hp);
+    if (c->umi.hdr_sep) header_umis(r1, n, (uint32_t)c->umi.hdr_sep, (uint32_t)c->umi.dev.length, hp.hdr_umi);
     return block_from_packed(c, hp, n, out);
 }
 
@@ -3056,6 +3138,7 @@ extern "C" int f2q_synth_create(f2q_ctx *c, const f2q_synth *s, f2q_block **out)
     if (!c || !s || !out) return F2Q_EINVAL;
     HIPC(c, hipSetDevice(c->device));
     if (int rc = single_only(c)) return rc;
+    if (c->umi.hdr_sep) return fail(c, F2Q_ESTATE, "f2q_synth_create on a header-UMI context (f2q_set_umi_header): synthetic blocks have no headers");
     SynthDev d; int rc = synth_to_dev(c, s, d);
     if (rc) return rc;
     const int R = d.read_len;

@@ -3,12 +3,14 @@
 //                  (<false>: the set alone; <true>: reads per pair too, f2q_set_umi_reads)
 //   k_count_umi_pair<READS, STAGE>   the same on the merged records of a paired context (f2q_set_umi_paired): the UMI in
 //                  one mate or split over both (UmiPairHook); STAGE: its own, wider staging area, or none
+//   k_header_umi   the UMI in every record's header line (f2q_set_umi_header), at ingest: one entry per record of the block;
+//                  k_count_umi<READS, true> / k_count_umi_pair<READS, STAGE, true> then take the UMI from that array
 //   k_umi_rehash<READS>  the pairs of a full set into a larger one (<true>: with their reads)
 //   k_umi_uf_init / k_umi_link<false> / k_umi_link_lane / k_umi_roots   UMIs at Hamming distance 1 collapsed per feature
 //                  (f2q_umi_collapse): three launches over the set, the kernel boundary is the only hand-off
 //   k_umi_link<true> / k_umi_dir_spread / k_umi_dir_roots   the directional rule (f2q_umi_collapse_directional), after
 //                  k_umi_uf_init: four launches
-// The per-lane logic (UmiDev, umi_claim_at, umi_insert, umi_rehash_one, umi_codes, UmiHook, umi_codes_paired, UmiPairHook, umi_find, uf_find / uf_union,
+// The per-lane logic (UmiDev, umi_claim_at, umi_insert, umi_rehash_one, umi_codes, UmiHook, umi_codes_paired, UmiPairHook, header_umi_codes, UmiHeaderHook, umi_find, uf_find / uf_union,
 // umi_neighbour, umi_link_one, umi_root_one, umi_link_dir_one, umi_dir_spread_one, umi_dir_root_one) lives in f2q_device.h.
 #pragma once
 
@@ -18,7 +20,9 @@
 // launch could bring a new pair and it would still be at most half full.
 // READS: every read with a valid UMI also adds 1 to reads[slot of its pair] (UmiHook<P, true>); false is the only
 // instance launched unless f2q_set_umi_reads asked for reads.
-template <bool READS>
+// HDR (f2q_set_umi_header): the UMI was read from the record's header at ingest (k_header_umi), the hook takes codes and
+// validity from rb.hdr_umi[position of the record in the block] and decodes nothing; everything after the hook is the same.
+template <bool READS, bool HDR = false>
 __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi(const RunDev *__restrict__ runp, const LibDev *__restrict__ libp,
                                                                 EcDev ec, RawBlock rb, Accum acc, UmiDev umi)
 {
@@ -34,14 +38,23 @@ __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi(const RunDev *__r
         const int r = (int)gp(rb.len)[i], qn = (int)gp(rb.qlen)[i];
         const unsigned long long qo = rb.qoff ? gp(rb.qoff)[i] : so + (unsigned long long)r;
         const unsigned long long gi = rb.first_index + (rb.index ? gp(rb.index)[i] : i);
+        const unsigned long long he = HDR ? gp(rb.hdr_umi)[rb.index ? gp(rb.index)[i] : i] : 0ull;
         const uint32_t ms = (uint32_t)so & 3u, mq = (uint32_t)qo & 3u;
         if (r >= 0 && qn >= 0 && ms + (uint32_t)r <= 4u * F2Q_GEN_WORDS && mq + (uint32_t)qn <= 4u * F2Q_GEN_WORDS) {
             stage_line(mine, raw, so, r);
             stage_line(mine + F2Q_GEN_WORDS, raw, qo, qn);
             const uint8_t *sl = reinterpret_cast<const uint8_t *>(mine) + ms;
             const uint8_t *ql = reinterpret_cast<const uint8_t *>(mine + F2Q_GEN_WORDS) + mq;
-            const UmiHook<const uint8_t *, READS> hook{&umi, run.thr, sl, r, ql, qn, ust};
-            general_read<const uint8_t *, true, false>(run, lib, ec, acc, sl, r, ql, qn, gi, st, nullptr, 0, 0, hook);
+            if constexpr (HDR) {
+                const UmiHeaderHook<READS> hook{&umi, he, ust};
+                general_read<const uint8_t *, true, false>(run, lib, ec, acc, sl, r, ql, qn, gi, st, nullptr, 0, 0, hook);
+            } else {
+                const UmiHook<const uint8_t *, READS> hook{&umi, run.thr, sl, r, ql, qn, ust};
+                general_read<const uint8_t *, true, false>(run, lib, ec, acc, sl, r, ql, qn, gi, st, nullptr, 0, 0, hook);
+            }
+        } else if constexpr (HDR) {
+            const UmiHeaderHook<READS> hook{&umi, he, ust};
+            general_read<gbytes, true, false>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, nullptr, 0, 0, hook);
         } else {
             const UmiHook<gbytes, READS> hook{&umi, run.thr, raw + so, r, raw + qo, qn, ust};
             general_read<gbytes, true, false>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, nullptr, 0, 0, hook);
@@ -70,7 +83,9 @@ __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi(const RunDev *__r
 #define F2Q_UMI_PAIR_WORDS 76u
 #define F2Q_UMI_PAIR_STAGE_DEFAULT false
 #define F2Q_UMI_PAIR_STRIDE (2u * F2Q_UMI_PAIR_WORDS + 1u)
-template <bool READS, bool STAGE>
+// HDR (f2q_set_umi_header on a paired context): the UMI of a pair is the one in mate 1's header, taken from rb.hdr_umi as
+// in k_count_umi<.., true>; the merged record is then read for the feature parts alone.
+template <bool READS, bool STAGE, bool HDR = false>
 __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi_pair(const RunDev *__restrict__ runp, const LibDev *__restrict__ libp,
                                                                      EcDev ec, RawBlock rb, Accum acc, UmiDev umi)
 {
@@ -87,14 +102,23 @@ __global__ __launch_bounds__(F2Q_GEN_THREADS) void k_count_umi_pair(const RunDev
         const unsigned long long qo = rb.qoff ? gp(rb.qoff)[i] : so + (unsigned long long)r;
         const unsigned long long gi = rb.first_index + (rb.index ? gp(rb.index)[i] : i);
         const int r1 = (int)gp(rb.len1)[i], qn1 = (int)gp(rb.qlen1)[i];
+        const unsigned long long he = HDR ? gp(rb.hdr_umi)[rb.index ? gp(rb.index)[i] : i] : 0ull;
         const uint32_t ms = (uint32_t)so & 3u, mq = (uint32_t)qo & 3u;
         if (STAGE && r >= 0 && qn >= 0 && ms + (uint32_t)r <= 4u * F2Q_UMI_PAIR_WORDS && mq + (uint32_t)qn <= 4u * F2Q_UMI_PAIR_WORDS) {
             stage_line(mine, raw, so, r);
             stage_line(mine + F2Q_UMI_PAIR_WORDS, raw, qo, qn);
             const uint8_t *sl = reinterpret_cast<const uint8_t *>(mine) + ms;
             const uint8_t *ql = reinterpret_cast<const uint8_t *>(mine + F2Q_UMI_PAIR_WORDS) + mq;
-            const UmiPairHook<const uint8_t *, READS> hook{&umi, run.thr, sl, r, r1, ql, qn, qn1, ust};
-            general_read<const uint8_t *, true, true>(run, lib, ec, acc, sl, r, ql, qn, gi, st, nullptr, r1, qn1, hook);
+            if constexpr (HDR) {
+                const UmiHeaderHook<READS> hook{&umi, he, ust};
+                general_read<const uint8_t *, true, true>(run, lib, ec, acc, sl, r, ql, qn, gi, st, nullptr, r1, qn1, hook);
+            } else {
+                const UmiPairHook<const uint8_t *, READS> hook{&umi, run.thr, sl, r, r1, ql, qn, qn1, ust};
+                general_read<const uint8_t *, true, true>(run, lib, ec, acc, sl, r, ql, qn, gi, st, nullptr, r1, qn1, hook);
+            }
+        } else if constexpr (HDR) {
+            const UmiHeaderHook<READS> hook{&umi, he, ust};
+            general_read<gbytes, true, true>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, nullptr, r1, qn1, hook);
         } else {
             const UmiPairHook<gbytes, READS> hook{&umi, run.thr, raw + so, r, r1, raw + qo, qn, qn1, ust};
             general_read<gbytes, true, true>(run, lib, ec, acc, raw + so, r, raw + qo, qn, gi, st, nullptr, r1, qn1, hook);
@@ -222,4 +246,35 @@ __global__ __launch_bounds__(256) void k_umi_dir_roots(UmiDev u, const uint32_t 
         if (flagged) acc_add(&tot[0], flagged);
         if (reads) acc_add(&tot[1], reads);
     }
+}
+
+// ---- f2q_set_umi_header: the UMI in the header line ------------------------------------------------------------------
+// After frame_text_device, on the text the raw records point into (a pair: mate 1's text).  k_classify's pattern: the 64
+// records of a wave are neighbours in the text, so the wave copies the stretch from its first header to the end of its last
+// one into LDS once (stage_span: 16-byte loads, every byte fetched once) and each lane walks its own header there
+// (header_umi_codes); a stretch longer than the staging area is walked in global memory.  out[r] = the entry of record r
+// (RawBlock::hdr_umi).  Line 4r is never the text's last line (the record is complete), so line_start[4r + 1] - 1 is the
+// header's '\n' itself and every byte read lies inside the text.
+struct HeaderUmiDev {
+    const uint8_t *text; const uint32_t *line_start; uint32_t n_records;
+    uint32_t sep, length;
+    unsigned long long *out;                     // [n_records]
+};
+__global__ __launch_bounds__(F2Q_ING_THREADS) void k_header_umi(HeaderUmiDev d)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t stage[F2Q_ING_LDS];
+    const uint32_t r0 = blockIdx.x * F2Q_ING_THREADS, r = r0 + threadIdx.x;
+    const uint32_t n_act = d.n_records - r0 < F2Q_ING_THREADS ? d.n_records - r0 : F2Q_ING_THREADS;
+    const bool live = r < d.n_records;
+    const auto ls = gp(d.line_start);
+    const uint32_t rr = live ? r : d.n_records - 1u;
+    const uint32_t s = ls[4u * rr], e = ls[4u * rr + 1u] - 1u;
+    const uint32_t lo = __shfl(s, 0, 64), hi = __shfl(e, (int)n_act - 1, 64);
+    const bool fits = hi >= lo && hi - (lo & ~15u) <= F2Q_ING_LDS;
+    unsigned long long entry = 0;
+    if (fits) {
+        stage_span(stage, gp(d.text), lo, hi);
+        if (live) entry = header_umi_entry<const uint8_t *>(stage + (s - (lo & ~15u)), e - s, d.sep, d.length);
+    } else if (live) entry = header_umi_entry<gbytes>(gp(d.text) + s, e - s, d.sep, d.length);
+    if (live) gpw(d.out)[r] = entry;
 }

@@ -109,7 +109,7 @@ def _counter_kwargs(param):
             kwargs['umi_paired'] = tuple(param['umi_paired'])
             if param.get('umi_rule') == 'directional':
                 kwargs['umi_reads'] = True
-        return kwargs
+        return kwargs                               # (--umih: the plain keys carry it; the UMI of a pair is in mate 1's header)
     kwargs = dict(mode=param['Running Mode'], miss=param['miss'], phred=param['phred'], length=param['length'],
                   start=param['start'], upstream=param['upstream'], downstream=param['downstream'],
                   miss_search_up=param['miss_search_up'], miss_search_down=param['miss_search_down'],
@@ -118,6 +118,10 @@ def _counter_kwargs(param):
     if param.get('umi'):                            # a UMI context (f2q_set_umi); part of the key contexts are kept under
         kwargs['umi'] = tuple(param['umi'])         # (--mu is not: collapsing changes no context)
         if param.get('umi_rule') == 'directional':  # --mur directional: the context keeps the reads of every pair (f2q_set_umi_reads)
+            kwargs['umi_reads'] = True
+    if param.get('umi_header'):                     # --umih: the UMI is in the read header (f2q_set_umi_header)
+        kwargs['umi_header'] = tuple(param['umi_header'])
+        if param.get('umi_rule') == 'directional':
             kwargs['umi_reads'] = True
     return kwargs
 
@@ -236,6 +240,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         raise RuntimeError("--umi: the UMI sets are not merged across several ranks; run one process")
     if param.get('umi_paired') and sharding.world().size > 1:
         raise RuntimeError("--umi1 / --umi2: the UMI sets are not merged across several ranks; run one process")
+    if param.get('umi_header') and sharding.world().size > 1:
+        raise RuntimeError("--umih: the UMI sets are not merged across several ranks; run one process")
     ctx = _context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
@@ -435,6 +441,8 @@ def initializer(cmd):
     for mate, part in enumerate(param.get('umi_paired') or (), 1):
         if part:
             print(f" Distinct UMIs are counted per feature: UMI part in mate {mate}, start position: {part[0]}, length: {part[1]}bp")
+    if param.get('umi_header'):
+        print(f" Distinct UMIs are counted per feature: UMI in the read header, behind the last '{param['umi_header'][0]}' of the read id, length: {param['umi_header'][1]}bp")
     if param.get('umi_mismatch'):
         print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
     if param.get('umi_rule') == 'directional':
@@ -480,10 +488,24 @@ def umi_text(codes, length):
 
 
 def umi_length(param):
-    """bases of the run's UMI (--umi, or --umi1 and --umi2 together), 0 without one"""
+    """bases of the run's UMI (--umi, --umih, or --umi1 and --umi2 together), 0 without one"""
     if param.get('umi'):
         return param['umi'][1]
+    if param.get('umi_header'):
+        return param['umi_header'][1]
     return sum(part[1] for part in param.get('umi_paired') or () if part)
+
+
+def parse_umih(text):
+    """(separator, L) of a --umih value SEP,L, split at the last comma; a string that says what is wrong with it otherwise"""
+    sep, comma, length = str(text).rpartition(",")
+    if not comma or len(sep) != 1 or not re.fullmatch(r"\s*\d+\s*", length):
+        return "expected SEP,L: one separator character, a comma, the number of bases"
+    if not 33 <= ord(sep) <= 126 or sep.isalnum() or sep == "+":
+        return f"the separator {sep!r} must be one printable ASCII character that is not a letter, a digit or '+'"
+    if not 1 <= int(length) <= 16:
+        return "the length L must be between 1 and 16"
+    return sep, int(length)
 
 
 def parse_umi(text):
@@ -526,7 +548,8 @@ def input_parser(argv=None):
     ap.add_argument("--umi", help="S,L: every read carries a UMI of L bases (1-16) at position S; Counter mode also reports the distinct UMIs per feature (<name>_umi.csv)")
     ap.add_argument("--umi1", help="With --pe, S,L: the UMI (or its first part) is L bases at position S of mate 1")
     ap.add_argument("--umi2", help="With --pe, S,L: the UMI (or its second part) is L bases at position S of mate 2 as sequenced (whatever --rc2 says); --umi1 and --umi2 together hold 16 bases at most")
-    ap.add_argument("--mu", help="With --umi (or --umi1 / --umi2): mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")
+    ap.add_argument("--umih", help="SEP,L: the UMI of every read is in its header, the L bases (1-16) behind the last SEP of the read id, e.g. _,8 after umi_tools extract / fastp --umi, :,8 for an Illumina index-read UMI; with --pe: mate 1's header. Takes the place of --umi / --umi1 / --umi2")
+    ap.add_argument("--mu", help="With --umi (or --umih, --umi1 / --umi2): mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")
     ap.add_argument("--mur", help="With --umi and --mu 1: the rule UMIs are collapsed by, cluster (default) or directional. directional: a UMI absorbs a neighbouring UMI only when it has at least twice its reads minus one (<name>_umi_directional.csv)")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
@@ -609,7 +632,20 @@ def input_parser(argv=None):
             colourful_errors("FATAL", f"--umi1 {args.umi1} --umi2 {args.umi2}: the two parts together hold 16 bases at most.")
             sys.exit(2)
         p['umi_paired'] = tuple(parts)
-    any_umi = args.umi is not None or args.umi1 is not None or args.umi2 is not None
+    if args.umih is not None:
+        others = [f for f, v in (("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2)) if v is not None]
+        if others:
+            colourful_errors("FATAL", f"--umih cannot be combined with {' / '.join(others)}: a run has one source of UMIs, the read header or the read.")
+            sys.exit(2)
+        if p['Running Mode'] != "C":
+            colourful_errors("FATAL", "--umih only has a meaning in Counter mode: it cannot be combined with --mo EC.")
+            sys.exit(2)
+        parsed = parse_umih(args.umih)
+        if isinstance(parsed, str):
+            colourful_errors("FATAL", f"--umih {args.umih}: {parsed}.")
+            sys.exit(2)
+        p['umi_header'] = parsed
+    any_umi = args.umi is not None or args.umi1 is not None or args.umi2 is not None or args.umih is not None
     if args.mu is not None:
         if not any_umi:
             colourful_errors("FATAL", "--mu only has a meaning with --umi: the mismatches allowed between two UMIs of one feature.")
@@ -657,6 +693,9 @@ def file_sizer_split(param):
     files = [p[0] for p in path_parser(param["seq_files"], ["*.gz", "*.fastq"])]
     if param.get('umi_paired') and sharding.world().size > 1:
         colourful_errors("FATAL", "--umi1 / --umi2: the UMI sets are not merged across several ranks; run one process.")
+        sys.exit(2)
+    if param.get('umi_header') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--umih: the UMI sets are not merged across several ranks; run one process.")
         sys.exit(2)
     if param.get('paired'):                                      # one sample per pair, named after its R1 file
         if sharding.world().size > 1:
@@ -759,6 +798,8 @@ def run_headers(param):
     for mate, part in enumerate(param.get('umi_paired') or (), 1):
         if part:
             lines.append(f"#UMI in mate {mate}, start, length: {part[0]},{part[1]}")
+    if param.get('umi_header'):
+        lines.append(f"#UMI in read header, separator, length: {param['umi_header'][0]},{param['umi_header'][1]}")
     if param.get('umi_mismatch'):
         lines.append(f"#UMI mismatches collapsed: {param['umi_mismatch']}")
     if param.get('umi_rule') == 'directional':

@@ -400,6 +400,45 @@ int f2q_umi_pairs(f2q_ctx *ctx, uint64_t cap, uint64_t *n, uint32_t *feature, ui
  * road (k_count_umi_pair); F2Q_UMI_PAIR_STAGE=0 / 1 picks that kernel's layout for A/B runs. */
 int f2q_set_umi_paired(f2q_ctx *ctx, int32_t start1, int32_t length1, int32_t start2, int32_t length2);
 
+/* ---- UMIs in read headers -----------------------------------------------------------------------
+ * umi_tools extract and fastp --umi move the UMI out of the read and append it to the read id (@NAME_ACGTACGT);
+ * bcl-convert / bcl2fastq write an index-read UMI as the last colon field of the id (@M0:7:FC:1:1101:100:200:ACGTACGT
+ * 1:N:0:ATCACG), a dual UMI as ACGT+TTGA.  f2q_set_umi_header makes a Counter context keep the same (feature, UMI) set
+ * from those: f2q_set_umi_reads, f2q_read_umis, f2q_umi_collapse, f2q_umi_collapse_directional, f2q_umi_pairs,
+ * F2Q_UMI_SLOTS, the growth of the set and f2q_reset_counts work on it unchanged.
+ *
+ * The rule, for a record's line 0 (`header_line`, bytes), sep (one byte) and length L:
+ *
+ *     def header_umi(header_line, sep, L):           # -> bytes or None
+ *         h = header_line.rstrip()                   # rstrip()-ed as the other three lines are
+ *         for i, c in enumerate(h):
+ *             if c in b" \t": h = h[:i]; break       # the read id: up to the first space or tab
+ *         k = h.rfind(bytes([sep]))
+ *         if k < 0: return None                      # no separator in the id
+ *         tail = h[k + 1:]
+ *         if tail.count(b"+") > 1: return None       # at most one '+' (dual UMI) is skipped, wherever it stands
+ *         tail = tail.replace(b"+", b"")
+ *         if len(tail) != L or set(tail.upper()) - set(b"ACGT"): return None
+ *         return tail.upper()                        # lower case counts, as for f2q_set_umi; an N makes it invalid
+ *
+ * There is no Phred test (a header has no quality) and a leading '@' is not asked for.  In the set's 2-bit codes base j
+ * of the returned string sits in bits 2j .. 2j+1, as everywhere else.  Every read is decided exactly as without the call:
+ * an assigned read with a valid header UMI brings (feature, UMI), any other assigned read counts as one with an invalid
+ * UMI (f2q_read_umis' extra[1]).  On a paired context the UMI of a pair is read from MATE 1's header by the same rule;
+ * mate 2's header is neither looked at nor compared.
+ *
+ * On a single-end Counter context the call takes the place of f2q_set_umi, on a paired one (after f2q_set_mate2) that of
+ * f2q_set_umi_paired; it comes once, before counting.  F2Q_EINVAL unless sep is one printable ASCII byte (33 .. 126)
+ * that is not alphanumeric and not '+', and 1 <= length <= 16.  F2Q_ESTATE on an Extract+Count context, on a context that
+ * is a UMI context already, after a counting call; afterwards for the sharded calls with world > 1, for f2q_synth_create
+ * (its blocks have no headers) and for f2q_count_resident on a block made before the call.  Every entry point that takes
+ * FASTQ text or files carries the UMI: f2q_count_block, f2q_block_from_fastq + f2q_count_resident, f2q_count_text,
+ * f2q_count_file (plain, gzip, BGZF, F2Q_DEVICE_INFLATE=1) and the three paired calls.  The header is read at ingest
+ * (k_header_umi on the framed text, one entry per record, owned by the block; the F2Q_HOST_PACK=1 road fills the same
+ * array on the host) and the counting kernels take the UMI from there.  Not implemented: a header UMI combined with an
+ * inline part, UMIs in the comment after the first space, comparing the two mates' headers. */
+int f2q_set_umi_header(f2q_ctx *ctx, int32_t sep, int32_t length);
+
 #ifdef __cplusplus
 }
 #endif
