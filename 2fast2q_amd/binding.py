@@ -25,6 +25,7 @@ EXPORTS = (
     "f2q_set_umi", "f2q_read_umis", "f2q_umi_collapse",
     "f2q_set_umi_reads", "f2q_umi_collapse_directional", "f2q_umi_pairs",
     "f2q_set_umi_paired", "f2q_set_umi_header",
+    "f2q_set_sample_barcodes", "f2q_read_demux",
 )
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
@@ -181,6 +182,8 @@ def load(path=None):
     L.f2q_umi_collapse.argtypes = [vp, C.c_int32, i64p, i64p]
     L.f2q_set_umi_reads.argtypes = [vp, C.c_int32]
     L.f2q_umi_collapse_directional.argtypes = [vp, i64p, i64p]
+    L.f2q_set_sample_barcodes.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32]
+    L.f2q_read_demux.argtypes = [vp, i64p, i64p, i64p]
     u32p = C.POINTER(C.c_uint32)
     L.f2q_umi_pairs.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), u32p, u32p, u32p]
     if path == LIB_PATH:
@@ -264,9 +267,15 @@ class Counter:
     the total number of bases, and everything ``umi=`` offers works on it (``umi=`` itself stays single-read only).
     ``umi_header=(sep, L)`` takes the UMI from the read header instead (f2q_set_umi_header): the L bases behind the last
     ``sep`` (one character, or its byte value) of the read id, mate 1's on a paired context; ``umi_length`` answers L.
+
+    ``sample_barcodes=(S, [seq, ...])`` demultiplexes a pooled sample by an inline barcode (f2q_set_sample_barcodes): every
+    read carries one of the barcodes (all of one length, 1 .. 16 bases, at most 1024) at read positions [S, S + L);
+    ``barcode_mismatch`` 0 / 1 is the number of substitutions allowed.  Counter mode, single reads, no UMIs;
+    ``read_demux()`` returns the count matrix per sample, the five counters per sample and the five barcode verdicts.
     """
 
-    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, umi_header=None, **params):
+    def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, umi_header=None,
+                 sample_barcodes=None, barcode_mismatch=0, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -283,7 +292,13 @@ class Counter:
         self.umi_header = None
         self.umi_length = 0              # bases of a UMI (set_umi / set_umi_paired), 0: no UMI context
         self.umi_reads = False
+        self.sample_barcodes = None      # (start, [barcodes]) of a demultiplexing context
+        self.barcode_mismatch = 0
         try:
+            if sample_barcodes is not None:
+                self.set_sample_barcodes(sample_barcodes[0], sample_barcodes[1], barcode_mismatch)
+            elif barcode_mismatch:
+                raise ValueError("barcode_mismatch needs sample_barcodes")
             if start2 is not None:
                 self.set_mate2(start2, rc2)
             if umi is not None:
@@ -378,6 +393,16 @@ class Counter:
         """keep the reads of every (feature, UMI) pair (f2q_set_umi_reads); after set_umi, before counting"""
         self._check(self._L.f2q_set_umi_reads(self._h, 1 if on else 0))
         self.umi_reads = bool(on)
+
+    def set_sample_barcodes(self, start, seqs, mismatch=0):
+        """the inline sample barcodes of a pooled sample (f2q_set_sample_barcodes); before counting"""
+        enc = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
+        if len({len(b) for b in enc}) > 1:
+            raise ValueError("the sample barcodes must all have one length")
+        length = len(enc[0]) if enc else 0
+        self._check(self._L.f2q_set_sample_barcodes(self._h, b"".join(enc), len(enc), length, int(start), int(mismatch)))
+        self.sample_barcodes = (int(start), [b.decode("latin-1").upper() for b in enc])
+        self.barcode_mismatch = int(mismatch)
 
     # -- counting: paired-end --
     @staticmethod
@@ -553,6 +578,18 @@ class Counter:
         self._check(self._L.f2q_read_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_int64)),
                                             stats.ctypes.data_as(C.POINTER(C.c_int64))))
         return counts[:self.n_features], stats
+
+    def read_demux(self):
+        """(matrix[nb + 1, n_features], sample_stats[nb + 1, 5], verdicts[5]) as int64 arrays (f2q_read_demux): row b is
+        barcode b, row nb the unassigned reads; verdicts = exact, one mismatch, ambiguous, no match, unreadable"""
+        nb = len(self.sample_barcodes[1]) if self.sample_barcodes else 0
+        matrix = np.zeros((nb + 1, max(self.n_features, 1)), dtype=np.int64)
+        sstats = np.zeros((nb + 1, 5), dtype=np.int64)
+        verdicts = np.zeros(5, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.f2q_read_demux(self._h, matrix.ctypes.data_as(i64p) if self.n_features else None,
+                                           sstats.ctypes.data_as(i64p), verdicts.ctypes.data_as(i64p)))
+        return matrix[:, :self.n_features], sstats, verdicts
 
     def read_umis(self):
         """(umis[n_features], umi_reads, umi_failed): distinct UMIs per feature, assigned reads with a valid / an invalid UMI"""

@@ -1360,6 +1360,97 @@ struct UmiHeaderHook {
     }
 };
 
+// ---- inline sample barcodes (f2q_set_sample_barcodes): pooled samples demultiplexed while they are counted ----
+// The rule is stated in include/f2q.h (barcode_of).  Every read gets a barcode verdict of its own, whatever the feature
+// verdict is; the sample of a read is its barcode's index, or n ("unassigned") for every verdict but the first two.
+// The host builds one open-addressing table (demux_build, f2q_host.h) of 64-bit slots:
+//   bits 0 .. 31   the window's 2-bit codes, base j in bits 2j .. 2j+1 (a 16-base barcode uses all of them: T x 16 is
+//                  0xFFFFFFFF and A x 16 is 0, so neither an all-ones nor a zero code can mean "empty")
+//   bits 32 .. 41  the sample (barcode index)
+//   bit 48         the entry is a substitution neighbour of its barcode (distance 1), not the barcode itself
+//   bit 49         ... and at least two barcodes have this neighbour: ambiguous
+//   bit 63         the slot is used; an empty slot is the word 0
+// With --sbm 1 every barcode's 3L neighbours are entries too (a neighbour that is a barcode keeps its exact entry), so an
+// all-ACGT window is decided by ONE look-up whatever M is.  The table is at most half full and only read by the kernel.
+#define F2Q_DEMUX_MAXLEN 16
+#define F2Q_DEMUX_MAXN 1024u
+#define F2Q_DEMUX_EXACT 0            // the five barcode verdicts, in f2q_read_demux's order
+#define F2Q_DEMUX_ONE 1
+#define F2Q_DEMUX_AMBIGUOUS 2
+#define F2Q_DEMUX_NOMATCH 3
+#define F2Q_DEMUX_UNREADABLE 4
+#define F2Q_DEMUX_USED (1ull << 63)
+#define F2Q_DEMUX_DIST1 (1ull << 48)
+#define F2Q_DEMUX_AMBIG (1ull << 49)
+#define F2Q_DEMUX_LDS_SLOTS 4096u    // a table of at most this many slots (32 KiB) can be copied into LDS (k_count_demux<true>)
+struct DemuxDev {
+    const unsigned long long *table; // [mask + 1] slots
+    uint32_t mask;                   // slots - 1
+    int32_t start, length, miss;     // the window [start, start + length), --sbm
+    uint32_t n, n_features;          // barcodes; the row length of matrix
+    unsigned long long *matrix;      // [(n + 1) * n_features]: reads assigned to feature f in sample b, row n = unassigned
+    unsigned long long *sstats;      // [(n + 1) * 5]: the five reference counters per sample
+    unsigned long long *verdicts;    // [5]: reads per barcode verdict
+};
+F2Q_HD unsigned long long demux_slot(uint32_t code, uint32_t sample, unsigned long long flags)
+{
+    return F2Q_DEMUX_USED | flags | ((unsigned long long)sample << 32) | code;
+}
+F2Q_HD uint32_t demux_hash(uint32_t code, uint32_t mask) { return hash32(code, 32) & mask; }
+// the slot that holds `code`, else 0.  T: the table where it lives (global memory, or the workgroup's copy in LDS)
+template <class T>
+F2Q_HD unsigned long long demux_find(T tab, uint32_t mask, uint32_t code)
+{
+    uint32_t s = demux_hash(code, mask);
+    for (uint32_t guard = 0; guard <= mask; guard++) {
+        const unsigned long long v = tab[s];
+        if (v == 0ull) return 0ull;
+        if ((uint32_t)v == code) return v;
+        s = (s + 1u) & mask;
+    }
+    return 0ull;
+}
+// the barcode verdict of one read (F2Q_DEMUX_*); sample = the barcode's index for EXACT / ONE, else d.n.
+// A window with ONE byte that is no base and --sbm 1: that byte is the one mismatch, so the barcode must agree on every
+// other position -- the four codes with the position substituted are looked up and only exact entries count (distinct
+// barcodes can share all other positions: several hits are ambiguous).  Two such bytes are two mismatches: no match.
+template <class P, class T>
+F2Q_HD int demux_decide(const DemuxDev &d, T tab, int thr, P seq, int r, P qual, int qn, uint32_t &sample)
+{
+    sample = d.n;
+    const int a = d.start, b = d.start + d.length;
+    if (b > r || b > qn) return F2Q_DEMUX_UNREADABLE;
+    if (qual_range_fails(qual, a, b, thr)) return F2Q_DEMUX_UNREADABLE;
+    uint32_t code = 0, odd = 0, at = 0;
+    for (int j = a; j < b; j++) {
+        uint32_t c = base_code(up8(seq[j]));
+        if (c > 3u) { odd++; at = (uint32_t)(j - a); c = 0u; }
+        code |= c << (2 * (j - a));
+    }
+    if (odd == 0u) {
+        const unsigned long long v = demux_find(tab, d.mask, code);
+        if (v == 0ull) return F2Q_DEMUX_NOMATCH;
+        if (v & F2Q_DEMUX_AMBIG) return F2Q_DEMUX_AMBIGUOUS;
+        sample = (uint32_t)(v >> 32) & 0x3FFu;
+        return (v & F2Q_DEMUX_DIST1) ? F2Q_DEMUX_ONE : F2Q_DEMUX_EXACT;
+    }
+    if (odd > 1u || d.miss == 0) return F2Q_DEMUX_NOMATCH;
+    uint32_t hits = 0, who = 0;
+    for (uint32_t c = 0; c < 4u; c++) {
+        const unsigned long long v = demux_find(tab, d.mask, code | (c << (2u * at)));
+        if (v != 0ull && !(v & F2Q_DEMUX_DIST1)) { hits++; who = (uint32_t)(v >> 32) & 0x3FFu; }
+    }
+    if (hits == 0u) return F2Q_DEMUX_NOMATCH;
+    if (hits > 1u) return F2Q_DEMUX_AMBIGUOUS;
+    sample = who;
+    return F2Q_DEMUX_ONE;
+}
+// general_read's hook on a demultiplexing context: the read's feature count again, in its sample's row of the matrix
+struct DemuxHook {
+    unsigned long long *row;         // matrix + sample * n_features
+    F2Q_HD void assigned(uint32_t f) const { acc_add(&row[f], 1ull); }
+};
+
 // ---------------------------------------------------------------------------------------------
 // general path: one read given as raw bytes.  st[] = the 5 reference counters (thread-local).
 // ---------------------------------------------------------------------------------------------

@@ -737,4 +737,75 @@ inline int fill_run(const f2q_params &p, RunDev &r, std::string &err, int n_mate
     return F2Q_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// inline sample barcodes (f2q_set_sample_barcodes; the slot layout: f2q_device.h, DemuxDev)
+// ---------------------------------------------------------------------------------------------
+struct DemuxTable {
+    std::vector<unsigned long long> slots;         // a power of two, at least twice the entries
+    uint32_t mask = 0, entries = 0, ambiguous = 0; // slots - 1; used slots; of those, neighbours of several barcodes
+    std::string seqs;                              // the barcodes, upper case, n * length bytes
+};
+// the arguments of f2q_set_sample_barcodes; upper-cases into `up`.  F2Q_EINVAL with a message that names the barcode
+inline int demux_validate(const char *seqs, uint32_t n, int32_t length, int32_t start, int32_t miss, std::string &up, std::string &err)
+{
+    if (n < 1u || n > F2Q_DEMUX_MAXN) { err = "sample barcodes: between 1 and 1024 of them, not " + std::to_string(n); return F2Q_EINVAL; }
+    if (length < 1 || length > F2Q_DEMUX_MAXLEN) { err = "sample barcodes have a common length of 1 .. 16 bases, not " + std::to_string(length); return F2Q_EINVAL; }
+    if (start < 0 || start > 0x3FFFFFFF) { err = "the sample barcode starts at a read position >= 0, not " + std::to_string(start); return F2Q_EINVAL; }
+    if (miss != 0 && miss != 1) { err = "sample barcodes are matched with 0 or 1 mismatches, not " + std::to_string(miss); return F2Q_EINVAL; }
+    if (!seqs) { err = "null argument"; return F2Q_EINVAL; }
+    up.assign(seqs, (size_t)n * (size_t)length);
+    std::vector<std::pair<uint32_t, uint32_t>> codes; codes.reserve(n);
+    for (uint32_t b = 0; b < n; b++) {
+        uint32_t code = 0;
+        for (int j = 0; j < length; j++) {
+            uint8_t &c = reinterpret_cast<uint8_t &>(up[(size_t)b * length + j]);
+            c = up8(c);
+            const uint32_t k = base_code(c);
+            if (k > 3u) {
+                std::string shown; for (int q = 0; q < length; q++) { const char ch = seqs[(size_t)b * length + q]; shown += (ch >= 33 && ch <= 126) ? ch : '?'; }
+                err = "sample barcode " + std::to_string(b) + " (" + shown + ") holds a byte that is not A/C/G/T"; return F2Q_EINVAL;
+            }
+            code |= k << (2 * j);
+        }
+        codes.emplace_back(code, b);
+    }
+    std::sort(codes.begin(), codes.end());
+    for (uint32_t i = 1; i < n; i++) if (codes[i].first == codes[i - 1].first) {
+        err = "sample barcode " + std::to_string(codes[i].second) + " (" + up.substr((size_t)codes[i].second * length, length) + ") repeats barcode " +
+              std::to_string(codes[i - 1].second); return F2Q_EINVAL;
+    }
+    return F2Q_OK;
+}
+// one entry of the table: a code that is there already as a neighbour of another barcode becomes ambiguous, an exact entry
+// is never touched by a neighbour and replaces one
+inline void demux_put(DemuxTable &t, uint32_t code, uint32_t sample, bool exact)
+{
+    uint32_t s = demux_hash(code, t.mask);
+    for (;;) {
+        unsigned long long &v = t.slots[s];
+        if (v == 0ull) { v = demux_slot(code, sample, exact ? 0ull : F2Q_DEMUX_DIST1); t.entries++; return; }
+        if ((uint32_t)v == code) {
+            if (exact) { if (v & F2Q_DEMUX_AMBIG) t.ambiguous--; v = demux_slot(code, sample, 0ull); }
+            else if ((v & F2Q_DEMUX_DIST1) && !(v & F2Q_DEMUX_AMBIG) && ((uint32_t)(v >> 32) & 0x3FFu) != sample) { v |= F2Q_DEMUX_AMBIG; t.ambiguous++; }
+            return;
+        }
+        s = (s + 1u) & t.mask;
+    }
+}
+// the table of n validated barcodes (demux_validate's `up`): the barcodes first, then, for miss == 1, their 3L neighbours
+inline void demux_build(const std::string &up, uint32_t n, int32_t length, int32_t miss, DemuxTable &t)
+{
+    const uint64_t most = (uint64_t)n * (miss ? 1u + 3u * (uint32_t)length : 1u);
+    uint64_t slots = 2; while (slots < 2 * most) slots <<= 1;
+    t.slots.assign((size_t)slots, 0ull); t.mask = (uint32_t)(slots - 1); t.entries = 0; t.ambiguous = 0; t.seqs = up;
+    std::vector<uint32_t> codes(n, 0u);
+    for (uint32_t b = 0; b < n; b++) {
+        for (int j = 0; j < length; j++) codes[b] |= base_code((uint8_t)up[(size_t)b * length + j]) << (2 * j);
+        demux_put(t, codes[b], b, true);
+    }
+    if (miss) for (uint32_t b = 0; b < n; b++)
+        for (int j = 0; j < length; j++)
+            for (uint32_t x = 1; x < 4u; x++) demux_put(t, codes[b] ^ (x << (2 * j)), b, false);
+}
+
 } // namespace f2q

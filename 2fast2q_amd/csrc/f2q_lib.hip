@@ -34,6 +34,7 @@ using namespace f2q;
 #include "f2q_inflate_kernels.h"
 #include "f2q_assign_kernels.h"
 #include "f2q_umi_kernels.h"
+#include "f2q_demux_kernels.h"
 
 // ===============================================================================================
 // host side
@@ -123,6 +124,17 @@ struct f2q_ctx {
         bool pair_stage = false;         // f2q_set_umi_paired: k_count_umi_pair<.., true> (F2Q_UMI_PAIR_STAGE)
         int32_t hdr_sep = 0;             // f2q_set_umi_header: the separator byte (0: the UMI is not in the header); the length is dev.length
     } umi;
+    // inline sample barcodes (f2q_set_sample_barcodes): the barcode table, the count matrix [(n + 1)][n_features], the five
+    // reference counters per sample and the five verdict counters; they live across pieces and counting calls
+    struct {
+        bool on = false;
+        DemuxDev dev{};
+        DemuxTable tab;                  // the host's copy of the table (uploaded once, with the first allocation)
+        std::vector<void *> allocs;      // table, matrix, sstats + verdicts
+        uint64_t matrix_n = 0;           // words of dev.matrix
+        bool lds_table = false;          // k_count_demux<true> (F2Q_DEMUX_TABLE=lds, and the table fits)
+        bool shmem_set = false;          // the instance has been told its dynamic LDS size
+    } demux;
     bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
     int n_cu = 256;
@@ -433,6 +445,41 @@ static int umi_read_ctr(f2q_ctx *c, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
     return F2Q_OK;
 }
 
+// the barcode table, the matrix and the counters given back: f2q_destroy, and a new library
+static void demux_drop(f2q_ctx *c)
+{
+    free_all(c, c->demux.allocs);
+    c->demux.dev.table = nullptr; c->demux.dev.matrix = nullptr; c->demux.dev.sstats = nullptr; c->demux.dev.verdicts = nullptr; c->demux.matrix_n = 0;
+}
+
+// Table, matrix and counters once barcodes and features are both known, through the context's device-memory cache.  A
+// failure gives back what this call got and leaves the context as it was: the call that led here may simply be repeated.
+static int demux_alloc(f2q_ctx *c)
+{
+    if (!c->demux.on || c->demux.dev.matrix) return F2Q_OK;
+    DemuxDev d = c->demux.dev; std::vector<void *> owner;
+    const uint64_t nf = std::max<uint64_t>(c->lib_h.n_features, 1), rows = (uint64_t)d.n + 1;
+    unsigned long long *tab = nullptr, *ctr = nullptr;
+    int rc;
+    if ((rc = dev_upload(c, (const unsigned long long *)c->demux.tab.slots.data(), c->demux.tab.slots.size(), &tab, owner)) ||
+        (rc = dev_alloc(c, (size_t)(rows * nf), &d.matrix, owner, 0)) ||
+        (rc = dev_alloc(c, (size_t)(rows * 5 + 5), &ctr, owner, 0))) {
+        free_all(c, owner);
+        return fail(c, F2Q_ENOMEM, "no device memory for the demultiplexed counts (" + std::to_string(rows) + " x " + std::to_string(nf) + " counters): " + c->err);
+    }
+    d.table = tab; d.sstats = ctr; d.verdicts = ctr + rows * 5; d.n_features = (uint32_t)c->lib_h.n_features;
+    c->demux.dev = d; c->demux.allocs = owner; c->demux.matrix_n = rows * nf;
+    return F2Q_OK;
+}
+
+// matrix and counters cleared (f2q_reset_counts); the table stays
+static int demux_clear(f2q_ctx *c)
+{
+    HIPC(c, hipMemsetAsync(c->demux.dev.matrix, 0, c->demux.matrix_n * sizeof(unsigned long long), c->stream));
+    HIPC(c, hipMemsetAsync(c->demux.dev.sstats, 0, ((size_t)c->demux.dev.n + 2) * 5 * sizeof(unsigned long long), c->stream));
+    return F2Q_OK;
+}
+
 extern "C" void f2q_destroy(f2q_ctx *c)
 {
     if (!c) return;
@@ -445,6 +492,7 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     free_all(c, c->asg_lib_allocs); free_all(c, c->asg_allocs);
     if (c->trace && c->umi.on) fprintf(stderr, "[f2q trace] UMI set: %llu slots, %llu rehashes\n", (unsigned long long)c->umi.n_slots, (unsigned long long)c->umi.rehashes);
     umi_drop(c);
+    demux_drop(c);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
@@ -499,6 +547,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     rc = alloc_acc(c, n);
     if (rc) return rc;
     if (c->umi.on) umi_drop(c);                       // a new library starts a new set
+    if (c->demux.on) { demux_drop(c); if ((rc = demux_alloc(c))) return rc; }      // ... and a new matrix: a row has a word per feature
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
     // symbol of any feature), every other odd symbol still sends the read to the byte-exact routine
@@ -520,6 +569,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
         memset(&c->ec, 0, sizeof c->ec); c->ec_slots = 0; c->hot_valid = false; c->ec_learned = 0;
     }
     if (c->umi.on && c->umi.dev.umis) if (int rc = umi_clear(c)) return rc;
+    if (c->demux.on && c->demux.dev.matrix) if (int rc = demux_clear(c)) return rc;
     c->reads_seen = 0;
     c->ec_gen++;
     // no host synchronisation: the clear is ordered on the context's stream like every launch and read-back after it
@@ -553,6 +603,7 @@ extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 }
 
 // ---- distinct UMIs per feature: the ABI ---------------------------------------------------------------------------
+static const char *const DEMUX_NO_UMI = "a demultiplexing context (f2q_set_sample_barcodes) takes no UMIs: the two are not combined";
 // what f2q_set_umi and f2q_set_umi_paired share once the window is in umi.dev
 static void umi_enable(f2q_ctx *c)
 {
@@ -568,6 +619,7 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
     if (!c) return F2Q_EINVAL;
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi takes a Counter context: Extract+Count assigns no read to a feature");
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) takes f2q_set_umi_paired");
+    if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
     if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
         return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
@@ -583,6 +635,7 @@ extern "C" int f2q_set_umi_header(f2q_ctx *c, int32_t sep, int32_t length)
 {
     if (!c) return F2Q_EINVAL;
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_header takes a Counter context: Extract+Count assigns no read to a feature");
+    if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_header comes once, in place of f2q_set_umi / f2q_set_umi_paired and before counting");
     const bool alnum = (sep >= '0' && sep <= '9') || (sep >= 'A' && sep <= 'Z') || (sep >= 'a' && sep <= 'z');
     if (sep < 33 || sep > 126 || alnum || sep == '+' || length < 1 || length > F2Q_UMI_MAXLEN)
@@ -601,6 +654,7 @@ extern "C" int f2q_set_umi_paired(f2q_ctx *c, int32_t start1, int32_t length1, i
 {
     if (!c) return F2Q_EINVAL;
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a Counter context: Extract+Count assigns no pair to a feature");
+    if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (!c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a paired context: call f2q_set_mate2 first (single reads: f2q_set_umi)");
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired comes once, after f2q_set_mate2 and before counting");
     if (start1 < 0 || start1 > 0x3FFFFFFF || start2 < 0 || start2 > 0x3FFFFFFF || length1 < 0 || length2 < 0 ||
@@ -637,6 +691,58 @@ extern "C" int f2q_read_umis(f2q_ctx *c, int64_t *umis, int64_t extra[2])
     if (int rc = umi_read_ctr(c, ctr)) return rc;
     if (umis) for (uint64_t i = 0; i < nf; i++) umis[i] = (int64_t)h[i];
     if (extra) { extra[0] = (int64_t)ctr[F2Q_UMI_READS]; extra[1] = (int64_t)ctr[F2Q_UMI_FAILED]; }
+    return F2Q_OK;
+}
+
+// ---- inline sample barcodes: the ABI (include/f2q.h) -----------------------------------------------------------------
+extern "C" int f2q_set_sample_barcodes(f2q_ctx *c, const char *seqs, uint32_t n, int32_t length, int32_t start, int32_t miss)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes takes a Counter context: Extract+Count with sample barcodes is not implemented");
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes takes single reads: a paired context (f2q_set_mate2) is not demultiplexed");
+    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a UMI context: sample barcodes and UMIs are not combined");
+    if (c->demux.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes comes once, after f2q_create and before counting");
+    std::string up, err;
+    if (int rc = demux_validate(seqs, n, length, start, miss, up, err)) return fail(c, rc, err);
+    HIPC(c, hipSetDevice(c->device));
+    demux_build(up, n, length, miss, c->demux.tab);
+    DemuxDev &d = c->demux.dev;
+    d = DemuxDev{};
+    d.mask = c->demux.tab.mask; d.start = start; d.length = length; d.miss = miss; d.n = n;
+    // F2Q_DEMUX_TABLE=lds / global: the table copied into LDS by every workgroup (when it fits) / read from global memory
+    const char *e = getenv("F2Q_DEMUX_TABLE");
+    const bool want_lds = e && !strcmp(e, "lds") ? true : e && !strcmp(e, "global") ? false : F2Q_DEMUX_TABLE_LDS_DEFAULT;
+    c->demux.lds_table = want_lds && c->demux.tab.slots.size() <= F2Q_DEMUX_LDS_SLOTS;
+    c->demux.on = true;
+    if (c->have_lib) if (int rc = demux_alloc(c)) { c->demux.on = false; return rc; }      // (nothing else was touched: as if the call had not been made)
+    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
+    c->force_general = true;
+    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
+    c->plan.inband_n = false; c->plan.n_only = false;
+    if (c->trace) fprintf(stderr, "[f2q trace] sample barcodes: %u of %d bases at %d, %d mismatches; table %zu slots, %u entries, %u ambiguous, %s\n",
+                          n, length, start, miss, c->demux.tab.slots.size(), c->demux.tab.entries, c->demux.tab.ambiguous, c->demux.lds_table ? "LDS" : "global");
+    return F2Q_OK;
+}
+
+extern "C" int f2q_read_demux(f2q_ctx *c, int64_t *matrix, int64_t *sample_stats, int64_t verdicts[5])
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->demux.on) return fail(c, F2Q_ESTATE, "not a demultiplexing context: call f2q_set_sample_barcodes first");
+    HIPC(c, hipSetDevice(c->device));
+    const DemuxDev &d = c->demux.dev;
+    const uint64_t nf = c->have_lib ? c->lib_h.n_features : 0, rows = (uint64_t)d.n + 1;
+    std::vector<unsigned long long> hm, hs(rows * 5 + 5, 0ull);
+    if (d.matrix) {                                              // (no library yet: nothing can have been counted)
+        if (matrix && nf) {
+            try { hm.resize(rows * nf); } catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy the demultiplexed counts"); }
+            HIPC(c, hipMemcpyAsync(hm.data(), d.matrix, rows * nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPC(c, hipMemcpyAsync(hs.data(), d.sstats, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (matrix) for (uint64_t i = 0; i < rows * nf; i++) matrix[i] = hm.empty() ? 0 : (int64_t)hm[i];
+    if (sample_stats) for (uint64_t i = 0; i < rows * 5; i++) sample_stats[i] = (int64_t)hs[i];
+    if (verdicts) for (int k = 0; k < 5; k++) verdicts[k] = (int64_t)hs[rows * 5 + k];
     return F2Q_OK;
 }
 
@@ -1324,6 +1430,23 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
         EC_POINT(c, c->umi.hdr_sep ? (rb.len1 ? "k_count_umi_pair (header)" : "k_count_umi (header)") : rb.len1 ? "k_count_umi_pair" : "k_count_umi");
         return F2Q_OK;
     }
+    if (c->demux.on) {                                           // the same road with the barcode verdict and the matrix (f2q_set_sample_barcodes)
+        if ((rc = demux_alloc(c))) return rc;                    // (only after an allocation that failed: a retry)
+        const DemuxDev &d = c->demux.dev;
+        const size_t shmem = (c->demux.lds_table ? ((size_t)d.mask + 1) * 8 : 0) + ((size_t)d.n + 1) * 5 * 4;
+        if (!c->demux.shmem_set) {                               // once per context, the most any context can ask for: the attribute belongs to the kernel, not to the context
+            const void *kern = c->demux.lds_table ? (const void *)k_count_demux<true> : (const void *)k_count_demux<false>;
+            const size_t most = (c->demux.lds_table ? (size_t)F2Q_DEMUX_LDS_SLOTS * 8 : 0) + ((size_t)F2Q_DEMUX_MAXN + 1) * 5 * 4;
+            HIPC(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+            c->demux.shmem_set = true;
+        }
+        if (c->demux.lds_table) hipLaunchKernelGGL(k_count_demux<true>, dim3(grid), dim3(F2Q_GEN_THREADS), shmem, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, d);
+        else hipLaunchKernelGGL(k_count_demux<false>, dim3(grid), dim3(F2Q_GEN_THREADS), shmem, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, d);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, "k_count_demux");
+        return F2Q_OK;
+    }
     if (rb.len1) hipLaunchKernelGGL(k_count_general<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     else hipLaunchKernelGGL(k_count_general<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     HIPC(c, hipGetLastError());
@@ -1461,6 +1584,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
     if (!k0) { k0 = c->ev_k0; k1 = c->ev_k1; }          // (a queued step brings its own pair)
     if (c->prm.mode == 0 && !c->have_lib) return fail(c, F2Q_ESTATE, "f2q_set_features must be called before counting in Counter mode");
     if (c->umi.on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
+    if (c->demux.on && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_sample_barcodes: a demultiplexing context counts single raw records only");
     if (c->umi.hdr_sep && b->rb.n && !b->rb.hdr_umi) return fail(c, F2Q_ESTATE, "the block was made before f2q_set_umi_header (or without headers): its records carry no header UMI");
     c->counted = true;
     Accum acc{c->acc_d, c->acc_d + (c->acc_n - 5), nullptr, nullptr, nullptr, nullptr};
@@ -1984,6 +2108,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
     if (!c) return F2Q_EINVAL;
     if (c->have_lib || c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_mate2 comes once, after f2q_create and before f2q_set_features");
     if (c->umi.on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only: f2q_set_mate2 comes first, then f2q_set_umi_paired");
+    if (c->demux.on) return fail(c, F2Q_ESTATE, "a demultiplexing context (f2q_set_sample_barcodes) counts single reads only");
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
     for (int i = 0; i < n_start2; i++) if (start2[i] < 0) return fail(c, F2Q_EINVAL, "a mate-2 window starts before the mate");
@@ -2660,6 +2785,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
     if (!c || !path || world == 0 || rank >= world) return F2Q_EINVAL;
     if (int rc = single_only(c)) return rc;
     if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
+    if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     size_t CH = file_chunk_bytes((size_t)256 << 20);
     TextSource src;
@@ -2944,6 +3070,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
     if (!c || !path || !census || world == 0 || rank >= world || !piece_bytes_ok(piece_bytes)) return F2Q_EINVAL;
     if (int rc = single_only(c)) return rc;
     if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
+    if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }

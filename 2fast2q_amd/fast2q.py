@@ -101,6 +101,44 @@ def features_loader(guides):
     return features
 
 
+def sample_barcodes_loader(path):
+    """(names, barcodes) of a --sb file: rows `name,barcode`, read as features_loader reads --g -- ',' ';' tab tried in turn,
+    the first two columns taken, barcodes upper-cased with blanks removed -- but stricter where --g is lenient: the first
+    separator that splits EVERY non-blank line is the file's (features_loader keeps the rows before the first short line and
+    adds up what the three separators give), blank lines are skipped, and nothing repeated is dropped: it is refused.
+    A string that says what is wrong with the file otherwise."""
+    if not os.path.isfile(path):
+        return f"no .csv file found in the following path: {path}"
+    rows = []
+    for sep in (",", ";", "\t"):
+        try:
+            with open(path) as handle:
+                rows = [(cols[0], cols[1].upper().replace(" ", "")) for cols in (line.rstrip().split(sep) for line in handle if line.strip())]
+        except IndexError:
+            rows = []
+        if rows:
+            break
+    if not rows:
+        return "the file doesn't seem to be comma, semicolon, or tab separated rows of name,barcode"
+    names, barcodes = [r[0] for r in rows], [r[1] for r in rows]
+    if len(rows) > 1024:
+        return f"{len(rows)} barcodes: at most 1024 are taken"
+    for name, barcode in rows:
+        if name == "unassigned":
+            return "the name unassigned is taken by the reads that carry no barcode"
+        if names.count(name) > 1:
+            return f"the name {name} appears at least twice"
+        if not 1 <= len(barcode) <= 16:
+            return f"the barcode of {name} ({barcode}) has {len(barcode)} bases: between 1 and 16 are taken"
+        if set(barcode) - set("ACGT"):
+            return f"the barcode of {name} ({barcode}) holds a symbol that is not A/C/G/T"
+        if len(barcode) != len(barcodes[0]):
+            return f"the barcode of {name} ({barcode}) has {len(barcode)} bases, that of {names[0]} has {len(barcodes[0])}: all barcodes have one length"
+        if barcodes.count(barcode) > 1:
+            return f"the barcode {barcode} appears at least twice ({', '.join(n for n, b in rows if b == barcode)})"
+    return names, barcodes
+
+
 def _counter_kwargs(param):
     if param.get('paired'):                         # a paired context: the windows of mate 2 and its direction (f2q_set_mate2)
         plain = {k: v for k, v in param.items() if k != 'paired'}
@@ -123,6 +161,10 @@ def _counter_kwargs(param):
         kwargs['umi_header'] = tuple(param['umi_header'])
         if param.get('umi_rule') == 'directional':
             kwargs['umi_reads'] = True
+    if param.get('sample_barcodes'):                # --sb: a demultiplexing context (f2q_set_sample_barcodes); part of the key too
+        sb = param['sample_barcodes']
+        kwargs['sample_barcodes'] = (sb['start'], tuple(sb['barcodes']))
+        kwargs['barcode_mismatch'] = sb['miss']
     return kwargs
 
 
@@ -242,6 +284,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         raise RuntimeError("--umi1 / --umi2: the UMI sets are not merged across several ranks; run one process")
     if param.get('umi_header') and sharding.world().size > 1:
         raise RuntimeError("--umih: the UMI sets are not merged across several ranks; run one process")
+    if param.get('sample_barcodes') and sharding.world().size > 1:
+        raise RuntimeError("--sb: the demultiplexed counts are not merged across several ranks; run one process")
     ctx = _context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
@@ -281,6 +325,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
                 rec["directional"] = ([int(n) for n in molecules], dict(umi_pairs=pairs, umi_edges=edges, umi_dominated=dominated,
                                                                         umi_molecules=int(sum(molecules)), umi_pair_reads=reads))
                 rec["pair_table"] = ctx.umi_pairs() if not param.get("delete", True) else None
+        if param.get('sample_barcodes'):            # --sb: the count matrix, the counters per sample barcode, the verdicts (f2q_read_demux)
+            param.setdefault('demux_counted', {})[raw] = ctx.read_demux()
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -374,6 +420,13 @@ def aligner(i, raw, features, param, reads_stats):
                 length = umi_length(param)          # (--umi1 + --umi2: the concatenation as sequenced)
                 csv_writer(os.path.join(param["directory"], sample.name + "_umi_pairs.csv"),
                            [["#Feature", "UMI", "Reads"]] + [[names[f], umi_text(int(c), length), int(n)] for f, c, n in zip(*pair_table)])
+    if raw in param.get('demux_counted', {}):        # --sb: the same rows once per sample barcode, then the unassigned reads
+        matrix, sstats, verdicts = param['demux_counted'].pop(raw)
+        names = [f.name for f in features.values()]
+        columns = [SampleResult(f"{sample.name}:{bname}", value, unit, _sample_rows(zip(names, (int(n) for n in matrix[b]))),
+                                dict(zip(binding.STAT_NAMES, (int(n) for n in sstats[b]))))
+                   for b, bname in enumerate(param['sample_barcodes']['names'] + ["unassigned"])]
+        param.setdefault("demux_samples", {})[sample.name] = (columns, [int(n) for n in verdicts])
     if not param['Progress bar']:
         colourful_errors("INFO", f"Sample {sample.name} was processed in {value} {unit}")
     param.setdefault("samples", {})[sample.name] = sample     # a later file of the same name replaces the earlier one,
@@ -443,6 +496,10 @@ def initializer(cmd):
             print(f" Distinct UMIs are counted per feature: UMI part in mate {mate}, start position: {part[0]}, length: {part[1]}bp")
     if param.get('umi_header'):
         print(f" Distinct UMIs are counted per feature: UMI in the read header, behind the last '{param['umi_header'][0]}' of the read id, length: {param['umi_header'][1]}bp")
+    if param.get('sample_barcodes'):
+        sb = param['sample_barcodes']
+        print(f" Reads are demultiplexed by {len(sb['barcodes'])} inline sample barcodes of {sb['path']}")
+        print(f" {sample_barcodes_header(param)[1:]}")
     if param.get('umi_mismatch'):
         print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
     if param.get('umi_rule') == 'directional':
@@ -494,6 +551,12 @@ def umi_length(param):
     if param.get('umi_header'):
         return param['umi_header'][1]
     return sum(part[1] for part in param.get('umi_paired') or () if part)
+
+
+def sample_barcodes_header(param):
+    """the line a --sb run adds to the parameter print-out and to the head of <name>_stats.csv"""
+    sb = param['sample_barcodes']
+    return f"#Sample barcodes, start, length, mismatches: {sb['start']},{len(sb['barcodes'][0])},{sb['miss']}"
 
 
 def parse_umih(text):
@@ -551,6 +614,9 @@ def input_parser(argv=None):
     ap.add_argument("--umih", help="SEP,L: the UMI of every read is in its header, the L bases (1-16) behind the last SEP of the read id, e.g. _,8 after umi_tools extract / fastp --umi, :,8 for an Illumina index-read UMI; with --pe: mate 1's header. Takes the place of --umi / --umi1 / --umi2")
     ap.add_argument("--mu", help="With --umi (or --umih, --umi1 / --umi2): mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")
     ap.add_argument("--mur", help="With --umi and --mu 1: the rule UMIs are collapsed by, cluster (default) or directional. directional: a UMI absorbs a neighbouring UMI only when it has at least twice its reads minus one (<name>_umi_directional.csv)")
+    ap.add_argument("--sb", help="The full path to a .csv file with rows name,barcode: the reads of every file are demultiplexed by an inline sample barcode (1-16 bases, at most 1024 barcodes of one length) while they are counted (<name>_demux.csv). Counter mode, single reads, one process")
+    ap.add_argument("--sbs", help="With --sb: the start position of the sample barcode within the read (default = 0)")
+    ap.add_argument("--sbm", help="With --sb: mismatches allowed in the sample barcode, 0 or 1 (default = 0)")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
     if args.v is not None:
@@ -664,6 +730,28 @@ def input_parser(argv=None):
             sys.exit(2)
         if args.mur == "directional":
             p['umi_rule'] = 'directional'
+    if args.sb is None and (args.sbs is not None or args.sbm is not None):
+        colourful_errors("FATAL", f"{'--sbs' if args.sbs is not None else '--sbm'} only has a meaning with --sb: the .csv file with the sample barcodes.")
+        sys.exit(2)
+    if args.sb is not None:
+        if p['Running Mode'] != "C":
+            colourful_errors("FATAL", "--sb only has a meaning in Counter mode: it cannot be combined with --mo EC.")
+            sys.exit(2)
+        others = [f for f, v in (("--pe", args.pe), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2), ("--umih", args.umih)) if v is not None]
+        if others:
+            colourful_errors("FATAL", f"--sb cannot be combined with {' / '.join(others)}: sample barcodes are taken from single reads without UMIs.")
+            sys.exit(2)
+        if args.sbs is not None and not (args.sbs.isascii() and args.sbs.isdigit() and int(args.sbs) <= 0x3FFFFFFF):
+            colourful_errors("FATAL", f"--sbs {args.sbs}: expected the start position of the sample barcode within the read, a number >= 0.")
+            sys.exit(2)
+        if args.sbm is not None and args.sbm not in ("0", "1"):
+            colourful_errors("FATAL", f"--sbm {args.sbm}: expected 0 or 1 (sample barcodes are matched at Hamming distance 1 at most).")
+            sys.exit(2)
+        loaded = sample_barcodes_loader(args.sb)
+        if isinstance(loaded, str):
+            colourful_errors("FATAL", f"--sb {args.sb}: {loaded}.")
+            sys.exit(2)
+        p['sample_barcodes'] = dict(path=args.sb, names=loaded[0], barcodes=loaded[1], start=int(args.sbs or 0), miss=int(args.sbm or 0))
     if args.assign is not None:
         if p['Running Mode'] != "EC":
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
@@ -696,6 +784,9 @@ def file_sizer_split(param):
         sys.exit(2)
     if param.get('umi_header') and sharding.world().size > 1:
         colourful_errors("FATAL", "--umih: the UMI sets are not merged across several ranks; run one process.")
+        sys.exit(2)
+    if param.get('sample_barcodes') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--sb: the demultiplexed counts are not merged across several ranks; run one process.")
         sys.exit(2)
     if param.get('paired'):                                      # one sample per pair, named after its R1 file
         if sharding.world().size > 1:
@@ -804,6 +895,8 @@ def run_headers(param):
         lines.append(f"#UMI mismatches collapsed: {param['umi_mismatch']}")
     if param.get('umi_rule') == 'directional':
         lines.append("#UMI collapse rule: directional")
+    if param.get('sample_barcodes'):
+        lines.append(sample_barcodes_header(param))
     return lines
 
 
@@ -813,6 +906,11 @@ def compile_table(samples):
     there (Extract+Count samples have different key sets).  A feature name holding '#' is left out of the table, as
     upstream's line filter does (:1350)."""
     ordered = sorted(samples.values(), key=lambda s: s.name + "_reads.csv")
+    return (ordered,) + _table_of(ordered)
+
+
+def _table_of(ordered):
+    """compile_table's head and rows for columns that are in their order already"""
     table = {}
     for column, sample in enumerate(ordered):
         for name, reads in sample.rows:
@@ -822,7 +920,7 @@ def compile_table(samples):
             table.setdefault(name, [0] * column).append(int(reads))
         for counts in table.values():
             counts.extend([0] * (column + 1 - len(counts)))
-    return ordered, ["#Feature"] + [s.name for s in ordered], table
+    return ["#Feature"] + [s.name for s in ordered], table
 
 
 def compiling(param):
@@ -843,6 +941,10 @@ def compiling(param):
             _, uhead, utable = compile_table(per_sample)
             csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}{suffix}.csv"),
                        [uhead] + [[feature] + counts for feature, counts in utable.items()])
+    if param.get("demux_samples"):                   # --sb: per file, in <name>.csv's column order, a column per barcode, then the unassigned reads
+        dhead, dtable = _table_of([column for s in ordered for column in param["demux_samples"].get(s.name, ((), ()))[0]])
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_demux.csv"),
+                   [dhead] + [[feature] + counts for feature, counts in dtable.items()])
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -873,6 +975,12 @@ UMI_TABLES = (("umis", "_umi", "UMIs", UMI_STATS_HEAD, ("umi_reads", "umi_failed
                ("umi_pairs", "umi_edges", "umi_dominated", "umi_molecules", "umi_pair_reads")))
 
 
+DEMUX_VERDICT_STATS_HEAD = ["#Sample name (sample barcodes)", "Number of reads with a barcode read without mismatches", "Number of reads with a barcode read with one mismatch",
+                            "Number of reads one mismatch away from several barcodes", "Number of reads that match no barcode",
+                            "Number of reads whose barcode is cut off or did not pass quality filtering"]
+DEMUX_SAMPLE_STATS_HEAD = ["#Sample name:sample barcode"] + STATS_HEAD[3:]
+
+
 def run_stats(headers, param, compiled, head, ordered):
     """<name>_stats.csv -- the run's '#key: value' lines, the column names, one row of numbers per sample (:1386-1412,
     taken from the counters themselves) -- plus the four overview plots (:1414-1527)"""
@@ -884,6 +992,13 @@ def run_stats(headers, param, compiled, head, ordered):
     for kind, _, _, stats_head, columns in UMI_TABLES:       # per kind: its head, then one line of counters per sample
         if any(kind in rec for rec in umi.values()):
             global_stat += [stats_head] + [[s.name] + [umi[s.name][kind].stats[c] for c in columns] for s in ordered if kind in umi.get(s.name, {})]
+    demux = param.get("demux_samples", {})
+    if demux:                                                    # --sb: the verdicts per file, then the counters per (file, barcode)
+        global_stat += [DEMUX_VERDICT_STATS_HEAD] + [[s.name] + demux[s.name][1] for s in ordered if s.name in demux]
+        global_stat += [DEMUX_SAMPLE_STATS_HEAD] + [
+            [c.name, c.stats["reads"], c.stats["perfect_counter"] + c.stats["imperfect_counter"], c.stats["perfect_counter"],
+             c.stats["imperfect_counter"], c.stats["non_aligned_counter"], c.stats["quality_failed"]]
+            for s in ordered if s.name in demux for c in demux[s.name][0]]
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib

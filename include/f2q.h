@@ -439,6 +439,60 @@ int f2q_set_umi_paired(f2q_ctx *ctx, int32_t start1, int32_t length1, int32_t st
  * inline part, UMIs in the comment after the first space, comparing the two mates' headers. */
 int f2q_set_umi_header(f2q_ctx *ctx, int32_t sep, int32_t length);
 
+/* ---- pooled samples: inline sample barcodes -----------------------------------------------------
+ * Pooled amplicon and CRISPR libraries are often multiplexed with a 6 .. 12 base tag at a fixed position of the same read
+ * that carries the feature.  It is no i5/i7 index, so the sequencer's software does not split on it.
+ * f2q_set_sample_barcodes makes a single-end Counter context decide, for EVERY read, which of n barcodes the read carries,
+ * and keep a count matrix [sample][feature] next to everything it kept before.
+ *
+ * The rule, for the rstrip()-ed sequence and quality lines of a record, the barcode start S >= 0, the common length L
+ * (1 .. 16) of the nb (1 .. 1024) barcodes -- A/C/G/T only, upper-cased on the way in, pairwise distinct -- and M in {0, 1}:
+ *
+ *     def barcode_of(seq, qual, S, L, phred, barcodes, M):       # -> (sample, verdict)
+ *         nb = len(barcodes)
+ *         if S + L > len(seq) or S + L > len(qual): return nb, UNREADABLE
+ *         ph = max(phred, 1)
+ *         if any(33 <= c <= min(ph + 31, 126) for c in qual[S:S + L]): return nb, UNREADABLE   # --ph, as a feature window
+ *         w = seq[S:S + L].upper()
+ *         d = [sum(x != y for x, y in zip(w, b)) for b in barcodes]   # bytes compared: an 'N' differs from every base
+ *         if 0 in d: return d.index(0), EXACT                         # unique: the barcodes are distinct
+ *         if M == 1 and d.count(1) == 1: return d.index(1), ONE_MISMATCH
+ *         if M == 1 and d.count(1) > 1: return nb, AMBIGUOUS
+ *         return nb, NO_MATCH
+ *
+ * The barcode verdict is independent of the feature verdict.  Counts, the five counters and every other output are what
+ * the same context gives without the call.  A read whose verdict is UNREADABLE, AMBIGUOUS or NO_MATCH belongs to the
+ * pseudo-sample nb, "unassigned".
+ *
+ * f2q_set_sample_barcodes: seqs holds n * length bytes, barcode b at seqs[b * length].  It comes once, after f2q_create
+ * and before counting (before or after f2q_set_features; a new library starts a new matrix).  F2Q_ESTATE on an
+ * Extract+Count context, a paired context (f2q_set_mate2), a UMI context of any kind, a context that has the barcodes
+ * already, or after a counting call; afterwards f2q_set_umi, f2q_set_umi_paired, f2q_set_umi_header, f2q_set_mate2 and
+ * the sharded calls with world > 1 are F2Q_ESTATE in turn.  F2Q_EINVAL for n outside 1 .. 1024, length outside 1 .. 16,
+ * start < 0, miss not 0 / 1, a byte that is not A/C/G/T (either case) or two equal barcodes: the message names the
+ * offending barcode.  F2Q_ENOMEM when the matrix ((n + 1) * n_features words of 8 bytes) cannot be had: nothing was
+ * counted into it, and the call that failed (this one, f2q_set_features or the counting call) may be repeated.
+ * From then on every read takes the raw-record road (k_count_demux), through f2q_count_block, f2q_block_from_fastq +
+ * f2q_count_resident / f2q_count_resident_queued, f2q_count_text and f2q_count_file (plain, gzip, BGZF,
+ * F2Q_DEVICE_INFLATE=1, F2Q_HOST_PACK=1); the state lives across the pieces of a file and across counting calls.
+ * F2Q_DEMUX_TABLE=lds / global picks where the kernel reads the barcode table from (A/B runs).
+ *
+ * f2q_read_demux: matrix[b * n_features + f] = reads of sample b assigned to feature f (row n: unassigned);
+ * sample_stats[b * 5 + k] = the five counters of f2q_read_counts restricted to sample b; verdicts = reads with verdict
+ * EXACT, ONE_MISMATCH, AMBIGUOUS, NO_MATCH, UNREADABLE (F2Q_BC_*).  It synchronises as f2q_read_counts does; any pointer
+ * may be NULL; F2Q_ESTATE without f2q_set_sample_barcodes.  f2q_reset_counts zeroes all three.  Invariants:
+ *   sum over b of matrix[b][f] == counts[f];  sum over b of sample_stats[b][k] == stats[k];
+ *   sum(verdicts) == stats[F2Q_READS];  verdicts[EXACT] + verdicts[ONE_MISMATCH] == sum over b < n of sample_stats[b][F2Q_READS].
+ * Not implemented: barcodes in the header comment, in mate 2 or on paired samples, with UMIs, with Extract+Count, on
+ * several ranks, indels or staggers, distance 2, the packed-tile kernels. */
+#define F2Q_BC_EXACT 0
+#define F2Q_BC_ONE_MISMATCH 1
+#define F2Q_BC_AMBIGUOUS 2
+#define F2Q_BC_NO_MATCH 3
+#define F2Q_BC_UNREADABLE 4
+int f2q_set_sample_barcodes(f2q_ctx *ctx, const char *seqs, uint32_t n, int32_t length, int32_t start, int32_t miss);
+int f2q_read_demux(f2q_ctx *ctx, int64_t *matrix /* (n+1) * n_features */, int64_t *sample_stats /* (n+1) * 5 */, int64_t verdicts[5]);
+
 #ifdef __cplusplus
 }
 #endif
