@@ -5,7 +5,10 @@
 //                                        members of exactly 65536 bytes: status OK, bytes equal to the input
 //   inflate_dev_fuzz fuzz <n> [seed]     n damaged members (bit flips, cut-offs, flipped trailers): the core agrees
 //                                        with zlib on accept / reject (an accepted copy has the same bytes)
-//   inflate_dev_fuzz file <path>         records of <u32 member bytes><payload><crc><isize>: prints one status per line
+//   inflate_dev_fuzz file <path> [seed]  records of <u32 member bytes><payload><crc><isize>: prints one status per line
+//   inflate_dev_fuzz bytes <path> <seed> <out>   the same, and writes a record <u32 text bytes><text> per member to <out>
+//                                        (no text unless the status is OK).  With a seed, every payload starts at an
+//                                        offset = seed mod 4 of its block: seeds 0..3 meet every alignment
 //
 // Every member is placed at a random offset of a 4-byte aligned heap block that ends 4 bytes (rounded up) past the
 // trailer, so ASan sees any read outside what the kernel may read.
@@ -25,6 +28,7 @@ using namespace f2q;
 static uint64_t rs = 88172645463325252ull;
 static uint32_t rnd() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return (uint32_t)(rs >> 11); }
 static InflLds *S;
+static int in_res = -1;      // file / bytes: every member's payload starts at an offset = in_res mod 4 (the seed mod 4)
 
 static std::vector<uint8_t> make(int kind, size_t n)
 {
@@ -69,7 +73,7 @@ static void put32(std::vector<uint8_t> &v, uint32_t x) { for (int k = 0; k < 4; 
 static uint32_t run(const std::vector<uint8_t> &member, std::vector<uint8_t> *out)
 {
     if (member.size() < 8) return F2Q_INF_OVERRUN;
-    const size_t off = rnd() % 16, end = off + member.size(), words = (end + 3) / 4;
+    const size_t off = in_res < 0 ? rnd() % 16 : in_res + 4 * (rnd() % 4), end = off + member.size(), words = (end + 3) / 4;
     uint32_t *blk = (uint32_t *)malloc(words * 4);
     uint8_t *b = (uint8_t *)blk;
     for (size_t i = 0; i < words * 4; i++) b[i] = (uint8_t)rnd();                  // garbage around the member
@@ -166,18 +170,24 @@ static int fuzz(int iters)
     return 0;
 }
 
-static int file(const char *path)
+static int file(const char *path, const char *text_path)
 {
-    FILE *f = fopen(path, "rb");
-    if (!f) { printf("cannot open %s\n", path); return 1; }
+    FILE *f = fopen(path, "rb"), *o = text_path ? fopen(text_path, "wb") : nullptr;
+    if (!f || (text_path && !o)) { printf("cannot open %s\n", f ? text_path : path); return 1; }
     uint8_t h[4];
     while (fread(h, 1, 4, f) == 4) {
         const uint32_t n = h[0] | (h[1] << 8) | (h[2] << 16) | ((uint32_t)h[3] << 24);
-        std::vector<uint8_t> m(n);
+        std::vector<uint8_t> m(n), out;
         if (n && fread(m.data(), 1, n, f) != n) { printf("short record\n"); return 1; }
-        printf("%u\n", run(m, nullptr));
+        printf("%u\n", run(m, &out));
+        if (o) {
+            std::vector<uint8_t> len;
+            put32(len, (uint32_t)out.size());
+            if (fwrite(len.data(), 1, 4, o) != 4 || (out.size() && fwrite(out.data(), 1, out.size(), o) != out.size())) { printf("cannot write %s\n", text_path); return 1; }
+        }
     }
     fclose(f);
+    if (o) fclose(o);
     return 0;
 }
 
@@ -188,9 +198,11 @@ int main(int argc, char **argv)
     if (argc > 3) rs ^= (uint64_t)atoll(argv[3]) * 0x9E3779B97F4A7C15ull;
     const std::string mode = argc > 1 ? argv[1] : "corpus";
     int rc = 1;
+    if ((mode == "file" || mode == "bytes") && argc > 3) in_res = atoi(argv[3]) & 3;
     if (mode == "corpus") rc = corpus();
     else if (mode == "fuzz") rc = fuzz(argc > 2 ? atoi(argv[2]) : 1000);
-    else if (mode == "file" && argc > 2) rc = file(argv[2]);
+    else if (mode == "file" && argc > 2) rc = file(argv[2], nullptr);
+    else if (mode == "bytes" && argc > 4) rc = file(argv[2], argv[4]);
     delete S;
     return rc;
 }

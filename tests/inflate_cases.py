@@ -60,10 +60,13 @@ def damaged(text):
     }
 
 
-def bgzf_wrap(members):
-    """BGZF headers ('BC' subfield = member size - 1) around raw members (payload + trailer)"""
+def bgzf_wrap(members, pad=None):
+    """BGZF headers ('BC' subfield = member size - 1) around raw members (payload + trailer).  pad (0..3, or one per
+    member): an extra subfield 'PD' of that many bytes in front of 'BC', which shifts the payload by 4 + pad bytes"""
     out = bytearray()
-    for m in members:
-        bsize = 18 + len(m)
-        out += b"\x1f\x8b\x08\x04\0\0\0\0\x00\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, bsize - 1) + m
+    pads = pad if isinstance(pad, (list, tuple)) else [pad] * len(members)
+    for m, k in zip(members, pads):
+        extra = b"" if k is None else b"PD" + struct.pack("<H", k) + b"\0" * k
+        bsize = 18 + len(extra) + len(m)
+        out += b"\x1f\x8b\x08\x04\0\0\0\0\x00\xff" + struct.pack("<H", 6 + len(extra)) + extra + b"BC" + struct.pack("<HH", 2, bsize - 1) + m
     return bytes(out)
