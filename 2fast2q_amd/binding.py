@@ -26,7 +26,10 @@ EXPORTS = (
     "f2q_set_umi_reads", "f2q_umi_collapse_directional", "f2q_umi_pairs",
     "f2q_set_umi_paired", "f2q_set_umi_header",
     "f2q_set_sample_barcodes", "f2q_read_demux",
+    "f2q_set_strand", "f2q_read_strands",
 )
+
+STRANDS = ("fwd", "rev", "both")            # F2Q_STRAND_FWD / _REV / _BOTH
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
           -8: "EUNSUPPORTED", -9: "EPAIRING"}
@@ -184,6 +187,8 @@ def load(path=None):
     L.f2q_umi_collapse_directional.argtypes = [vp, i64p, i64p]
     L.f2q_set_sample_barcodes.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32]
     L.f2q_read_demux.argtypes = [vp, i64p, i64p, i64p]
+    L.f2q_set_strand.argtypes = [vp, C.c_int32]
+    L.f2q_read_strands.argtypes = [vp, i64p, i64p]
     u32p = C.POINTER(C.c_uint32)
     L.f2q_umi_pairs.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), u32p, u32p, u32p]
     if path == LIB_PATH:
@@ -272,10 +277,15 @@ class Counter:
     read carries one of the barcodes (all of one length, 1 .. 16 bases, at most 1024) at read positions [S, S + L);
     ``barcode_mismatch`` 0 / 1 is the number of substitutions allowed.  Counter mode, single reads, no UMIs;
     ``read_demux()`` returns the count matrix per sample, the five counters per sample and the five barcode verdicts.
+
+    ``strand="fwd" | "rev" | "both"`` is the orientation single reads are counted in (f2q_set_strand): as written, as their
+    reverse complement, or as written first and as the reverse complement when that assigned no feature.  Counter mode,
+    single reads, no UMIs, no sample barcodes; ``read_strands()`` returns the reads assigned on the reverse strand per
+    feature and the four strand counters.
     """
 
     def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, umi_header=None,
-                 sample_barcodes=None, barcode_mismatch=0, **params):
+                 sample_barcodes=None, barcode_mismatch=0, strand="fwd", **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -294,7 +304,9 @@ class Counter:
         self.umi_reads = False
         self.sample_barcodes = None      # (start, [barcodes]) of a demultiplexing context
         self.barcode_mismatch = 0
+        self.strand = "fwd"              # the strand mode of the context (set_strand)
         try:
+            self.set_strand(strand)
             if sample_barcodes is not None:
                 self.set_sample_barcodes(sample_barcodes[0], sample_barcodes[1], barcode_mismatch)
             elif barcode_mismatch:
@@ -403,6 +415,14 @@ class Counter:
         self._check(self._L.f2q_set_sample_barcodes(self._h, b"".join(enc), len(enc), length, int(start), int(mismatch)))
         self.sample_barcodes = (int(start), [b.decode("latin-1").upper() for b in enc])
         self.barcode_mismatch = int(mismatch)
+
+    def set_strand(self, strand):
+        """the orientation single reads are counted in: "fwd", "rev" or "both" (f2q_set_strand); before counting"""
+        if strand not in STRANDS:
+            raise ValueError(f"strand is one of {', '.join(STRANDS)}, not {strand!r}")
+        self._check(self._L.f2q_set_strand(self._h, STRANDS.index(strand)))
+        if strand != "fwd":
+            self.strand = strand
 
     # -- counting: paired-end --
     @staticmethod
@@ -590,6 +610,15 @@ class Counter:
         self._check(self._L.f2q_read_demux(self._h, matrix.ctypes.data_as(i64p) if self.n_features else None,
                                            sstats.ctypes.data_as(i64p), verdicts.ctypes.data_as(i64p)))
         return matrix[:, :self.n_features], sstats, verdicts
+
+    def read_strands(self):
+        """(rev_counts[n_features], extra[4]) as int64 arrays (f2q_read_strands): reads assigned on the reverse strand per
+        feature; extra = assigned forward, reverse perfect, reverse imperfect, reverse strands examined"""
+        rev = np.zeros(max(self.n_features, 1), dtype=np.int64)
+        extra = np.zeros(4, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.f2q_read_strands(self._h, rev.ctypes.data_as(i64p), extra.ctypes.data_as(i64p)))
+        return rev[:self.n_features], extra
 
     def read_umis(self):
         """(umis[n_features], umi_reads, umi_failed): distinct UMIs per feature, assigned reads with a valid / an invalid UMI"""

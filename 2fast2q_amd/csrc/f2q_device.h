@@ -2773,4 +2773,115 @@ F2Q_HD void pack_read(const PackPlan &pl, const R &r, uint32_t planar_nw, Sink &
     sink.len(l | (flagged ? F2Q_LEN_FLAG : 0u) | (lower ? F2Q_LEN_CASE : 0u));      // (read_is_clean: never both kinds of marks)
 }
 
+// ---------------------------------------------------------------------------------------------
+// read orientation (f2q_set_strand): the reverse strand of a single read, and the two-trip loop of k_count_strand
+// ---------------------------------------------------------------------------------------------
+// The rule is stated in include/f2q.h (mirrored, strand_verdict).  The reverse strand of a record is the record whose
+// sequence line is reversed and complemented by comp8 and whose quality line is reversed, each line by ITS OWN length, and
+// then rstrip()-ed again: the leading blanks of a line have become trailing ones.
+struct StrandDev {
+    int32_t mode;                    // F2Q_STRAND_REV / F2Q_STRAND_BOTH (the kernel's instance says the same)
+    unsigned long long *rev_counts;  // [n_features]: reads assigned on the reverse strand
+    unsigned long long *extra;       // [4]: forward assigned, reverse perfect, reverse imperfect, reverse examined
+};
+// general_read's hook on a strand context: the reverse trip counts its feature once more, in rev_counts
+struct StrandHook {
+    unsigned long long *rev;         // nullptr on the forward trip
+    F2Q_HD void assigned(uint32_t f) const { if (rev) acc_add(&rev[f], 1ull); }
+};
+F2Q_HD bool blank8(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == 0x0b || c == 0x0c; }      // bytes.rstrip()
+// 0x80 in every byte of u that equals the byte repeated in k (exact for every byte value)
+F2Q_HD uint32_t eq8x4(uint32_t u, uint32_t k)
+{
+    const uint32_t x = u ^ k;
+    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
+}
+// comp8 on the four bytes of a word: A <-> T differ by 0x15, C <-> G by 0x04, the case bit (0x20) is kept
+F2Q_HD uint32_t comp8x4(uint32_t w)
+{
+    const uint32_t u = w & 0xDFDFDFDFu;                      // (u == 'A' exactly for 'A' and 'a')
+    const uint32_t at = eq8x4(u, 0x41414141u) | eq8x4(u, 0x54545454u), cg = eq8x4(u, 0x43434343u) | eq8x4(u, 0x47474747u);
+    return w ^ ((at >> 7) * 0x15u) ^ ((cg >> 7) * 0x04u);
+}
+// One staged line mirrored in place.  The line is the n bytes at byte offset mis (0 .. 3) of the words w[0 ..
+// (mis + n + 3) / 4); the words are swapped end for end with their bytes reversed (one byte permute each; COMP: the
+// sequence line, complemented four bytes at a time), so the byte at mis + n - 1 lands at the offset 4 * words - (mis + n)
+// of the first word: that is the mirrored line's misalignment, and no shift is needed.  n is cut by the line's leading
+// blanks, which are now behind its end.  Touches nothing outside the words the line was staged in.
+template <bool COMP>
+F2Q_HD void mirror_line(uint32_t *w, uint32_t &mis, int &n)
+{
+    if (n <= 0) return;
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(w) + mis;
+    int lead = 0;
+    while (lead < n && blank8(b[lead])) lead++;
+    const uint32_t end = mis + (uint32_t)n, nw = (end + 3u) >> 2;
+    uint32_t i = 0, j = nw - 1u;
+    for (; i < j; i++, j--) {
+        uint32_t lo = __builtin_bswap32(w[j]), hi = __builtin_bswap32(w[i]);
+        if (COMP) { lo = comp8x4(lo); hi = comp8x4(hi); }
+        w[i] = lo; w[j] = hi;
+    }
+    if (i == j) { const uint32_t v = __builtin_bswap32(w[i]); w[i] = COMP ? comp8x4(v) : v; }
+    mis = 4u * nw - end;
+    n -= lead;
+}
+// A line that was not staged, behind the same [] as a pointer: as written, or (rev) from its end, the sequence line
+// (comp) complemented byte by byte -- MateBytes' manner, for a record in global memory
+template <class P>
+struct StrandBytes {
+    P p; int last; bool rev, comp;   // last: the index of the line's last byte as written
+    F2Q_HD uint8_t operator[](int j) const
+    {
+        if (!rev) return p[j];
+        const uint8_t c = p[last - j];
+        return comp ? comp8(c) : c;
+    }
+};
+// One record of a strand context: a lane of k_count_strand<BOTH>.  sw / qw: the words the two lines are staged in (their
+// bytes at offsets ms / mq), or nullptr: the record is walked where it lies (gseq / gqual).  BOTH: the forward strand
+// first, the reverse strand only when the forward strand assigned nothing; else the reverse strand alone.  The routine has
+// ONE call site per layout, inside a loop of at most two trips; a trip's verdict goes to one[] and the read's to st[] when
+// it is known.  ext[]: thread-local sums in StrandDev::extra's order.
+template <bool BOTH, class G>
+F2Q_HD void strand_read(const RunDev &run, const LibDev &lib, const EcDev &ec, const Accum &acc, const StrandDev &sd,
+                        uint32_t *sw, uint32_t *qw, uint32_t ms, uint32_t mq, G gseq, G gqual, int r, int qn,
+                        unsigned long long gi, unsigned long long st[5], unsigned long long ext[4])
+{
+    StrandBytes<G> as{gseq, r - 1, false, true}, aq{gqual, qn - 1, false, false};
+    unsigned long long keep[5] = {0, 0, 0, 0, 0};
+#pragma unroll 1
+    for (int trip = BOTH ? 0 : 1; trip < 2; trip++) {
+        if (trip == 1) {
+            if (sw) { mirror_line<true>(sw, ms, r); mirror_line<false>(qw, mq, qn); }
+            else {
+                int lead = 0;
+                while (lead < r && blank8(gseq[lead])) lead++;
+                r -= lead; as.rev = true;
+                lead = 0;
+                while (lead < qn && blank8(gqual[lead])) lead++;
+                qn -= lead; aq.rev = true;
+            }
+            ext[3]++;
+        }
+        unsigned long long one[5] = {0, 0, 0, 0, 0};
+        const StrandHook hook{trip ? sd.rev_counts : nullptr};
+        if (sw) general_read<const uint8_t *, true, false, StrandHook>(run, lib, ec, acc, reinterpret_cast<const uint8_t *>(sw) + ms, r,
+                                                                        reinterpret_cast<const uint8_t *>(qw) + mq, qn, gi, one, nullptr, 0, 0, hook);
+        else general_read<StrandBytes<G>, true, false, StrandHook>(run, lib, ec, acc, as, r, aq, qn, gi, one, nullptr, 0, 0, hook);
+        const bool hit = (one[1] | one[2]) != 0;
+        if (trip == 0) {
+#pragma unroll
+            for (int k = 0; k < 5; k++) keep[k] = one[k];
+            if (hit) { ext[0]++; break; }                    // an assigned forward strand is never re-examined
+        } else if (hit || !BOTH) {                           // (BOTH and nobody assigns it: counted as the forward strand counts it)
+#pragma unroll
+            for (int k = 0; k < 5; k++) keep[k] = one[k];
+            ext[1] += one[1]; ext[2] += one[2];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; k++) st[k] += keep[k];
+}
+
 } // namespace f2q

@@ -35,6 +35,7 @@ using namespace f2q;
 #include "f2q_assign_kernels.h"
 #include "f2q_umi_kernels.h"
 #include "f2q_demux_kernels.h"
+#include "f2q_strand_kernels.h"
 
 // ===============================================================================================
 // host side
@@ -135,6 +136,14 @@ struct f2q_ctx {
         bool lds_table = false;          // k_count_demux<true> (F2Q_DEMUX_TABLE=lds, and the table fits)
         bool shmem_set = false;          // the instance has been told its dynamic LDS size
     } demux;
+    // read orientation (f2q_set_strand): reads assigned on the reverse strand per feature and the four strand counters; they
+    // live across pieces and counting calls
+    struct {
+        int32_t mode = 0;                // F2Q_STRAND_FWD (a plain context) / _REV / _BOTH
+        StrandDev dev{};
+        std::vector<void *> allocs;      // rev_counts + extra, one allocation
+        uint64_t words = 0;              // of that allocation: max(n_features, 1) + 4
+    } strand;
     bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
     int n_cu = 256;
@@ -480,6 +489,28 @@ static int demux_clear(f2q_ctx *c)
     return F2Q_OK;
 }
 
+// the reverse-strand counts and the strand counters given back: f2q_destroy, and a new library
+static void strand_drop(f2q_ctx *c)
+{
+    free_all(c, c->strand.allocs);
+    c->strand.dev.rev_counts = nullptr; c->strand.dev.extra = nullptr; c->strand.words = 0;
+}
+
+// rev_counts and the four counters once the mode and the features are both known, zeroed.  A failure leaves the context as
+// it was: the call that led here may simply be repeated.
+static int strand_alloc(f2q_ctx *c)
+{
+    if (!c->strand.mode || c->strand.dev.rev_counts) return F2Q_OK;
+    const uint64_t nf = std::max<uint64_t>(c->lib_h.n_features, 1);
+    unsigned long long *w = nullptr; std::vector<void *> owner;
+    if (dev_alloc(c, (size_t)(nf + 4), &w, owner, 0)) {
+        free_all(c, owner);
+        return fail(c, F2Q_ENOMEM, "no device memory for the reverse-strand counts (" + std::to_string(nf) + " counters): " + c->err);
+    }
+    c->strand.dev.rev_counts = w; c->strand.dev.extra = w + nf; c->strand.allocs = owner; c->strand.words = nf + 4;
+    return F2Q_OK;
+}
+
 extern "C" void f2q_destroy(f2q_ctx *c)
 {
     if (!c) return;
@@ -493,6 +524,7 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     if (c->trace && c->umi.on) fprintf(stderr, "[f2q trace] UMI set: %llu slots, %llu rehashes\n", (unsigned long long)c->umi.n_slots, (unsigned long long)c->umi.rehashes);
     umi_drop(c);
     demux_drop(c);
+    strand_drop(c);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
@@ -548,6 +580,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (rc) return rc;
     if (c->umi.on) umi_drop(c);                       // a new library starts a new set
     if (c->demux.on) { demux_drop(c); if ((rc = demux_alloc(c))) return rc; }      // ... and a new matrix: a row has a word per feature
+    if (c->strand.mode) { strand_drop(c); if ((rc = strand_alloc(c))) return rc; }  // ... and reverse-strand counts that start afresh
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
     // symbol of any feature), every other odd symbol still sends the read to the byte-exact routine
@@ -570,6 +603,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
     }
     if (c->umi.on && c->umi.dev.umis) if (int rc = umi_clear(c)) return rc;
     if (c->demux.on && c->demux.dev.matrix) if (int rc = demux_clear(c)) return rc;
+    if (c->strand.mode && c->strand.dev.rev_counts) HIPC(c, hipMemsetAsync(c->strand.dev.rev_counts, 0, c->strand.words * sizeof(unsigned long long), c->stream));
     c->reads_seen = 0;
     c->ec_gen++;
     // no host synchronisation: the clear is ordered on the context's stream like every launch and read-back after it
@@ -603,6 +637,7 @@ extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 }
 
 // ---- distinct UMIs per feature: the ABI ---------------------------------------------------------------------------
+static const char *const STRAND_NO_UMI = "a context with a strand mode (f2q_set_strand: rev / both) takes no UMIs: the two are not combined";
 static const char *const DEMUX_NO_UMI = "a demultiplexing context (f2q_set_sample_barcodes) takes no UMIs: the two are not combined";
 // what f2q_set_umi and f2q_set_umi_paired share once the window is in umi.dev
 static void umi_enable(f2q_ctx *c)
@@ -620,6 +655,7 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi takes a Counter context: Extract+Count assigns no read to a feature");
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) takes f2q_set_umi_paired");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
+    if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
     if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
         return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
@@ -636,6 +672,7 @@ extern "C" int f2q_set_umi_header(f2q_ctx *c, int32_t sep, int32_t length)
     if (!c) return F2Q_EINVAL;
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_header takes a Counter context: Extract+Count assigns no read to a feature");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
+    if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_header comes once, in place of f2q_set_umi / f2q_set_umi_paired and before counting");
     const bool alnum = (sep >= '0' && sep <= '9') || (sep >= 'A' && sep <= 'Z') || (sep >= 'a' && sep <= 'z');
     if (sep < 33 || sep > 126 || alnum || sep == '+' || length < 1 || length > F2Q_UMI_MAXLEN)
@@ -655,6 +692,7 @@ extern "C" int f2q_set_umi_paired(f2q_ctx *c, int32_t start1, int32_t length1, i
     if (!c) return F2Q_EINVAL;
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a Counter context: Extract+Count assigns no pair to a feature");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
+    if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
     if (!c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a paired context: call f2q_set_mate2 first (single reads: f2q_set_umi)");
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired comes once, after f2q_set_mate2 and before counting");
     if (start1 < 0 || start1 > 0x3FFFFFFF || start2 < 0 || start2 > 0x3FFFFFFF || length1 < 0 || length2 < 0 ||
@@ -701,6 +739,7 @@ extern "C" int f2q_set_sample_barcodes(f2q_ctx *c, const char *seqs, uint32_t n,
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes takes a Counter context: Extract+Count with sample barcodes is not implemented");
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes takes single reads: a paired context (f2q_set_mate2) is not demultiplexed");
     if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a UMI context: sample barcodes and UMIs are not combined");
+    if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
     if (c->demux.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes comes once, after f2q_create and before counting");
     std::string up, err;
     if (int rc = demux_validate(seqs, n, length, start, miss, up, err)) return fail(c, rc, err);
@@ -743,6 +782,46 @@ extern "C" int f2q_read_demux(f2q_ctx *c, int64_t *matrix, int64_t *sample_stats
     if (matrix) for (uint64_t i = 0; i < rows * nf; i++) matrix[i] = hm.empty() ? 0 : (int64_t)hm[i];
     if (sample_stats) for (uint64_t i = 0; i < rows * 5; i++) sample_stats[i] = (int64_t)hs[i];
     if (verdicts) for (int k = 0; k < 5; k++) verdicts[k] = (int64_t)hs[rows * 5 + k];
+    return F2Q_OK;
+}
+
+// ---- read orientation: the ABI (include/f2q.h) ------------------------------------------------------------------------
+extern "C" int f2q_set_strand(f2q_ctx *c, int32_t mode)
+{
+    if (!c) return F2Q_EINVAL;
+    if (mode != F2Q_STRAND_FWD && mode != F2Q_STRAND_REV && mode != F2Q_STRAND_BOTH)
+        return fail(c, F2Q_EINVAL, "the strand mode is F2Q_STRAND_FWD (0), F2Q_STRAND_REV (1) or F2Q_STRAND_BOTH (2), not " + std::to_string(mode));
+    if (mode == F2Q_STRAND_FWD) return F2Q_OK;               // the record as written: what every context does
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) takes a Counter context: Extract+Count on the reverse strand is not implemented");
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) takes single reads: a paired context (f2q_set_mate2) has its own orientation (rc2)");
+    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a UMI context: a strand mode and UMIs are not combined");
+    if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
+    if (c->strand.mode || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) comes once, after f2q_create and before counting");
+    HIPC(c, hipSetDevice(c->device));
+    c->strand.mode = mode; c->strand.dev = StrandDev{}; c->strand.dev.mode = mode;
+    if (c->have_lib) if (int rc = strand_alloc(c)) { c->strand.mode = 0; return rc; }      // (nothing else was touched: as if the call had not been made)
+    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
+    c->force_general = true;
+    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
+    c->plan.inband_n = false; c->plan.n_only = false;
+    if (c->trace) fprintf(stderr, "[f2q trace] strand mode %s: every read takes k_count_strand<%s>\n", mode == F2Q_STRAND_BOTH ? "both" : "rev", mode == F2Q_STRAND_BOTH ? "true" : "false");
+    return F2Q_OK;
+}
+
+extern "C" int f2q_read_strands(f2q_ctx *c, int64_t *rev_counts, int64_t extra[4])
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->strand.mode) return fail(c, F2Q_ESTATE, "no strand mode: call f2q_set_strand with F2Q_STRAND_REV or F2Q_STRAND_BOTH first");
+    HIPC(c, hipSetDevice(c->device));
+    const uint64_t nf = c->have_lib ? c->lib_h.n_features : 0;
+    std::vector<unsigned long long> h;
+    if (c->strand.dev.rev_counts) {                          // (no library yet: nothing can have been counted)
+        try { h.resize(c->strand.words); } catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy the reverse-strand counts"); }
+        HIPC(c, hipMemcpyAsync(h.data(), c->strand.dev.rev_counts, c->strand.words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (rev_counts) for (uint64_t f = 0; f < nf; f++) rev_counts[f] = h.empty() ? 0 : (int64_t)h[f];
+    if (extra) for (int k = 0; k < 4; k++) extra[k] = h.empty() ? 0 : (int64_t)h[c->strand.words - 4 + k];
     return F2Q_OK;
 }
 
@@ -1447,6 +1526,15 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
         EC_POINT(c, "k_count_demux");
         return F2Q_OK;
     }
+    if (c->strand.mode) {                                        // the same road on the reverse strand, or on both (f2q_set_strand)
+        if ((rc = strand_alloc(c))) return rc;                   // (only after an allocation that failed: a retry)
+        if (c->strand.mode == F2Q_STRAND_BOTH) hipLaunchKernelGGL(k_count_strand<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->strand.dev);
+        else hipLaunchKernelGGL(k_count_strand<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->strand.dev);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, c->strand.mode == F2Q_STRAND_BOTH ? "k_count_strand<both>" : "k_count_strand<rev>");
+        return F2Q_OK;
+    }
     if (rb.len1) hipLaunchKernelGGL(k_count_general<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     else hipLaunchKernelGGL(k_count_general<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     HIPC(c, hipGetLastError());
@@ -1584,6 +1672,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
     if (!k0) { k0 = c->ev_k0; k1 = c->ev_k1; }          // (a queued step brings its own pair)
     if (c->prm.mode == 0 && !c->have_lib) return fail(c, F2Q_ESTATE, "f2q_set_features must be called before counting in Counter mode");
     if (c->umi.on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
+    if (c->strand.mode && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_strand: a context with a strand mode counts single raw records only");
     if (c->demux.on && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_sample_barcodes: a demultiplexing context counts single raw records only");
     if (c->umi.hdr_sep && b->rb.n && !b->rb.hdr_umi) return fail(c, F2Q_ESTATE, "the block was made before f2q_set_umi_header (or without headers): its records carry no header UMI");
     c->counted = true;
@@ -2109,6 +2198,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
     if (c->have_lib || c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_mate2 comes once, after f2q_create and before f2q_set_features");
     if (c->umi.on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only: f2q_set_mate2 comes first, then f2q_set_umi_paired");
     if (c->demux.on) return fail(c, F2Q_ESTATE, "a demultiplexing context (f2q_set_sample_barcodes) counts single reads only");
+    if (c->strand.mode) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts single reads only");
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
     for (int i = 0; i < n_start2; i++) if (start2[i] < 0) return fail(c, F2Q_EINVAL, "a mate-2 window starts before the mate");
@@ -2786,6 +2876,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
     if (int rc = single_only(c)) return rc;
     if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
+    if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     size_t CH = file_chunk_bytes((size_t)256 << 20);
     TextSource src;
@@ -3071,6 +3162,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
     if (int rc = single_only(c)) return rc;
     if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
+    if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }

@@ -165,6 +165,8 @@ def _counter_kwargs(param):
         sb = param['sample_barcodes']
         kwargs['sample_barcodes'] = (sb['start'], tuple(sb['barcodes']))
         kwargs['barcode_mismatch'] = sb['miss']
+    if param.get('strand'):                         # --strand rev / both (f2q_set_strand); part of the key too
+        kwargs['strand'] = param['strand']
     return kwargs
 
 
@@ -286,6 +288,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         raise RuntimeError("--umih: the UMI sets are not merged across several ranks; run one process")
     if param.get('sample_barcodes') and sharding.world().size > 1:
         raise RuntimeError("--sb: the demultiplexed counts are not merged across several ranks; run one process")
+    if param.get('strand') and sharding.world().size > 1:
+        raise RuntimeError("--strand: the reverse-strand counts are not merged across several ranks; run one process")
     ctx = _context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
@@ -327,6 +331,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
                 rec["pair_table"] = ctx.umi_pairs() if not param.get("delete", True) else None
         if param.get('sample_barcodes'):            # --sb: the count matrix, the counters per sample barcode, the verdicts (f2q_read_demux)
             param.setdefault('demux_counted', {})[raw] = ctx.read_demux()
+        if param.get('strand'):                     # --strand rev / both: reads assigned on the reverse strand, the strand counters (f2q_read_strands)
+            param.setdefault('strand_counted', {})[raw] = ctx.read_strands()
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -427,6 +433,12 @@ def aligner(i, raw, features, param, reads_stats):
                                 dict(zip(binding.STAT_NAMES, (int(n) for n in sstats[b]))))
                    for b, bname in enumerate(param['sample_barcodes']['names'] + ["unassigned"])]
         param.setdefault("demux_samples", {})[sample.name] = (columns, [int(n) for n in verdicts])
+    if raw in param.get('strand_counted', {}):       # --strand rev / both: the sample's column split by the strand a read was counted on
+        rev_counts, extra = param['strand_counted'].pop(raw)
+        split = [(f.name, int(f.counts) - int(n), int(n)) for f, n in zip(features.values(), rev_counts)]
+        columns = [SampleResult(f"{sample.name}:fwd", value, unit, _sample_rows((name, fwd) for name, fwd, _ in split), {}),
+                   SampleResult(f"{sample.name}:rev", value, unit, _sample_rows((name, rev) for name, _, rev in split), {})]
+        param.setdefault("strand_samples", {})[sample.name] = (columns, [int(n) for n in extra])
     if not param['Progress bar']:
         colourful_errors("INFO", f"Sample {sample.name} was processed in {value} {unit}")
     param.setdefault("samples", {})[sample.name] = sample     # a later file of the same name replaces the earlier one,
@@ -500,6 +512,9 @@ def initializer(cmd):
         sb = param['sample_barcodes']
         print(f" Reads are demultiplexed by {len(sb['barcodes'])} inline sample barcodes of {sb['path']}")
         print(f" {sample_barcodes_header(param)[1:]}")
+    if param.get('strand'):
+        print(f" Reads are counted on {'the reverse strand' if param['strand'] == 'rev' else 'the forward strand, else on the reverse strand'}")
+        print(f" {strand_header(param)[1:]}")
     if param.get('umi_mismatch'):
         print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
     if param.get('umi_rule') == 'directional':
@@ -557,6 +572,11 @@ def sample_barcodes_header(param):
     """the line a --sb run adds to the parameter print-out and to the head of <name>_stats.csv"""
     sb = param['sample_barcodes']
     return f"#Sample barcodes, start, length, mismatches: {sb['start']},{len(sb['barcodes'][0])},{sb['miss']}"
+
+
+def strand_header(param):
+    """the line a --strand rev / both run adds to the parameter print-out and to the head of <name>_stats.csv"""
+    return f"#Strand: {param['strand']}"
 
 
 def parse_umih(text):
@@ -617,6 +637,7 @@ def input_parser(argv=None):
     ap.add_argument("--sb", help="The full path to a .csv file with rows name,barcode: the reads of every file are demultiplexed by an inline sample barcode (1-16 bases, at most 1024 barcodes of one length) while they are counted (<name>_demux.csv). Counter mode, single reads, one process")
     ap.add_argument("--sbs", help="With --sb: the start position of the sample barcode within the read (default = 0)")
     ap.add_argument("--sbm", help="With --sb: mismatches allowed in the sample barcode, 0 or 1 (default = 0)")
+    ap.add_argument("--strand", help="fwd (default), rev or both: the orientation the reads are counted in. rev: every read is reverse-complemented first; both: a read that is assigned no feature as sequenced is tried reverse-complemented (<name>_strand.csv). Counter mode, single reads, one process")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
     if args.v is not None:
@@ -752,6 +773,19 @@ def input_parser(argv=None):
             colourful_errors("FATAL", f"--sb {args.sb}: {loaded}.")
             sys.exit(2)
         p['sample_barcodes'] = dict(path=args.sb, names=loaded[0], barcodes=loaded[1], start=int(args.sbs or 0), miss=int(args.sbm or 0))
+    if args.strand is not None:
+        if args.strand not in ("fwd", "rev", "both"):
+            colourful_errors("FATAL", f"--strand {args.strand}: expected fwd, rev or both.")
+            sys.exit(2)
+        if args.strand != "fwd":                                 # (fwd is a run without the flag)
+            if p['Running Mode'] != "C":
+                colourful_errors("FATAL", f"--strand {args.strand} only has a meaning in Counter mode: it cannot be combined with --mo EC.")
+                sys.exit(2)
+            others = [f for f, v in (("--pe", args.pe), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2), ("--umih", args.umih), ("--sb", args.sb)) if v is not None]
+            if others:
+                colourful_errors("FATAL", f"--strand {args.strand} cannot be combined with {' / '.join(others)}: the reverse strand is read from single reads without UMIs or sample barcodes.")
+                sys.exit(2)
+            p['strand'] = args.strand
     if args.assign is not None:
         if p['Running Mode'] != "EC":
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
@@ -787,6 +821,9 @@ def file_sizer_split(param):
         sys.exit(2)
     if param.get('sample_barcodes') and sharding.world().size > 1:
         colourful_errors("FATAL", "--sb: the demultiplexed counts are not merged across several ranks; run one process.")
+        sys.exit(2)
+    if param.get('strand') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--strand: the reverse-strand counts are not merged across several ranks; run one process.")
         sys.exit(2)
     if param.get('paired'):                                      # one sample per pair, named after its R1 file
         if sharding.world().size > 1:
@@ -897,6 +934,8 @@ def run_headers(param):
         lines.append("#UMI collapse rule: directional")
     if param.get('sample_barcodes'):
         lines.append(sample_barcodes_header(param))
+    if param.get('strand'):
+        lines.append(strand_header(param))
     return lines
 
 
@@ -945,6 +984,10 @@ def compiling(param):
         dhead, dtable = _table_of([column for s in ordered for column in param["demux_samples"].get(s.name, ((), ()))[0]])
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_demux.csv"),
                    [dhead] + [[feature] + counts for feature, counts in dtable.items()])
+    if param.get("strand_samples"):                  # --strand rev / both: per file, in <name>.csv's column order, the forward and the reverse column
+        shead, stable = _table_of([column for s in ordered for column in param["strand_samples"].get(s.name, ((), ()))[0]])
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_strand.csv"),
+                   [shead] + [[feature] + counts for feature, counts in stable.items()])
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -981,6 +1024,10 @@ DEMUX_VERDICT_STATS_HEAD = ["#Sample name (sample barcodes)", "Number of reads w
 DEMUX_SAMPLE_STATS_HEAD = ["#Sample name:sample barcode"] + STATS_HEAD[3:]
 
 
+STRAND_STATS_HEAD = ["#Sample name (strands)", "Number of reads assigned on the forward strand", "Number of reads assigned on the reverse strand without mismatches",
+                     "Number of reads assigned on the reverse strand with mismatches", "Number of reads whose reverse strand was examined"]
+
+
 def run_stats(headers, param, compiled, head, ordered):
     """<name>_stats.csv -- the run's '#key: value' lines, the column names, one row of numbers per sample (:1386-1412,
     taken from the counters themselves) -- plus the four overview plots (:1414-1527)"""
@@ -999,6 +1046,9 @@ def run_stats(headers, param, compiled, head, ordered):
             [c.name, c.stats["reads"], c.stats["perfect_counter"] + c.stats["imperfect_counter"], c.stats["perfect_counter"],
              c.stats["imperfect_counter"], c.stats["non_aligned_counter"], c.stats["quality_failed"]]
             for s in ordered if s.name in demux for c in demux[s.name][0]]
+    strands = param.get("strand_samples", {})
+    if strands:                                                  # --strand rev / both: the four strand counters per file
+        global_stat += [STRAND_STATS_HEAD] + [[s.name] + strands[s.name][1] for s in ordered if s.name in strands]
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib

@@ -493,6 +493,63 @@ int f2q_set_umi_header(f2q_ctx *ctx, int32_t sep, int32_t length);
 int f2q_set_sample_barcodes(f2q_ctx *ctx, const char *seqs, uint32_t n, int32_t length, int32_t start, int32_t miss);
 int f2q_read_demux(f2q_ctx *ctx, int64_t *matrix /* (n+1) * n_features */, int64_t *sample_stats /* (n+1) * 5 */, int64_t verdicts[5]);
 
+/* ---- read orientation: single reads counted on the reverse strand, or on either ------------------
+ * Ligation-based amplicon libraries, PCR-free preps and pools with flipped amplicons come off the sequencer with the
+ * feature on the reverse strand of some or all reads: reverse-complemented, at the other end of the read.
+ * f2q_set_strand makes a single-end Counter context read every record as its mirror image (F2Q_STRAND_REV), or as
+ * written first and as its mirror image when that assigned no feature (F2Q_STRAND_BOTH).
+ *
+ * The rule.  verdict(seq, qual) is the reference's decision for a record whose rstrip()-ed lines 2 and 4 are seq and
+ * qual: the feature or none, and which of the five counters the read adds to.
+ *
+ *     COMP = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")     # comp8: every other byte stays what it is, case is kept
+ *
+ *     def mirrored(seq, qual):
+ *         # each line is mirrored by ITS OWN length; quality bytes are never translated.  The second rstrip() is
+ *         # deliberate: the reverse strand of a record is exactly what the reference would read from the four lines
+ *         # "@", revcomp(seq), "+", reversed(qual) -- leading blanks of a line become trailing ones and fall away
+ *         return seq.translate(COMP)[::-1].rstrip(), qual[::-1].rstrip()
+ *
+ *     def strand_verdict(seq, qual, mode):                 # -> (verdict, strand)
+ *         if mode == REV:
+ *             return verdict(*mirrored(seq, qual)), REVERSE
+ *         F = verdict(seq, qual)
+ *         if mode == FWD or F.feature is not None:         # forward first: an assigned forward strand is never re-examined,
+ *             return F, FORWARD                            # not even when it is imperfect and the reverse strand is perfect
+ *         R = verdict(*mirrored(seq, qual))
+ *         return (R, REVERSE) if R.feature is not None else (F, FORWARD)   # nobody assigns it: counted as the forward strand counts it
+ *
+ * It holds for every read shape of the single-end Counter road: fixed windows (one or several, ':'-joined), --us/--ds
+ * anchors with --msu/--msd/--qsu/--qsd, any --m, any --ph.  Consequences: BOTH on a sample without reverse-strand reads
+ * gives the plain run; counts under BOTH are >= counts under FWD for every feature; REV on a text equals a plain run on
+ * the text with every record mirrored.
+ *
+ * f2q_set_strand comes after f2q_create and before counting (before or after f2q_set_features).  Mode 0 is accepted on
+ * every context, at any time, and changes nothing.  F2Q_EINVAL for a mode outside the three.  With a non-zero mode:
+ * F2Q_ESTATE on an Extract+Count context, a paired context (f2q_set_mate2), a UMI context of any kind, a demultiplexing
+ * context (f2q_set_sample_barcodes), a context that has a non-zero mode already, or after a counting call; afterwards
+ * f2q_set_mate2, f2q_set_umi, f2q_set_umi_paired, f2q_set_umi_header, f2q_set_sample_barcodes and the sharded calls with
+ * world > 1 are F2Q_ESTATE in turn, with a message that names the strand mode.  From then on every read takes the
+ * raw-record road (k_count_strand), through f2q_count_block, f2q_block_from_fastq + f2q_count_resident /
+ * f2q_count_resident_queued, f2q_count_text and f2q_count_file (plain, gzip, BGZF, F2Q_DEVICE_INFLATE=1,
+ * F2Q_HOST_PACK=1); the state lives across the pieces of a file and across counting calls.
+ *
+ * f2q_read_strands: rev_counts[f] = reads assigned to feature f on the reverse strand; extra[0] = reads assigned on the
+ * forward strand, extra[1] / extra[2] = reads assigned perfectly / imperfectly on the reverse strand, extra[3] = reads
+ * whose reverse strand was examined.  It synchronises as f2q_read_counts does; either pointer may be NULL; F2Q_ESTATE
+ * without a non-zero mode.  f2q_reset_counts zeroes it; a new library starts it afresh.  Invariants:
+ *   rev_counts[f] <= counts[f];  sum(rev_counts) == extra[1] + extra[2];
+ *   extra[0] + extra[1] + extra[2] == stats[F2Q_PERFECT] + stats[F2Q_IMPERFECT];
+ *   BOTH: extra[3] == stats[F2Q_READS] - extra[0];
+ *   REV:  extra[0] == 0, extra[3] == stats[F2Q_READS], rev_counts == counts.
+ * Not implemented: Extract+Count, paired samples, UMIs and sample barcodes with a strand mode, several ranks, the best
+ * of both strands by distance, the packed-tile kernels. */
+#define F2Q_STRAND_FWD 0
+#define F2Q_STRAND_REV 1
+#define F2Q_STRAND_BOTH 2
+int f2q_set_strand(f2q_ctx *ctx, int32_t mode);
+int f2q_read_strands(f2q_ctx *ctx, int64_t *rev_counts /* n_features */, int64_t extra[4]);
+
 #ifdef __cplusplus
 }
 #endif
