@@ -152,7 +152,7 @@ struct f2q_ctx {
     bool force_general = false;           // F2Q_FORCE_GENERAL=1: every read through the byte-exact general kernel (cross-checks)
     bool force_v1 = false;                // F2Q_FORCE_V1=1: keep the one-read-per-lane kernel (A/B runs)
     bool no_lt = false;                   // F2Q_NO_LT=1: never the LDS-table kernel (A/B runs, cross-checks)
-    uint32_t lt_max_wgs = 0;              // F2Q_LT_WGS=n: at most n workgroups of the kernels that count in u16 LDS counters -- k_count_fixed4_lds, k_count_anchor_lt, k_count_anchor_pairs (tests: many reads per histogram) -- and of k_part_scatter, k_count_fixed4, k_count_multi4 (tests: several tiles per wave on a small block)
+    uint32_t lt_max_wgs = 0;              // F2Q_LT_WGS=n: at most n workgroups of the kernels that count in u16 LDS counters -- k_count_fixed4_lds, k_count_anchor_lt, k_count_anchor_pairs (tests: many reads per histogram) -- and of k_part_scatter, k_count_fixed4, k_count_multi4, k_extract_anchor_hot, k_extract_fixed4_hot (tests: several tiles per wave on a small block)
     bool no_pt = false;                   // F2Q_NO_PT=1: never the partitioned-table kernels (A/B runs, cross-checks)
     uint64_t pt_chunk_reads = (uint64_t)1 << 28;   // F2Q_PT_CHUNK: most reads per scatter/count round of the partitioned path (1.7 GB of streams per 200 M reads; 400 M reads in two rounds run 8 % faster than in six)
     uint64_t pt_min_reads = (uint64_t)1 << 21;     // F2Q_PT_MIN_READS: smaller blocks keep the packed-table kernel (three launches and the
@@ -1613,14 +1613,16 @@ static int launch_hot(f2q_ctx *c, const PackedBlock &v, uint64_t slot_base, Accu
     if (!v.planar_nw) {
         // fixed window: one wave per tile
         const uint32_t wgs = (v.n_tiles + F2Q_FH_WAVES - 1) / F2Q_FH_WAVES;
-        const uint32_t fgrid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu);
+        uint32_t fgrid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu);
+        if (c->lt_max_wgs) fgrid = std::min<uint32_t>(fgrid, c->lt_max_wgs);
         auto kern = learning ? k_extract_fixed4_hot<true> : k_extract_fixed4_hot<false>;
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         hipLaunchKernelGGL(kern, dim3(fgrid), dim3(F2Q_FH_THREADS), shmem, c->stream, c->run_d, c->ec, c->hot, v, acc, c->reads_seen,
                            c->defer_d, slot_base, (uint64_t)c->defer_cap);
     } else {
         const uint32_t groups = (v.n_tiles + F2Q_HOT_GROUPS - 1) / F2Q_HOT_GROUPS;
-        const uint32_t grid = std::min<uint32_t>(groups, (uint32_t)c->n_cu);
+        uint32_t grid = std::min<uint32_t>(groups, (uint32_t)c->n_cu);
+        if (c->lt_max_wgs) grid = std::min<uint32_t>(grid, c->lt_max_wgs);
         anchored_geom(v.planar_nw, c->plan.kb, same_q(c->run_h), [&](auto NW, auto KB, auto SQ) {
             auto kern = learning ? k_extract_anchor_hot<NW, KB, SQ, true> : k_extract_anchor_hot<NW, KB, SQ, false>;
             (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);

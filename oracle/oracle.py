@@ -161,7 +161,8 @@ class Oracle:
         raw = C.create_string_buffer(max(nb, 1))
         offs = (C.c_int64 * (n + 1))()
         L.orc_get_keys(self._h, raw, offs)
-        return [raw.raw[offs[i]:offs[i + 1]].decode("latin-1") for i in range(n)]
+        text, offs = raw.raw, list(offs)                           # (one copy of the buffer, not one per key)
+        return [text[offs[i]:offs[i + 1]].decode("latin-1") for i in range(n)]
 
     def result_dict(self):
         """{key: count}: Counter mode keys are feature sequences, EC mode the de-novo strings."""

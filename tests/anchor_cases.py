@@ -94,6 +94,18 @@ def make_read(rng, kind, cassettes, which, max_len, prefix_max, tail_max, prefix
             elif kind == "up_mm2": u = sub(rng, u, 2)
             elif kind == "down_mm2": d = sub(rng, d, 2)
             elif kind == "no_up" and k == 0: seq, u, w = "", "", w[rng.randrange(1, len(w)):]
+            # Extract+Count kinds (tests/ec_cases.py): the window's own length, 'N's at stated places, case, an odd symbol
+            elif kind.startswith("len:"): w = (w * 4)[:int(kind[4:])]                       # len:L -- a window of L bases
+            elif kind.startswith("nn:"):                                                     # nn:L:K:first|last -- L bases, K 'N's, one of
+                _, L, K, where = kind.split(":")                                             # them at the first / last position
+                L, K = int(L), int(K)
+                b = list((w * 2)[:L])
+                for p in ([0] if where == "first" else [L - 1]) + [3 + 4 * j for j in range(K - 1)]:
+                    b[p] = "N"
+                w = "".join(b)
+                assert w.count("N") == K
+            elif kind == "lower": w = w.lower()
+            elif kind == "odd": w = w[:7] + "R" + w[8:]
             a = len(seq)
             if kind == "q_win_first": low = a + len(u)
             elif kind == "q_win_last": low = a + len(u) + len(w) - 1
