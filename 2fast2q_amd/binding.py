@@ -27,9 +27,11 @@ EXPORTS = (
     "f2q_set_umi_paired", "f2q_set_umi_header",
     "f2q_set_sample_barcodes", "f2q_read_demux",
     "f2q_set_strand", "f2q_read_strands",
+    "f2q_set_parts", "f2q_parts_info", "f2q_read_parts", "f2q_parts_recombinants",
 )
 
 STRANDS = ("fwd", "rev", "both")            # F2Q_STRAND_FWD / _REV / _BOTH
+PARTS_CLASSES = ("pair_perfect", "pair_imperfect", "recombinant", "part1_only", "part2_only", "neither")   # F2Q_PARTS_*
 
 ERRORS = {-1: "EINVAL", -2: "ENODEVICE", -3: "EHIP", -4: "ENOMEM", -5: "EIO", -6: "ETRUNCATED", -7: "ESTATE",
           -8: "EUNSUPPORTED", -9: "EPAIRING"}
@@ -191,6 +193,10 @@ def load(path=None):
     L.f2q_read_strands.argtypes = [vp, i64p, i64p]
     u32p = C.POINTER(C.c_uint32)
     L.f2q_umi_pairs.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), u32p, u32p, u32p]
+    L.f2q_set_parts.argtypes = [vp]
+    L.f2q_parts_info.argtypes = [vp, u32p, u32p]
+    L.f2q_read_parts.argtypes = [vp, i64p, i64p, i64p, i64p]
+    L.f2q_parts_recombinants.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), u32p, u32p, u32p]
     if path == LIB_PATH:
         _lib = L
     return L
@@ -282,10 +288,15 @@ class Counter:
     reverse complement, or as written first and as the reverse complement when that assigned no feature.  Counter mode,
     single reads, no UMIs, no sample barcodes; ``read_strands()`` returns the reads assigned on the reverse strand per
     feature and the four strand counters.
+
+    ``parts=True`` matches each part of a pair library alone (f2q_set_parts): Counter mode, exactly two fixed windows
+    (``start="a,b"``, or one window per mate with ``start2``), every feature "A:B".  ``parts_info()`` gives the sizes of
+    the two part libraries (ids in first-occurrence order over the features), ``read_parts()`` the counts per feature by
+    the part rule, the two marginals and the six read classes, ``parts_recombinants()`` the recombinant pairs.
     """
 
     def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, umi_header=None,
-                 sample_barcodes=None, barcode_mismatch=0, strand="fwd", **params):
+                 sample_barcodes=None, barcode_mismatch=0, strand="fwd", parts=False, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -305,6 +316,7 @@ class Counter:
         self.sample_barcodes = None      # (start, [barcodes]) of a demultiplexing context
         self.barcode_mismatch = 0
         self.strand = "fwd"              # the strand mode of the context (set_strand)
+        self.parts = False               # each part of a pair library matched alone (set_parts)
         try:
             self.set_strand(strand)
             if sample_barcodes is not None:
@@ -321,6 +333,8 @@ class Counter:
                 self.set_umi_header(*umi_header)
             if umi_reads:
                 self.set_umi_reads(True)
+            if parts:
+                self.set_parts()
         except BaseException:
             self.close()
             raise
@@ -423,6 +437,36 @@ class Counter:
         self._check(self._L.f2q_set_strand(self._h, STRANDS.index(strand)))
         if strand != "fwd":
             self.strand = strand
+
+    def set_parts(self):
+        """match each part of a pair library alone and count recombinants (f2q_set_parts); after set_mate2, before counting"""
+        self._check(self._L.f2q_set_parts(self._h))
+        self.parts = True
+
+    def parts_info(self):
+        """(n1, n2): the sizes of the two part libraries (f2q_parts_info)"""
+        n1, n2 = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.f2q_parts_info(self._h, C.byref(n1), C.byref(n2)))
+        return n1.value, n2.value
+
+    def read_parts(self):
+        """(parts_counts[n_features], part1_reads[n1], part2_reads[n2], classes[6]) as int64 arrays (f2q_read_parts);
+        classes in the order of PARTS_CLASSES"""
+        n1, n2 = self.parts_info()
+        i64p = C.POINTER(C.c_int64)
+        out = [np.zeros(max(n, 1), dtype=np.int64) for n in (self.n_features, n1, n2, 6)]
+        self._check(self._L.f2q_read_parts(self._h, *[a.ctypes.data_as(i64p) for a in out]))
+        return out[0][:self.n_features], out[1][:n1], out[2][:n2], out[3]
+
+    def parts_recombinants(self):
+        """(part1[n], part2[n], reads[n]) as uint32 arrays sorted by (part1, part2): every recombinant pair the set holds
+        (f2q_parts_recombinants)"""
+        u32p = C.POINTER(C.c_uint32)
+        n = C.c_uint64(0)
+        self._check(self._L.f2q_parts_recombinants(self._h, 0, C.byref(n), None, None, None))
+        out = [np.zeros(max(n.value, 1), dtype=np.uint32) for _ in range(3)]
+        self._check(self._L.f2q_parts_recombinants(self._h, max(n.value, 1), C.byref(n), *[a.ctypes.data_as(u32p) for a in out]))
+        return tuple(a[:n.value] for a in out)
 
     # -- counting: paired-end --
     @staticmethod

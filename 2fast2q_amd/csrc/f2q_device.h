@@ -1504,6 +1504,100 @@ F2Q_HD void general_read(const RunDev &run, const LibDev &lib, const EcDev &ec, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// pair libraries, each part matched alone (f2q_set_parts; the rule as Python: include/f2q.h)
+// ---------------------------------------------------------------------------------------------
+// A Counter context with exactly two fixed windows against a library whose features all read A:B.  Next to the joined
+// verdict (general_read, unchanged) every read gets one verdict per part: what a run with that window alone would give it
+// against the library of the distinct parts of that position -- the same slice, the same Phred test, the same match_key.
+// Two assigned parts (i1, i2) are looked up in the read-only pair table (i1 << 32 | i2) -> feature (host-built, at most half
+// full, ~0 = empty).  A pair the library holds counts for its feature; one it does not hold is a recombinant and goes into
+// a growing set with its reads -- the (feature, UMI) set's own code with i1 where the feature is and i2 where the codes
+// are: `rec` is a UmiDev whose slots / mask / reads / ctr are used (umi_claim_at, umi_read_add, k_umi_rehash<true>).
+#define F2Q_PARTS_PERFECT 0          // the six read classes, in f2q_read_parts' order
+#define F2Q_PARTS_IMPERFECT 1
+#define F2Q_PARTS_RECOMBINANT 2
+#define F2Q_PARTS_PART1_ONLY 3
+#define F2Q_PARTS_PART2_ONLY 4
+#define F2Q_PARTS_NEITHER 5
+#define F2Q_PARTS_CLASSES 6
+#define F2Q_PARTS_NONE 0xFFFFFFFFu
+struct PartsDev {
+    const LibDev *lib1, *lib2;             // the part libraries (device copies of their descriptors)
+    const unsigned long long *pair_keys;   // [pair_mask + 1]: (i1 << 32) | i2, ~0 = empty
+    const uint32_t *pair_feat;             // parallel: the feature of that pair
+    uint32_t pair_mask, n_features;
+    const uint32_t *ids;                   // [2 * n_features]: feature -> (i1, i2)
+    unsigned long long *counts;            // [n_features] parts_counts
+    unsigned long long *part1, *part2;     // [n1], [n2] the marginals
+    unsigned long long *classes;           // [F2Q_PARTS_CLASSES]
+    UmiDev rec;                            // the recombinant set
+};
+F2Q_HD uint32_t parts_pair_hash(unsigned long long k, uint32_t mask) { return hash32(k ^ (k >> 29), 32) & mask; }
+// the feature that pairs (i1, i2), else F2Q_PARTS_NONE
+F2Q_HD uint32_t parts_pair_find(const PartsDev &p, uint32_t i1, uint32_t i2)
+{
+    const unsigned long long k = ((unsigned long long)i1 << 32) | i2;
+    uint32_t s = parts_pair_hash(k, p.pair_mask);
+    for (uint32_t guard = 0; guard <= p.pair_mask; guard++) {
+        const unsigned long long v = gp(p.pair_keys)[s];
+        if (v == k) return gp(p.pair_feat)[s];
+        if (v == KEY_EMPTY) return F2Q_PARTS_NONE;
+        s = (s + 1u) & p.pair_mask;
+    }
+    return F2Q_PARTS_NONE;
+}
+// The verdict of one part: window [start, start + run.length) of a mate that holds n bases and qn quality bytes and begins
+// at seq[sb] / qual[qb] -- general_read's steps for a run with this one window.  1 perfect, 2 imperfect (id set),
+// 3 non-aligned, 4 quality-failed
+template <class P>
+F2Q_HD int part_verdict(const RunDev &run, const LibDev &lib, P seq, int sb, int n, P qual, int qb, int qn, int start, uint32_t &id)
+{
+    int a, b, qa, qe;
+    py_slice(n, start, start + run.length, a, b);
+    py_slice(qn, start, start + run.length, qa, qe);
+    if (qual_range_fails(qual, qb + qa, qb + qe, run.thr)) return 4;
+    KeyViewT<P> kv; kv.seq = seq; kv.nseg = 1; kv.a[0] = sb + a; kv.b[0] = sb + b; kv.len = b - a;
+    return match_key<true>(run, lib, kv, id);
+}
+// the class of a read from its two part verdicts; f = the feature of a pair the library holds (else F2Q_PARTS_NONE)
+F2Q_HD int parts_class(const PartsDev &p, int v1, uint32_t i1, int v2, uint32_t i2, uint32_t &f)
+{
+    const bool a1 = v1 == 1 || v1 == 2, a2 = v2 == 1 || v2 == 2;
+    f = F2Q_PARTS_NONE;
+    if (!a1 && !a2) return F2Q_PARTS_NEITHER;
+    if (!a2) return F2Q_PARTS_PART1_ONLY;
+    if (!a1) return F2Q_PARTS_PART2_ONLY;
+    f = parts_pair_find(p, i1, i2);
+    if (f == F2Q_PARTS_NONE) return F2Q_PARTS_RECOMBINANT;
+    return v1 == 1 && v2 == 1 ? F2Q_PARTS_PERFECT : F2Q_PARTS_IMPERFECT;
+}
+// One record: the joined verdict as ever (st[]), then the part verdicts and what the context keeps for the class.
+// cst: thread-local class sums [F2Q_PARTS_CLASSES] and, behind them, [6] = new pairs of the recombinant set
+template <class P, bool PAIRED>
+F2Q_HD void parts_read(const RunDev &run, const LibDev &lib, const EcDev &ec, const Accum &acc, const PartsDev &p,
+                       P seq, int r, P qual, int qn, unsigned long long read_index, unsigned long long st[5],
+                       unsigned long long cst[F2Q_PARTS_CLASSES + 1], int r1 = 0, int qn1 = 0)
+{
+    general_read<P, true, PAIRED>(run, lib, ec, acc, seq, r, qual, qn, read_index, st, nullptr, r1, qn1);
+    uint32_t i1 = 0, i2 = 0, f = F2Q_PARTS_NONE;
+    const int v1 = PAIRED ? part_verdict(run, *p.lib1, seq, 0, r1, qual, 0, qn1, run.start[0], i1)
+                          : part_verdict(run, *p.lib1, seq, 0, r, qual, 0, qn, run.start[0], i1);
+    const int v2 = PAIRED ? part_verdict(run, *p.lib2, seq, r1, r - r1, qual, qn1, qn - qn1, run.start[1], i2)
+                          : part_verdict(run, *p.lib2, seq, 0, r, qual, 0, qn, run.start[1], i2);
+    const int cls = parts_class(p, v1, i1, v2, i2, f);
+    cst[cls]++;
+    if (cls != F2Q_PARTS_NEITHER && cls != F2Q_PARTS_PART2_ONLY) acc_add(&p.part1[i1], 1ull);
+    if (cls != F2Q_PARTS_NEITHER && cls != F2Q_PARTS_PART1_ONLY) acc_add(&p.part2[i2], 1ull);
+    if (cls == F2Q_PARTS_PERFECT || cls == F2Q_PARTS_IMPERFECT) acc_add(&p.counts[f], 1ull);
+    else if (cls == F2Q_PARTS_RECOMBINANT) {
+        uint32_t slot = 0;
+        const uint32_t rc = umi_claim_at(p.rec, ((unsigned long long)i1 << 32) | i2, slot);
+        if (rc != 2u) umi_read_add(p.rec, slot);
+        cst[F2Q_PARTS_CLASSES] += (unsigned long long)(rc == 1u);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // fast path, fixed offset: one lane = one read of a packed tile.
 // tile planes are [word][lane]: bases 16 per u32 (2 bits, LSB first), qualities 4 per u32.
 // ---------------------------------------------------------------------------------------------

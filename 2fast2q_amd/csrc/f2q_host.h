@@ -6,6 +6,7 @@
 #include <string.h>
 #include <algorithm>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/f2q.h"
@@ -806,6 +807,57 @@ inline void demux_build(const std::string &up, uint32_t n, int32_t length, int32
     if (miss) for (uint32_t b = 0; b < n; b++)
         for (int j = 0; j < length; j++)
             for (uint32_t x = 1; x < 4u; x++) demux_put(t, codes[b] ^ (x << (2 * j)), b, false);
+}
+
+// ---------------------------------------------------------------------------------------------
+// pair libraries, each part matched alone (f2q_set_parts; the slot layout: f2q_device.h, PartsDev)
+// ---------------------------------------------------------------------------------------------
+struct PartsTable {
+    std::string seqs[2];                           // the part libraries: distinct parts of position 1 / 2, first-occurrence order
+    std::vector<uint32_t> offs[2];                 // n + 1 offsets each
+    std::vector<uint32_t> ids;                     // [2 * n_features]: feature -> (i1, i2)
+    std::vector<unsigned long long> keys;          // the pair table: a power of two, at least twice the pairs; ~0 = empty
+    std::vector<uint32_t> feat;
+    uint32_t mask = 0, pairs = 0;                  // slots - 1; distinct (i1, i2) the library holds
+    uint32_t n(int pos) const { return offs[pos].empty() ? 0u : (uint32_t)offs[pos].size() - 1u; }
+};
+// the library of f2q_set_features as two part libraries: every feature must read A:B with A and B non-empty.  F2Q_EINVAL
+// with a message that names the feature
+inline int parts_validate(const char *seqs, const uint32_t *offs, uint32_t n, PartsTable &t, std::string &err)
+{
+    t = PartsTable();
+    t.offs[0].assign(1, 0u); t.offs[1].assign(1, 0u);
+    t.ids.assign(2 * (size_t)n, 0u);
+    std::unordered_map<std::string, uint32_t> seen[2];          // part -> id, per position: the two id spaces are separate
+    auto id_of = [&](int pos, const std::string &part) {
+        const auto got = seen[pos].emplace(part, t.n(pos));
+        if (got.second) { t.seqs[pos] += part; t.offs[pos].push_back((uint32_t)t.seqs[pos].size()); }
+        return got.first->second;
+    };
+    for (uint32_t f = 0; f < n; f++) {
+        const std::string s(seqs + offs[f], offs[f + 1] - offs[f]);
+        const size_t colon = s.find(':');
+        if (colon == std::string::npos || colon == 0 || colon + 1 == s.size() || s.find(':', colon + 1) != std::string::npos) {
+            std::string shown; for (char ch : s.substr(0, 60)) shown += (ch >= 33 && ch <= 126) ? ch : '?';
+            err = "feature " + std::to_string(f) + " (" + shown + ") is not two non-empty parts joined by ':'"; return F2Q_EINVAL;
+        }
+        t.ids[2 * (size_t)f] = id_of(0, s.substr(0, colon));
+        t.ids[2 * (size_t)f + 1] = id_of(1, s.substr(colon + 1));
+    }
+    return F2Q_OK;
+}
+// the pair table of a validated library; a repeated pair stays with its first feature (the exact hit of the joined key)
+inline void parts_build(PartsTable &t)
+{
+    const size_t n = t.ids.size() / 2;
+    uint64_t slots = 2; while (slots < 2 * (uint64_t)n) slots <<= 1;
+    t.keys.assign((size_t)slots, KEY_EMPTY); t.feat.assign((size_t)slots, 0u); t.mask = (uint32_t)(slots - 1); t.pairs = 0;
+    for (size_t f = 0; f < n; f++) {
+        const unsigned long long k = ((unsigned long long)t.ids[2 * f] << 32) | t.ids[2 * f + 1];
+        uint32_t s = parts_pair_hash(k, t.mask);
+        while (t.keys[s] != KEY_EMPTY && t.keys[s] != k) s = (s + 1u) & t.mask;
+        if (t.keys[s] == KEY_EMPTY) { t.keys[s] = k; t.feat[s] = (uint32_t)f; t.pairs++; }
+    }
 }
 
 } // namespace f2q

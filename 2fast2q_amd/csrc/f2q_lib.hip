@@ -36,6 +36,7 @@ using namespace f2q;
 #include "f2q_umi_kernels.h"
 #include "f2q_demux_kernels.h"
 #include "f2q_strand_kernels.h"
+#include "f2q_parts_kernels.h"
 
 // ===============================================================================================
 // host side
@@ -144,6 +145,20 @@ struct f2q_ctx {
         std::vector<void *> allocs;      // rev_counts + extra, one allocation
         uint64_t words = 0;              // of that allocation: max(n_features, 1) + 4
     } strand;
+    // pair libraries with each part matched alone (f2q_set_parts): the two part libraries (indices of their own, as the
+    // assign library has one), the pair table, parts_counts / the marginals / the six class counters (one allocation) and
+    // the recombinant set, which outlives the pieces of a file; parts_reserve sizes it before every launch
+    struct {
+        bool on = false;
+        PartsDev dev{};
+        PartsTable tab;                  // the host's copy: part texts, feature -> ids, the pair table
+        HostIndex ix[2];
+        LibDev lib_h[2]{};
+        std::vector<void *> lib_allocs[2], fix_allocs, set_allocs;   // the part libraries / tables and counters / the set
+        uint64_t words = 0;              // of the counters' allocation: nf + n1 + n2 + 6 (each count at least 1)
+        uint64_t n_slots = 0, min_slots = (uint64_t)1 << 16;         // F2Q_PARTS_SLOTS: the first set's size (tests: growth from a small one)
+        uint64_t held_ub = 0, rehashes = 0;
+    } parts;
     bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
     int n_cu = 256;
@@ -511,6 +526,76 @@ static int strand_alloc(f2q_ctx *c)
     return F2Q_OK;
 }
 
+// ---- pair libraries, each part matched alone: tables, counters and the recombinant set ---------------------------------
+// everything given back: f2q_destroy, and a new library
+static void parts_drop(f2q_ctx *c)
+{
+    for (int k = 0; k < 2; k++) free_all(c, c->parts.lib_allocs[k]);
+    free_all(c, c->parts.fix_allocs); free_all(c, c->parts.set_allocs);
+    c->parts.dev = PartsDev{}; c->parts.words = 0; c->parts.n_slots = 0; c->parts.held_ub = 0;
+}
+
+// The part libraries, the pair table and zeroed counters for the library seqs / offs / n (f2q_set_features' arguments),
+// built next to what the context holds and swapped in at the end: a failure (F2Q_EINVAL: a feature that is not two parts,
+// named in the message; F2Q_ENOMEM) leaves the context as it was.  The set starts empty (parts_reserve allocates it).
+static int parts_install(f2q_ctx *c, const char *seqs, const uint32_t *offs, uint32_t n)
+{
+    PartsTable t; std::string err;
+    if (int rc = parts_validate(seqs, offs, n, t, err)) return fail(c, rc, "f2q_set_parts: " + err);
+    parts_build(t);
+    HostIndex ix[2]; LibDev lh[2]; LibDev *ld[2] = {nullptr, nullptr}; std::vector<void *> la[2], fix;
+    PartsDev d{};
+    unsigned long long *keys = nullptr, *words = nullptr, *ctr = nullptr; uint32_t *feat = nullptr, *ids = nullptr;
+    const uint64_t nf = std::max<uint64_t>(n, 1), n1 = std::max<uint64_t>(t.n(0), 1), n2 = std::max<uint64_t>(t.n(1), 1);
+    int rc = F2Q_OK;
+    for (int k = 0; k < 2 && !rc; k++) {
+        build_index(ix[k], t.seqs[k].data(), t.offs[k].data(), t.n(k), c->run_h.miss, 0);
+        rc = upload_index(c, ix[k], lh[k], &ld[k], la[k], nullptr);
+    }
+    if (rc || (rc = dev_upload(c, (const unsigned long long *)t.keys.data(), t.keys.size(), &keys, fix)) ||
+        (rc = dev_upload(c, t.feat.data(), t.feat.size(), &feat, fix)) || (rc = dev_upload(c, t.ids.data(), t.ids.size(), &ids, fix)) ||
+        (rc = dev_alloc(c, (size_t)(nf + n1 + n2 + F2Q_PARTS_CLASSES), &words, fix, 0)) ||
+        (rc = dev_alloc(c, (size_t)F2Q_UMI_CTR_WORDS, &ctr, fix, 0))) {
+        for (int k = 0; k < 2; k++) free_all(c, la[k]);
+        free_all(c, fix);
+        return fail(c, F2Q_ENOMEM, "no device memory for the part libraries and tables (" + std::to_string(n1) + " + " + std::to_string(n2) + " parts, " + std::to_string(nf) + " features): " + c->err);
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));                    // (the uploads read t, which moves below)
+    parts_drop(c);
+    d.lib1 = ld[0]; d.lib2 = ld[1]; d.pair_keys = keys; d.pair_feat = feat; d.pair_mask = t.mask; d.n_features = n; d.ids = ids;
+    d.counts = words; d.part1 = words + nf; d.part2 = words + nf + n1; d.classes = words + nf + n1 + n2;
+    d.rec.ctr = ctr;
+    c->parts.dev = d; c->parts.words = nf + n1 + n2 + F2Q_PARTS_CLASSES; c->parts.fix_allocs = fix;
+    for (int k = 0; k < 2; k++) { c->parts.ix[k] = std::move(ix[k]); c->parts.lib_h[k] = lh[k]; c->parts.lib_allocs[k] = la[k]; }
+    c->parts.tab = std::move(t);
+    if (c->trace) fprintf(stderr, "[f2q trace] parts: n1 %u, n2 %u, pair table %zu slots (%u pairs of %u features)\n",
+                          c->parts.tab.n(0), c->parts.tab.n(1), c->parts.tab.keys.size(), c->parts.tab.pairs, n);
+    return F2Q_OK;
+}
+
+// counters and the set cleared (f2q_reset_counts); the tables and the set's size stay
+static int parts_clear(f2q_ctx *c)
+{
+    HIPC(c, hipMemsetAsync(c->parts.dev.counts, 0, c->parts.words * sizeof(unsigned long long), c->stream));
+    HIPC(c, hipMemsetAsync(c->parts.dev.rec.ctr, 0, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), c->stream));
+    if (c->parts.dev.rec.slots) {
+        HIPC(c, hipMemsetAsync(c->parts.dev.rec.slots, 0xFF, c->parts.n_slots * sizeof(unsigned long long), c->stream));
+        HIPC(c, hipMemsetAsync(c->parts.dev.rec.reads, 0, c->parts.n_slots * sizeof(uint32_t), c->stream));
+    }
+    c->parts.held_ub = 0;
+    return F2Q_OK;
+}
+
+// the set's counters after everything on the stream; waits for the stream
+static int parts_read_ctr(f2q_ctx *c, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
+{
+    for (int i = 0; i < F2Q_UMI_CTR_WORDS; i++) ctr[i] = 0;
+    if (c->parts.dev.rec.ctr) HIPC(c, hipMemcpyAsync(ctr, c->parts.dev.rec.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "recombinant set overflow (internal sizing error)");
+    return F2Q_OK;
+}
+
 extern "C" void f2q_destroy(f2q_ctx *c)
 {
     if (!c) return;
@@ -525,6 +610,8 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     umi_drop(c);
     demux_drop(c);
     strand_drop(c);
+    if (c->trace && c->parts.on) fprintf(stderr, "[f2q trace] recombinant set: %llu slots, %llu rehashes\n", (unsigned long long)c->parts.n_slots, (unsigned long long)c->parts.rehashes);
+    parts_drop(c);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
@@ -560,6 +647,10 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "Extract+Count mode takes no feature library (fast2q.py:1701)");
     HIPC(c, hipSetDevice(c->device));
     for (uint32_t i = 0; i < n; i++) if (offs[i + 1] < offs[i]) return fail(c, F2Q_EINVAL, "offsets must be non-decreasing");
+    if (c->parts.on) {                                // a parts context takes A:B libraries only: refused before anything changes
+        PartsTable t; std::string err;
+        if (int rc = parts_validate(seqs ? seqs : "", offs, n, t, err)) return fail(c, rc, "f2q_set_features on a parts context (f2q_set_parts): " + err);
+    }
     c->plan = make_plan(c->run_h);                   // the library decides below whether the packed paths apply
     c->plan.rc2 = c->rc2;
     if (c->force_general) { c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false; }
@@ -581,6 +672,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (c->umi.on) umi_drop(c);                       // a new library starts a new set
     if (c->demux.on) { demux_drop(c); if ((rc = demux_alloc(c))) return rc; }      // ... and a new matrix: a row has a word per feature
     if (c->strand.mode) { strand_drop(c); if ((rc = strand_alloc(c))) return rc; }  // ... and reverse-strand counts that start afresh
+    if (c->parts.on && (rc = parts_install(c, seqs ? seqs : "", offs, n))) return rc;   // ... and part libraries, a pair table and a set of its own
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
     // symbol of any feature), every other odd symbol still sends the read to the byte-exact routine
@@ -604,6 +696,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
     if (c->umi.on && c->umi.dev.umis) if (int rc = umi_clear(c)) return rc;
     if (c->demux.on && c->demux.dev.matrix) if (int rc = demux_clear(c)) return rc;
     if (c->strand.mode && c->strand.dev.rev_counts) HIPC(c, hipMemsetAsync(c->strand.dev.rev_counts, 0, c->strand.words * sizeof(unsigned long long), c->stream));
+    if (c->parts.on && c->parts.dev.counts) if (int rc = parts_clear(c)) return rc;
     c->reads_seen = 0;
     c->ec_gen++;
     // no host synchronisation: the clear is ordered on the context's stream like every launch and read-back after it
@@ -638,6 +731,7 @@ extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 
 // ---- distinct UMIs per feature: the ABI ---------------------------------------------------------------------------
 static const char *const STRAND_NO_UMI = "a context with a strand mode (f2q_set_strand: rev / both) takes no UMIs: the two are not combined";
+static const char *const PARTS_NO_UMI = "a parts context (f2q_set_parts) takes no UMIs: the two are not combined";
 static const char *const DEMUX_NO_UMI = "a demultiplexing context (f2q_set_sample_barcodes) takes no UMIs: the two are not combined";
 // what f2q_set_umi and f2q_set_umi_paired share once the window is in umi.dev
 static void umi_enable(f2q_ctx *c)
@@ -656,6 +750,7 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) takes f2q_set_umi_paired");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
+    if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
     if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
         return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
@@ -673,6 +768,7 @@ extern "C" int f2q_set_umi_header(f2q_ctx *c, int32_t sep, int32_t length)
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_header takes a Counter context: Extract+Count assigns no read to a feature");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
+    if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_header comes once, in place of f2q_set_umi / f2q_set_umi_paired and before counting");
     const bool alnum = (sep >= '0' && sep <= '9') || (sep >= 'A' && sep <= 'Z') || (sep >= 'a' && sep <= 'z');
     if (sep < 33 || sep > 126 || alnum || sep == '+' || length < 1 || length > F2Q_UMI_MAXLEN)
@@ -693,6 +789,7 @@ extern "C" int f2q_set_umi_paired(f2q_ctx *c, int32_t start1, int32_t length1, i
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a Counter context: Extract+Count assigns no pair to a feature");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
+    if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (!c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a paired context: call f2q_set_mate2 first (single reads: f2q_set_umi)");
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired comes once, after f2q_set_mate2 and before counting");
     if (start1 < 0 || start1 > 0x3FFFFFFF || start2 < 0 || start2 > 0x3FFFFFFF || length1 < 0 || length2 < 0 ||
@@ -740,6 +837,7 @@ extern "C" int f2q_set_sample_barcodes(f2q_ctx *c, const char *seqs, uint32_t n,
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes takes single reads: a paired context (f2q_set_mate2) is not demultiplexed");
     if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a UMI context: sample barcodes and UMIs are not combined");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
+    if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a parts context (f2q_set_parts): the two are not combined");
     if (c->demux.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes comes once, after f2q_create and before counting");
     std::string up, err;
     if (int rc = demux_validate(seqs, n, length, start, miss, up, err)) return fail(c, rc, err);
@@ -796,6 +894,7 @@ extern "C" int f2q_set_strand(f2q_ctx *c, int32_t mode)
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) takes single reads: a paired context (f2q_set_mate2) has its own orientation (rc2)");
     if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a UMI context: a strand mode and UMIs are not combined");
     if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
+    if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a parts context (f2q_set_parts): the two are not combined");
     if (c->strand.mode || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) comes once, after f2q_create and before counting");
     HIPC(c, hipSetDevice(c->device));
     c->strand.mode = mode; c->strand.dev = StrandDev{}; c->strand.dev.mode = mode;
@@ -822,6 +921,96 @@ extern "C" int f2q_read_strands(f2q_ctx *c, int64_t *rev_counts, int64_t extra[4
     HIPC(c, hipStreamSynchronize(c->stream));
     if (rev_counts) for (uint64_t f = 0; f < nf; f++) rev_counts[f] = h.empty() ? 0 : (int64_t)h[f];
     if (extra) for (int k = 0; k < 4; k++) extra[k] = h.empty() ? 0 : (int64_t)h[c->strand.words - 4 + k];
+    return F2Q_OK;
+}
+
+// ---- pair libraries, each part matched alone: the ABI (include/f2q.h) -------------------------------------------------
+extern "C" int f2q_set_parts(f2q_ctx *c)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_parts takes a Counter context: Extract+Count assigns no read to a feature");
+    if (!c->run_h.fixed) return fail(c, F2Q_ESTATE, "f2q_set_parts takes fixed windows (--st): anchored runs (--us/--ds) are not implemented");
+    if (c->n_mate1 ? (c->n_mate1 != 1 || c->run_h.n_iter != 2) : c->run_h.n_iter != 2)
+        return fail(c, F2Q_ESTATE, c->n_mate1 ? "f2q_set_parts on a paired context takes one window per mate, not " + std::to_string(c->n_mate1) + " + " + std::to_string(c->run_h.n_iter - c->n_mate1)
+                                              : "f2q_set_parts takes exactly two windows (--st a,b), not " + std::to_string(c->run_h.n_iter));
+    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on a UMI context: part verdicts and UMIs are not combined");
+    if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
+    if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_parts on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
+    if (c->parts.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_parts comes once, after f2q_create (and f2q_set_mate2) and before counting");
+    HIPC(c, hipSetDevice(c->device));
+    { const char *e = getenv("F2Q_PARTS_SLOTS"); if (e && atol(e) > 0) { c->parts.min_slots = 2; while (c->parts.min_slots < (uint64_t)atol(e) && c->parts.min_slots < (1ull << 32)) c->parts.min_slots <<= 1; } }
+    if (c->have_lib) if (int rc = parts_install(c, (const char *)c->ix.feat_bytes.data(), c->ix.feat_off.data(), c->ix.n_features)) return rc;   // (nothing else was touched: as if the call had not been made)
+    c->parts.on = true;
+    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
+    c->force_general = true;
+    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
+    c->plan.inband_n = false; c->plan.n_only = false;
+    return F2Q_OK;
+}
+
+extern "C" int f2q_parts_info(f2q_ctx *c, uint32_t *n1, uint32_t *n2)
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->parts.on) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
+    if (n1) *n1 = c->parts.tab.n(0);
+    if (n2) *n2 = c->parts.tab.n(1);
+    return F2Q_OK;
+}
+
+extern "C" int f2q_read_parts(f2q_ctx *c, int64_t *parts_counts, int64_t *part1_reads, int64_t *part2_reads, int64_t classes[6])
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->parts.on) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
+    HIPC(c, hipSetDevice(c->device));
+    const PartsDev &d = c->parts.dev;
+    std::vector<unsigned long long> h;
+    if (d.counts) {                                              // (no library yet: nothing can have been counted)
+        try { h.resize(c->parts.words); } catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy the part counts"); }
+        HIPC(c, hipMemcpyAsync(h.data(), d.counts, c->parts.words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    }
+    unsigned long long ctr[F2Q_UMI_CTR_WORDS];
+    if (int rc = parts_read_ctr(c, ctr)) return rc;
+    if (h.empty()) { if (classes) for (int k = 0; k < F2Q_PARTS_CLASSES; k++) classes[k] = 0; return F2Q_OK; }
+    const uint64_t nf = c->lib_h.n_features, n1 = c->parts.tab.n(0), n2 = c->parts.tab.n(1);
+    if (parts_counts) for (uint64_t i = 0; i < nf; i++) parts_counts[i] = (int64_t)h[i];
+    if (part1_reads) for (uint64_t i = 0; i < n1; i++) part1_reads[i] = (int64_t)h[(size_t)(d.part1 - d.counts) + i];
+    if (part2_reads) for (uint64_t i = 0; i < n2; i++) part2_reads[i] = (int64_t)h[(size_t)(d.part2 - d.counts) + i];
+    if (classes) for (int k = 0; k < F2Q_PARTS_CLASSES; k++) classes[k] = (int64_t)h[(size_t)(d.classes - d.counts) + k];
+    return F2Q_OK;
+}
+
+// every recombinant pair with its reads, sorted by (i1, i2): the set copied and filtered on the host (no hot path)
+extern "C" int f2q_parts_recombinants(f2q_ctx *c, uint64_t cap, uint64_t *n, uint32_t *part1, uint32_t *part2, uint32_t *reads)
+{
+    if (!c || !n) return F2Q_EINVAL;
+    if (!c->parts.on) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
+    HIPC(c, hipSetDevice(c->device));
+    const PartsDev &d = c->parts.dev;
+    unsigned long long ctr[F2Q_UMI_CTR_WORDS], recombinant = 0;
+    if (d.classes) HIPC(c, hipMemcpyAsync(&recombinant, d.classes + F2Q_PARTS_RECOMBINANT, sizeof recombinant, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = parts_read_ctr(c, ctr)) return rc;
+    if (recombinant >= (1ull << 32))
+        return fail(c, F2Q_EUNSUPPORTED, "f2q_parts_recombinants: 2^32 or more recombinant reads -- a pair's 32-bit count may have wrapped");
+    *n = ctr[F2Q_UMI_HELD];
+    if (!part1 && !part2 && !reads) return F2Q_OK;
+    if (cap < *n) return fail(c, F2Q_EINVAL, "f2q_parts_recombinants: room for " + std::to_string(cap) + " pairs, the set holds " + std::to_string(*n));
+    if (!*n || !d.rec.slots) return F2Q_OK;
+    std::vector<unsigned long long> words; std::vector<uint32_t> cnt;
+    std::vector<std::pair<unsigned long long, uint32_t>> held;
+    try { words.resize(c->parts.n_slots); cnt.resize(c->parts.n_slots); held.reserve((size_t)*n); }
+    catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy a recombinant set of " + std::to_string(c->parts.n_slots) + " slots"); }
+    HIPC(c, hipMemcpyAsync(words.data(), d.rec.slots, c->parts.n_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(cnt.data(), d.rec.reads, c->parts.n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    uint64_t occupied = 0;
+    for (uint64_t i = 0; i < c->parts.n_slots; i++) if (words[i] != KEY_EMPTY && occupied++ < *n) held.emplace_back(words[i], cnt[i]);      // (never past the reserve)
+    if (occupied != *n) return fail(c, F2Q_EHIP, "the recombinant set holds " + std::to_string(occupied) + " pairs, its counter says " + std::to_string(*n));
+    std::sort(held.begin(), held.end());                         // the word is (i1 << 32) | i2
+    for (size_t i = 0; i < held.size(); i++) {
+        if (part1) part1[i] = (uint32_t)(held[i].first >> 32);
+        if (part2) part2[i] = (uint32_t)held[i].first;
+        if (reads) reads[i] = held[i].second;
+    }
     return F2Q_OK;
 }
 
@@ -1306,6 +1495,45 @@ static int umi_reserve(f2q_ctx *c, uint64_t n)
     return F2Q_OK;
 }
 
+// umi_reserve for the recombinant set of a parts context (f2q_set_parts): before a launch over n records the set is made
+// large enough to be at most half full afterwards even if every record brings a new pair; the pairs held are read from the
+// device only when the host's bound says the set might be too small; a set that is grows to hold twice what it must
+// (amortised doubling); the rehash (k_umi_rehash<true>) carries the reads; the new set is allocated before the old one is
+// given back, so a failed allocation leaves the context as it was.
+static int parts_reserve(f2q_ctx *c, uint64_t n)
+{
+    int rc;
+    UmiDev &u = c->parts.dev.rec;
+    if (u.slots && 2 * (c->parts.held_ub + n) <= c->parts.n_slots) { c->parts.held_ub += n; return F2Q_OK; }
+    unsigned long long ctr[F2Q_UMI_CTR_WORDS] = {0, 0, 0, 0};
+    if (u.slots) {
+        if ((rc = parts_read_ctr(c, ctr))) return rc;
+        if (2 * (ctr[F2Q_UMI_HELD] + n) <= c->parts.n_slots) { c->parts.held_ub = ctr[F2Q_UMI_HELD] + n; return F2Q_OK; }
+    }
+    const uint64_t held = ctr[F2Q_UMI_HELD];
+    uint64_t slots = std::max<uint64_t>(c->parts.min_slots, 2);
+    while (slots < 2 * (held + n) || slots < 4 * held) slots <<= 1;
+    if (slots > (1ull << 32)) return fail(c, F2Q_ENOMEM, "the recombinant set would exceed 2^32 slots");
+    UmiDev fresh = u; std::vector<void *> owner;
+    if ((rc = dev_alloc(c, (size_t)slots, &fresh.slots, owner, 0xFF)) || (rc = dev_alloc(c, (size_t)slots, &fresh.reads, owner, 0))) {
+        free_all(c, owner);
+        return fail(c, F2Q_ENOMEM, "no device memory for a recombinant set of " + std::to_string(slots) + " slots: " + c->err);
+    }
+    fresh.mask = (uint32_t)(slots - 1);
+    if (u.slots && held) {
+        hipLaunchKernelGGL(k_umi_rehash<true>, dim3((unsigned)((c->parts.n_slots + 255) / 256)), dim3(256), 0, c->stream, u, fresh);
+        HIPC(c, hipGetLastError());
+        c->parts.rehashes++;
+        if (c->trace) fprintf(stderr, "[f2q trace] recombinant set rehash %llu: %llu pairs, %llu -> %llu slots\n", (unsigned long long)c->parts.rehashes,
+                              (unsigned long long)held, (unsigned long long)c->parts.n_slots, (unsigned long long)slots);
+    }
+    free_all(c, c->parts.set_allocs);                            // (waits for the stream)
+    c->parts.set_allocs = owner;
+    u.slots = fresh.slots; u.reads = fresh.reads; u.mask = fresh.mask; c->parts.n_slots = slots;
+    c->parts.held_ub = held + n;
+    return F2Q_OK;
+}
+
 // the linking launch (defaults and alternatives: DESIGN.md): threads per workgroup (F2Q_UMI_LINK_WG: whole waves, at most
 // F2Q_UMI_LINK_THREADS), workgroups per CU at most (F2Q_UMI_LINK_GRID: 1 .. 4096), the lane-per-slot layout instead of the
 // wave-cooperative one (F2Q_UMI_LINK=lane: A/B runs); anything else is the default.  g256: the grid of the slot-stride kernels
@@ -1535,6 +1763,16 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
         EC_POINT(c, c->strand.mode == F2Q_STRAND_BOTH ? "k_count_strand<both>" : "k_count_strand<rev>");
         return F2Q_OK;
     }
+    if (c->parts.on) {                                           // the same road with the part verdicts, the tables and the recombinant set (f2q_set_parts)
+        if (!c->parts.dev.counts) return fail(c, F2Q_ESTATE, "a parts context without its tables: f2q_set_features failed");
+        if ((rc = parts_reserve(c, rb.n))) return rc;
+        if (rb.len1) hipLaunchKernelGGL(k_count_parts<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->parts.dev);
+        else hipLaunchKernelGGL(k_count_parts<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->parts.dev);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, rb.len1 ? "k_count_parts<paired>" : "k_count_parts");
+        return F2Q_OK;
+    }
     if (rb.len1) hipLaunchKernelGGL(k_count_general<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     else hipLaunchKernelGGL(k_count_general<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
     HIPC(c, hipGetLastError());
@@ -1676,6 +1914,8 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
     if (c->umi.on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
     if (c->strand.mode && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_strand: a context with a strand mode counts single raw records only");
     if (c->demux.on && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_sample_barcodes: a demultiplexing context counts single raw records only");
+    if (c->parts.on && (b->pb.n_tiles || (b->rb.n && (b->rb.len1 != nullptr) != (c->n_mate1 != 0))))
+        return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_parts: a parts context counts raw records only");
     if (c->umi.hdr_sep && b->rb.n && !b->rb.hdr_umi) return fail(c, F2Q_ESTATE, "the block was made before f2q_set_umi_header (or without headers): its records carry no header UMI");
     c->counted = true;
     Accum acc{c->acc_d, c->acc_d + (c->acc_n - 5), nullptr, nullptr, nullptr, nullptr};
@@ -2201,6 +2441,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
     if (c->umi.on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only: f2q_set_mate2 comes first, then f2q_set_umi_paired");
     if (c->demux.on) return fail(c, F2Q_ESTATE, "a demultiplexing context (f2q_set_sample_barcodes) counts single reads only");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts single reads only");
+    if (c->parts.on) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) keeps its windows: f2q_set_mate2 comes first, then f2q_set_parts");
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
     for (int i = 0; i < n_start2; i++) if (start2[i] < 0) return fail(c, F2Q_EINVAL, "a mate-2 window starts before the mate");
@@ -2879,6 +3120,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
     if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
     if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
+    if (c->parts.on && world > 1) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) counts whole files: the tables and sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     size_t CH = file_chunk_bytes((size_t)256 << 20);
     TextSource src;
@@ -3165,6 +3407,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
     if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
     if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
+    if (c->parts.on && world > 1) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) counts whole files: the tables and sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }

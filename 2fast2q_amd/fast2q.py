@@ -167,7 +167,29 @@ def _counter_kwargs(param):
         kwargs['barcode_mismatch'] = sb['miss']
     if param.get('strand'):                         # --strand rev / both (f2q_set_strand); part of the key too
         kwargs['strand'] = param['strand']
+    if param.get('parts'):                          # --parts: each part of a pair library matched alone (f2q_set_parts); part of the key too
+        kwargs['parts'] = True
     return kwargs
+
+
+def part_libraries(seqs):
+    """(parts of position 1, parts of position 2) of a pair library, each in first-occurrence order over the features: the
+    ids f2q_set_parts gives them (include/f2q.h)"""
+    firsts, seconds = {}, {}
+    for seq in seqs:
+        a, _, b = seq.partition(":")
+        firsts.setdefault(a, len(firsts))
+        seconds.setdefault(b, len(seconds))
+    return list(firsts), list(seconds)
+
+
+def check_parts_library(features):
+    """--parts: every feature is two non-empty parts joined by ':'; a sentence that names the first row that is not, else None"""
+    for seq, feature in features.items():
+        parts = seq.split(":")
+        if len(parts) != 2 or not parts[0] or not parts[1]:
+            return f"the feature {feature.name} ({seq}) is not two non-empty parts joined by ':'"
+    return None
 
 
 # ---- contexts are kept between samples ----------------------------------------------------------------------------
@@ -290,7 +312,9 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         raise RuntimeError("--sb: the demultiplexed counts are not merged across several ranks; run one process")
     if param.get('strand') and sharding.world().size > 1:
         raise RuntimeError("--strand: the reverse-strand counts are not merged across several ranks; run one process")
-    ctx = _context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
+    if param.get('parts') and sharding.world().size > 1:
+        raise RuntimeError("--parts: the part tables and recombinant sets are not merged across several ranks; run one process")
+    ctx =_context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
         if param.get('paired'):
@@ -333,6 +357,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             param.setdefault('demux_counted', {})[raw] = ctx.read_demux()
         if param.get('strand'):                     # --strand rev / both: reads assigned on the reverse strand, the strand counters (f2q_read_strands)
             param.setdefault('strand_counted', {})[raw] = ctx.read_strands()
+        if param.get('parts'):                      # --parts: counts by the part rule, the marginals, the six classes (f2q_read_parts) and the recombinant pairs
+            param.setdefault('parts_counted', {})[raw] = (ctx.read_parts(), ctx.parts_recombinants())
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -439,6 +465,18 @@ def aligner(i, raw, features, param, reads_stats):
         columns = [SampleResult(f"{sample.name}:fwd", value, unit, _sample_rows((name, fwd) for name, fwd, _ in split), {}),
                    SampleResult(f"{sample.name}:rev", value, unit, _sample_rows((name, rev) for name, _, rev in split), {})]
         param.setdefault("strand_samples", {})[sample.name] = (columns, [int(n) for n in extra])
+    if raw in param.get('parts_counted', {}):        # --parts: the same rows holding parts_counts; the recombinant pairs by their texts; the classes
+        (parts_counts, part1, part2, classes), (i1, i2, reads) = param['parts_counted'].pop(raw)
+        names = [f.name for f in features.values()]
+        firsts, seconds = part_libraries(list(features))
+        recombinants = {(firsts[a], seconds[b]): int(n) for a, b, n in zip(i1, i2, reads)}
+        param.setdefault("parts_samples", {})[sample.name] = (
+            SampleResult(sample.name, value, unit, _sample_rows(zip(names, (int(n) for n in parts_counts))), dict(local)),
+            recombinants, dict(zip(binding.PARTS_CLASSES, (int(n) for n in classes))))
+        if not param.get("delete", True) and sharding.world().rank == 0:
+            os.makedirs(param["directory"], exist_ok=True)
+            csv_writer(os.path.join(param["directory"], sample.name + "_parts_marginals.csv"),
+                       [["#position", "part", "reads"]] + [[1, part, int(n)] for part, n in zip(firsts, part1)] + [[2, part, int(n)] for part, n in zip(seconds, part2)])
     if not param['Progress bar']:
         colourful_errors("INFO", f"Sample {sample.name} was processed in {value} {unit}")
     param.setdefault("samples", {})[sample.name] = sample     # a later file of the same name replaces the earlier one,
@@ -515,6 +553,9 @@ def initializer(cmd):
     if param.get('strand'):
         print(f" Reads are counted on {'the reverse strand' if param['strand'] == 'rev' else 'the forward strand, else on the reverse strand'}")
         print(f" {strand_header(param)[1:]}")
+    if param.get('parts'):
+        print(" Each of the two feature parts is also matched on its own; recombinant reads are counted per pair of parts")
+        print(f" {PARTS_HEADER[1:]}")
     if param.get('umi_mismatch'):
         print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
     if param.get('umi_rule') == 'directional':
@@ -579,6 +620,10 @@ def strand_header(param):
     return f"#Strand: {param['strand']}"
 
 
+# the line a --parts run adds to the parameter print-out and to the head of <name>_stats.csv
+PARTS_HEADER = "#Parts matched independently: 2"
+
+
 def parse_umih(text):
     """(separator, L) of a --umih value SEP,L, split at the last comma; a string that says what is wrong with it otherwise"""
     sep, comma, length = str(text).rpartition(",")
@@ -638,6 +683,7 @@ def input_parser(argv=None):
     ap.add_argument("--sbs", help="With --sb: the start position of the sample barcode within the read (default = 0)")
     ap.add_argument("--sbm", help="With --sb: mismatches allowed in the sample barcode, 0 or 1 (default = 0)")
     ap.add_argument("--strand", help="fwd (default), rev or both: the orientation the reads are counted in. rev: every read is reverse-complemented first; both: a read that is assigned no feature as sequenced is tried reverse-complemented (<name>_strand.csv). Counter mode, single reads, one process")
+    ap.add_argument("--parts", nargs='?', const=True, help="Pair libraries (features A:B over exactly two windows: --st a,b, or --pe --st a --st2 b): each part is also matched on its own with --m mismatches per part; reads whose two parts the library does not pair are counted as recombinants (<name>_parts.csv, <name>_recombinants.csv). Counter mode, one process")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
     if args.v is not None:
@@ -786,6 +832,22 @@ def input_parser(argv=None):
                 colourful_errors("FATAL", f"--strand {args.strand} cannot be combined with {' / '.join(others)}: the reverse strand is read from single reads without UMIs or sample barcodes.")
                 sys.exit(2)
             p['strand'] = args.strand
+    if args.parts is not None:
+        if p['Running Mode'] != "C":
+            colourful_errors("FATAL", "--parts only has a meaning in Counter mode: it cannot be combined with --mo EC.")
+            sys.exit(2)
+        others = [f for f, v in (("--us", args.us), ("--ds", args.ds), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2), ("--umih", args.umih), ("--sb", args.sb)) if v is not None]
+        if args.strand in ("rev", "both"):
+            others.append(f"--strand {args.strand}")
+        if others:
+            colourful_errors("FATAL", f"--parts cannot be combined with {' / '.join(others)}: the parts are matched at fixed positions, without UMIs, sample barcodes or a strand mode.")
+            sys.exit(2)
+        windows = [len(str(p['start']).split(","))] + ([len(str(args.st2).split(","))] if args.pe is not None else [])
+        if windows not in ([2], [1, 1]):
+            colourful_errors("FATAL", f"--parts needs exactly two windows: --st a,b for single reads, or one window per mate with --pe (--st a --st2 b); "
+                                      f"--st {p['start']}" + (f" --st2 {args.st2}" if args.pe is not None else "") + f" names {' + '.join(str(n) for n in windows)}.")
+            sys.exit(2)
+        p['parts'] = True
     if args.assign is not None:
         if p['Running Mode'] != "EC":
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
@@ -824,6 +886,9 @@ def file_sizer_split(param):
         sys.exit(2)
     if param.get('strand') and sharding.world().size > 1:
         colourful_errors("FATAL", "--strand: the reverse-strand counts are not merged across several ranks; run one process.")
+        sys.exit(2)
+    if param.get('parts') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--parts: the part tables and recombinant sets are not merged across several ranks; run one process.")
         sys.exit(2)
     if param.get('paired'):                                      # one sample per pair, named after its R1 file
         if sharding.world().size > 1:
@@ -936,6 +1001,8 @@ def run_headers(param):
         lines.append(sample_barcodes_header(param))
     if param.get('strand'):
         lines.append(strand_header(param))
+    if param.get('parts'):
+        lines.append(PARTS_HEADER)
     return lines
 
 
@@ -988,6 +1055,15 @@ def compiling(param):
         shead, stable = _table_of([column for s in ordered for column in param["strand_samples"].get(s.name, ((), ()))[0]])
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_strand.csv"),
                    [shead] + [[feature] + counts for feature, counts in stable.items()])
+    if param.get("parts_samples"):                   # --parts: <name>.csv's layout and row order holding parts_counts; the recombinant pairs of any sample
+        parts = param["parts_samples"]
+        _, phead, ptable = compile_table({name: rec[0] for name, rec in parts.items()})
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_parts.csv"),
+                   [phead] + [[feature] + counts for feature, counts in ptable.items()])
+        columns = [parts[s.name][1] for s in ordered if s.name in parts]
+        pairs = sorted({pair for column in columns for pair in column}, key=lambda pair: (-sum(column.get(pair, 0) for column in columns), pair))
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_recombinants.csv"),
+                   [["#Part1", "Part2"] + [s.name for s in ordered if s.name in parts]] + [[a, b] + [column.get((a, b), 0) for column in columns] for a, b in pairs])
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -1028,6 +1104,12 @@ STRAND_STATS_HEAD = ["#Sample name (strands)", "Number of reads assigned on the 
                      "Number of reads assigned on the reverse strand with mismatches", "Number of reads whose reverse strand was examined"]
 
 
+PARTS_STATS_HEAD = ["#Sample name (parts)", "Number of reads whose two parts are a library pair, both without mismatches",
+                    "Number of reads whose two parts are a library pair, at least one with mismatches", "Number of recombinant reads (two assigned parts the library does not pair)",
+                    "Number of distinct recombinant pairs", "Number of reads with part 1 assigned only", "Number of reads with part 2 assigned only",
+                    "Number of reads with no part assigned"]
+
+
 def run_stats(headers, param, compiled, head, ordered):
     """<name>_stats.csv -- the run's '#key: value' lines, the column names, one row of numbers per sample (:1386-1412,
     taken from the counters themselves) -- plus the four overview plots (:1414-1527)"""
@@ -1049,6 +1131,11 @@ def run_stats(headers, param, compiled, head, ordered):
     strands = param.get("strand_samples", {})
     if strands:                                                  # --strand rev / both: the four strand counters per file
         global_stat += [STRAND_STATS_HEAD] + [[s.name] + strands[s.name][1] for s in ordered if s.name in strands]
+    parts = param.get("parts_samples", {})
+    if parts:                                                    # --parts: the six read classes per file, the distinct recombinant pairs next to their reads
+        global_stat += [PARTS_STATS_HEAD] + [
+            [s.name, c["pair_perfect"], c["pair_imperfect"], c["recombinant"], len(parts[s.name][1]), c["part1_only"], c["part2_only"], c["neither"]]
+            for s in ordered if s.name in parts for c in [parts[s.name][2]]]
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib
@@ -1127,6 +1214,11 @@ def main(argv=None):
     features = {}
     if param['Running Mode'] == 'C':
         features = features_loader(param["feature"])
+        if param.get('parts'):                       # refused before the output directory exists
+            wrong = check_parts_library(features)
+            if wrong:
+                colourful_errors("FATAL", f"--parts takes a library of pairs, --g {param['feature']}: {wrong}.")
+                sys.exit(2)
     elif param.get('assign'):
         param['assign_features'] = features_loader(param["feature"])
     aligner_mp_dispenser(features, param)

@@ -550,6 +550,78 @@ int f2q_read_demux(f2q_ctx *ctx, int64_t *matrix /* (n+1) * n_features */, int64
 int f2q_set_strand(f2q_ctx *ctx, int32_t mode);
 int f2q_read_strands(f2q_ctx *ctx, int64_t *rev_counts /* n_features */, int64_t extra[4]);
 
+/* ---- pair libraries: each part matched alone, recombinants counted --------------------------------
+ * Dual-guide and barcode x guide pools are A:B features over two windows.  The reference joins the two windows with ':'
+ * and matches the JOINED key with --m mismatches in total (fast2q.py:362-380); a perfectly good A next to a perfectly good
+ * B that the library does not pair -- a recombinant, from template switching in PCR or lentiviral packaging -- is then
+ * "non-aligned", next to junk.  f2q_set_parts makes a Counter context with exactly two fixed windows give every read, next
+ * to the reference's verdict, one verdict per part, and keep new tables from them.  Counts, the five counters and every
+ * other output stay what the same context gives without the call.
+ *
+ * The rule.  features = the library of f2q_set_features, every one "A:B" with A and B non-empty.
+ *
+ *     def part_libraries(features):                    # ids in first-occurrence order; the two id spaces are separate
+ *         lib1, lib2 = [], []                          # (a sequence may be a part 1 and a part 2)
+ *         for f in features:
+ *             a, b = f.split(":")
+ *             if a not in lib1: lib1.append(a)
+ *             if b not in lib2: lib2.append(b)
+ *         return lib1, lib2
+ *
+ *     def part_verdicts(read, run):                    # -> ((kind1, i1), (kind2, i2))
+ *         # verdict_i = what a Counter run with the single window --st s_i --l L, the run's --ph and --m, gives this read
+ *         # against part library i: PERFECT (id), IMPERFECT (id: the unique nearest within --m), NON_ALIGNED or
+ *         # QUALITY_FAILED (fast2q.py:349-380 with one window).  Single-end: both windows of the one read.  Paired: window 1
+ *         # on mate 1, window 2 on mate 2 as the run takes it (reverse-complemented, its quality reversed, under revcomp).
+ *         # A clipped window, lower case, 'N' and the unique-nearest rule all follow; --m counts mismatches PER PART here.
+ *         return counter_verdict(lib1, read, s_1), counter_verdict(lib2, read, s_2)
+ *
+ *     def parts_class(v1, v2, features):               # -> (class, feature or None)
+ *         a1, a2 = v1.kind in (PERFECT, IMPERFECT), v2.kind in (PERFECT, IMPERFECT)
+ *         if not a1 and not a2: return NEITHER, None
+ *         if not a2: return PART1_ONLY, None
+ *         if not a1: return PART2_ONLY, None
+ *         key = lib1[v1.id] + ":" + lib2[v2.id]
+ *         if key not in features: return RECOMBINANT, None
+ *         f = features.index(key)                      # a repeated feature: the first, the exact hit of the joined key
+ *         return (PAIR_PERFECT if v1.kind == v2.kind == PERFECT else PAIR_IMPERFECT), f
+ *
+ * Per read: PAIR_* adds 1 to parts_counts[f]; RECOMBINANT adds 1 to the reads of (i1, i2) in a growing set; every assigned
+ * part adds 1 to its marginal (part1_reads[i1], part2_reads[i2]) whatever the other part did.  At --m 0 parts_counts equals
+ * counts.  Invariants: sum(classes) == stats[F2Q_READS]; sum(parts_counts) == classes[PAIR_PERFECT] + classes[PAIR_IMPERFECT];
+ * the reads of the set add up to classes[RECOMBINANT]; sum(part1_reads) == pairs + recombinant + part1_only (part 2 alike).
+ *
+ * f2q_set_parts comes once, after f2q_create (and f2q_set_mate2) and before counting, before or after f2q_set_features; a
+ * new library rebuilds the part libraries and the pair table and starts new tables.  F2Q_ESTATE, the message naming the
+ * cause: an Extract+Count context, --us/--ds, a window count other than two (paired: other than one per mate), a UMI
+ * context of any kind, a demultiplexing context, a non-zero strand mode, called twice or after a counting call; afterwards
+ * f2q_set_umi, f2q_set_umi_paired, f2q_set_umi_header, f2q_set_sample_barcodes, f2q_set_strand with a non-zero mode,
+ * f2q_set_mate2 and the sharded calls with world > 1 are F2Q_ESTATE in turn.  F2Q_EINVAL, from this call or from
+ * f2q_set_features on such a context, naming the feature: a feature that is not two non-empty parts.  F2Q_ENOMEM leaves the
+ * context as it was.  From then on every read takes the raw-record road (k_count_parts) through f2q_count_block,
+ * f2q_block_from_fastq + f2q_count_resident / f2q_count_resident_queued, f2q_count_text, f2q_count_file (plain, gzip, BGZF,
+ * F2Q_DEVICE_INFLATE=1, F2Q_HOST_PACK=1) and the three paired calls.  The recombinant set lives across the pieces of a file
+ * and across counting calls and grows through the context's device-memory cache; F2Q_PARTS_SLOTS=n sets its first size;
+ * F2Q_TRACE=1 names every rehash and prints n1, n2 and the pair table's slots once.
+ *
+ * f2q_parts_info: the sizes of the two part libraries.  f2q_read_parts (synchronises as f2q_read_counts does; any pointer
+ * may be NULL): parts_counts[n_features], part1_reads[n1], part2_reads[n2], classes[6] in the order of F2Q_PARTS_*.
+ * f2q_parts_recombinants: every pair of the set with its reads, sorted by (i1, i2) -- a function of the set, not of read
+ * order.  *n = pairs held; with all three arrays NULL that is all; F2Q_EINVAL when cap < n.  A pair's reads are 32 bits:
+ * F2Q_EUNSUPPORTED once the context has counted 2^32 recombinant reads.  f2q_reset_counts clears all of it.
+ * Not implemented: three or more parts, anchored runs, UMIs / sample barcodes / a strand mode on a parts context, several
+ * ranks (everything is additive), the packed-tile kernels. */
+#define F2Q_PARTS_PAIR_PERFECT 0
+#define F2Q_PARTS_PAIR_IMPERFECT 1
+#define F2Q_PARTS_RECOMBINANT 2
+#define F2Q_PARTS_PART1_ONLY 3
+#define F2Q_PARTS_PART2_ONLY 4
+#define F2Q_PARTS_NEITHER 5
+int f2q_set_parts(f2q_ctx *ctx);
+int f2q_parts_info(f2q_ctx *ctx, uint32_t *n1, uint32_t *n2);
+int f2q_read_parts(f2q_ctx *ctx, int64_t *parts_counts /* n_features */, int64_t *part1_reads /* n1 */, int64_t *part2_reads /* n2 */, int64_t classes[6]);
+int f2q_parts_recombinants(f2q_ctx *ctx, uint64_t cap, uint64_t *n, uint32_t *part1, uint32_t *part2, uint32_t *reads);
+
 #ifdef __cplusplus
 }
 #endif
