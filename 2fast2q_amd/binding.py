@@ -28,6 +28,7 @@ EXPORTS = (
     "f2q_set_sample_barcodes", "f2q_read_demux",
     "f2q_set_strand", "f2q_read_strands",
     "f2q_set_parts", "f2q_parts_info", "f2q_read_parts", "f2q_parts_recombinants",
+    "f2q_set_stagger", "f2q_read_stagger",
 )
 
 STRANDS = ("fwd", "rev", "both")            # F2Q_STRAND_FWD / _REV / _BOTH
@@ -194,6 +195,8 @@ def load(path=None):
     u32p = C.POINTER(C.c_uint32)
     L.f2q_umi_pairs.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), u32p, u32p, u32p]
     L.f2q_set_parts.argtypes = [vp]
+    L.f2q_set_stagger.argtypes = [vp, C.c_int32]
+    L.f2q_read_stagger.argtypes = [vp, i64p, i64p, C.c_int32]
     L.f2q_parts_info.argtypes = [vp, u32p, u32p]
     L.f2q_read_parts.argtypes = [vp, i64p, i64p, i64p, i64p]
     L.f2q_parts_recombinants.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), u32p, u32p, u32p]
@@ -293,10 +296,15 @@ class Counter:
     (``start="a,b"``, or one window per mate with ``start2``), every feature "A:B".  ``parts_info()`` gives the sizes of
     the two part libraries (ids in first-occurrence order over the features), ``read_parts()`` the counts per feature by
     the part rule, the two marginals and the six read classes, ``parts_recombinants()`` the recombinant pairs.
+
+    ``stagger=N`` (1 .. 32) tries the one fixed window at the starts s .. s + N (f2q_set_stagger): the earliest exact start
+    wins, else the earliest start within ``miss``.  Counter mode, single reads, one ``start``, no UMIs, sample barcodes,
+    strand mode or parts; ``read_stagger()`` returns the reads assigned perfectly / imperfectly at each offset.  0: a plain
+    context.
     """
 
     def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, umi_header=None,
-                 sample_barcodes=None, barcode_mismatch=0, strand="fwd", parts=False, **params):
+                 sample_barcodes=None, barcode_mismatch=0, strand="fwd", parts=False, stagger=0, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -317,6 +325,7 @@ class Counter:
         self.barcode_mismatch = 0
         self.strand = "fwd"              # the strand mode of the context (set_strand)
         self.parts = False               # each part of a pair library matched alone (set_parts)
+        self.stagger = 0                 # extra starts the window is tried at (set_stagger)
         try:
             self.set_strand(strand)
             if sample_barcodes is not None:
@@ -335,6 +344,8 @@ class Counter:
                 self.set_umi_reads(True)
             if parts:
                 self.set_parts()
+            if stagger:
+                self.set_stagger(stagger)
         except BaseException:
             self.close()
             raise
@@ -442,6 +453,18 @@ class Counter:
         """match each part of a pair library alone and count recombinants (f2q_set_parts); after set_mate2, before counting"""
         self._check(self._L.f2q_set_parts(self._h))
         self.parts = True
+
+    def set_stagger(self, n):
+        """try the one fixed window at the starts s .. s + n, 0 <= n <= 32 (f2q_set_stagger); before counting; 0 clears it"""
+        self._check(self._L.f2q_set_stagger(self._h, int(n)))
+        self.stagger = int(n)
+
+    def read_stagger(self):
+        """(perfect[n + 1], imperfect[n + 1]) as int64 arrays (f2q_read_stagger): reads assigned at each offset"""
+        out = [np.zeros(self.stagger + 1, dtype=np.int64) for _ in range(2)]
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.f2q_read_stagger(self._h, out[0].ctypes.data_as(i64p), out[1].ctypes.data_as(i64p), self.stagger + 1))
+        return tuple(out)
 
     def parts_info(self):
         """(n1, n2): the sizes of the two part libraries (f2q_parts_info)"""

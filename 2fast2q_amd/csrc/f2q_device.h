@@ -2978,4 +2978,165 @@ F2Q_HD void strand_read(const RunDev &run, const LibDev &lib, const EcDev &ec, c
     for (int k = 0; k < 5; k++) st[k] += keep[k];
 }
 
+// ---------------------------------------------------------------------------------------------
+// staggered libraries (f2q_set_stagger): one fixed window tried at the starts s .. s + n
+// ---------------------------------------------------------------------------------------------
+// The rule is stated in include/f2q.h (stagger_verdict).  V(d) is part_verdict at start s + d: the slice, the Phred test
+// and match_key of a run with that one window.  The read counts as the earliest perfect V(d), else as the earliest
+// imperfect V(d), else as V(0) counts it.  Two layouts that must agree: the walk (the rule as written, on any pointer
+// type) and the span (a staged record, a library of regular features, 1 <= L <= 31: every start decided from registers).
+#define F2Q_STAGGER_MAX 32
+struct StaggerDev {
+    int32_t n;                       // the starts are s + 0 .. s + n
+    int32_t walk;                    // 1: the walk layout everywhere (F2Q_STAGGER_WALK=1)
+    unsigned long long *hist;        // [2][n + 1]: reads assigned perfectly / imperfectly at each offset
+};
+// the walk layout: returns 1 perfect, 2 imperfect (id, off set), 3 non-aligned, 4 quality failed (off = -1).
+// v0 / di / idi: what the starts before `from` have given (the span layout hands its clipped starts over in this way)
+template <class P>
+F2Q_HD int stagger_walk(const RunDev &run, const LibDev &lib, int from, int n, P seq, int r, P qual, int qn,
+                        int &v0, int &di, uint32_t &idi, uint32_t &id, int &off)
+{
+    for (int d = from; d <= n; d++) {
+        uint32_t f = 0;
+        const int v = part_verdict(run, lib, seq, 0, r, qual, 0, qn, run.start[0] + d, f);
+        if (d == 0) v0 = v;
+        if (v == 1) { id = f; off = d; return 1; }            // the earliest exact start: nothing later can outrank it
+        if (v == 2 && di < 0) { di = d; idi = f; }
+    }
+    return 0;
+}
+// positions [s, s + lim) of a staged record as registers: 2-bit codes (position p in bits 2p .. 2p + 1 of lo, or of hi
+// from p = 32; a non-ACGT symbol stored as 0), one bit per non-ACGT symbol and one per quality byte that fails thr.
+// sw / qw: the words the lines are staged in, their bytes at offsets ms / mq (stage_line's layout).  lim <= 63, and
+// s + lim <= min(r, qn): only words that hold bytes of the lines are read.
+struct StaggerSpan { uint64_t lo, hi, nmask, qmask; };
+F2Q_HD void stagger_span(const uint32_t *sw, const uint32_t *qw, uint32_t ms, uint32_t mq, int s, int lim, int thr, StaggerSpan &sp)
+{
+    sp.lo = 0; sp.hi = 0; sp.nmask = 0; sp.qmask = 0;
+    if (lim <= 0) return;
+    const uint32_t fs = ms + (uint32_t)s, es = fs + (uint32_t)lim;
+    for (uint32_t w = fs >> 2; 4u * w < es; w++) {
+        const uint32_t u = sw[w];
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b++) {
+            const uint32_t at = 4u * w + b;
+            if (at < fs || at >= es) continue;
+            const uint32_t p = at - fs;
+            uint32_t c = base_code(up8((uint8_t)(u >> (8u * b))));
+            if (c > 3u) { sp.nmask |= 1ull << p; c = 0; }
+            if (p < 32u) sp.lo |= (uint64_t)c << (2u * p); else sp.hi |= (uint64_t)c << (2u * (p - 32u));
+        }
+    }
+    if (thr < 33) return;
+    const uint32_t fq = mq + (uint32_t)s, eq = fq + (uint32_t)lim;
+    for (uint32_t w = fq >> 2; 4u * w < eq; w++) {
+        const uint32_t u = qw[w];
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b++) {
+            const uint32_t at = 4u * w + b;
+            if (at < fq || at >= eq) continue;
+            if (q_fails((uint8_t)(u >> (8u * b)), thr)) sp.qmask |= 1ull << (at - fq);
+        }
+    }
+}
+// the 2-bit key of the window of L bases at span position d (d <= 32, d + L <= 63): a funnel shift of the two words
+F2Q_HD uint64_t stagger_key(const StaggerSpan &sp, int d, int L)
+{
+    const uint64_t k = d == 0 ? sp.lo : d < 32 ? (sp.lo >> (2 * d)) | (sp.hi << (64 - 2 * d)) : sp.hi;
+    return k & ((1ull << (2 * L)) - 1ull);
+}
+// bit j of m -> bit 2j (match_regular's `forced`)
+F2Q_HD uint64_t stagger_spread(uint64_t m)
+{
+    m &= 0xFFFFFFFFull;
+    m = (m | (m << 16)) & 0x0000FFFF0000FFFFull;
+    m = (m | (m << 8)) & 0x00FF00FF00FF00FFull;
+    m = (m | (m << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    m = (m | (m << 2)) & 0x3333333333333333ull;
+    m = (m | (m << 1)) & 0x5555555555555555ull;
+    return m;
+}
+#define F2Q_STAGGER_BATCH 4          // exact probes of pass 1 whose first loads are in flight together
+// the span layout.  nv starts (0 .. nv - 1) have their window wholly inside both lines and are decided from sp; the
+// starts nv .. n are clipped by a line's end (they come after every whole one) and go to the walk routine one by one.
+F2Q_HD int stagger_spanned(const RunDev &run, const LibDev &lib, int n, const uint8_t *seq, int r, const uint8_t *qual, int qn,
+                           const StaggerSpan &sp, int nv, uint32_t &id, int &off)
+{
+    const int L = run.length;
+    const uint64_t wm = (1ull << L) - 1ull, bad = sp.nmask | sp.qmask;
+    const LenGroup &g = lib.grp[L];
+    // pass 1: every whole start whose window is clean, one exact probe each (lib_exact with the first loads batched)
+    if (g.n != 0) {
+        const uint32_t m = (1u << g.exact.bits) - 1u;
+        const auto tab_keys = gp(lib.tab_keys) + g.exact.off;
+        int dp = -1; uint32_t sp_slot = 0;
+        for (int d0 = 0; d0 < nv; d0 += F2Q_STAGGER_BATCH) {
+            uint64_t key[F2Q_STAGGER_BATCH], k0[F2Q_STAGGER_BATCH];
+            uint32_t slot[F2Q_STAGGER_BATCH];
+#pragma unroll
+            for (int j = 0; j < F2Q_STAGGER_BATCH; j++) {
+                const int d = d0 + j;
+                const bool live = dp < 0 && d < nv && ((bad >> d) & wm) == 0;
+                key[j] = live ? stagger_key(sp, d, L) : 0;
+                slot[j] = hash_slot(key[j], g.exact.bits);
+                k0[j] = live ? tab_keys[slot[j]] : KEY_EMPTY;
+            }
+#pragma unroll
+            for (int j = 0; j < F2Q_STAGGER_BATCH; j++) {
+                uint64_t k = k0[j]; uint32_t s = slot[j];
+                while (dp < 0 && k != KEY_EMPTY) {
+                    if (k == key[j]) { dp = d0 + j; sp_slot = s; break; }
+                    s = (s + 1u) & m;
+                    k = tab_keys[s];
+                }
+            }
+        }
+        if (dp >= 0) { id = gp(lib.tab_idx)[g.exact.off + sp_slot]; off = dp; return 1; }
+    }
+    int v0 = nv > 0 ? ((sp.qmask & wm) ? 4 : 3) : 3, di = -1; uint32_t idi = 0;
+    if (nv <= n && stagger_walk(run, lib, nv, n, seq, r, qual, qn, v0, di, idi, id, off)) return 1;
+    // pass 2: nothing is exact, so the whole starts are searched within --m in start order (lanes diverge here)
+    if (run.miss > 0) {
+        for (int d = 0; d < nv; d++) {
+            if ((sp.qmask >> d) & wm) continue;
+            const uint64_t nm = (sp.nmask >> d) & wm;
+            const int nforced = popc64(nm);
+            if (nforced > run.miss) continue;
+            MinTrack t; t.init(run.miss);
+            lib_near(lib, stagger_key(sp, d, L), L, stagger_spread(nm), t);
+            if (t.cnt == 1) { id = t.idx; off = d; return 2; }
+        }
+    }
+    if (di >= 0) { id = idi; off = di; return 2; }
+    off = -1;
+    return v0;
+}
+// One record of a stagger context: a lane of k_count_stagger.  sw / qw: the words the two lines are staged in (their bytes
+// at offsets ms / mq), or nullptr: the record is walked where it lies (gseq / gqual).  Returns the read's verdict (1 .. 4),
+// its feature in id and its offset in off (-1: no start assigned it).
+template <class G>
+F2Q_HD int stagger_read(const RunDev &run, const LibDev &lib, const StaggerDev &sd, const uint32_t *sw, const uint32_t *qw,
+                        uint32_t ms, uint32_t mq, G gseq, G gqual, int r, int qn, uint32_t &id, int &off)
+{
+    int v0 = 3, di = -1; uint32_t idi = 0;
+    if (!sw) {
+        if (stagger_walk(run, lib, 0, sd.n, gseq, r, gqual, qn, v0, di, idi, id, off)) return 1;
+    } else {
+        const uint8_t *seq = reinterpret_cast<const uint8_t *>(sw) + ms, *qual = reinterpret_cast<const uint8_t *>(qw) + mq;
+        const int s = run.start[0], L = run.length;
+        if (!sd.walk && lib.n_irregular == 0 && L >= 1 && L <= F2Q_REG_MAXLEN && s >= 0) {
+            const int room = (r < qn ? r : qn) - s - L + 1;                  // starts whose window lies inside both lines
+            const int nv = room < 0 ? 0 : room > sd.n + 1 ? sd.n + 1 : room;
+            StaggerSpan sp;
+            stagger_span(sw, qw, ms, mq, s, nv > 0 ? nv - 1 + L : 0, run.thr, sp);
+            return stagger_spanned(run, lib, sd.n, seq, r, qual, qn, sp, nv, id, off);
+        }
+        if (stagger_walk(run, lib, 0, sd.n, seq, r, qual, qn, v0, di, idi, id, off)) return 1;
+    }
+    if (di >= 0) { id = idi; off = di; return 2; }
+    off = -1;
+    return v0;
+}
+
 } // namespace f2q

@@ -36,6 +36,7 @@ using namespace f2q;
 #include "f2q_umi_kernels.h"
 #include "f2q_demux_kernels.h"
 #include "f2q_strand_kernels.h"
+#include "f2q_stagger_kernels.h"
 #include "f2q_parts_kernels.h"
 
 // ===============================================================================================
@@ -145,6 +146,13 @@ struct f2q_ctx {
         std::vector<void *> allocs;      // rev_counts + extra, one allocation
         uint64_t words = 0;              // of that allocation: max(n_features, 1) + 4
     } strand;
+    // staggered libraries (f2q_set_stagger): the window tried at the starts s .. s + n, the reads assigned at each offset
+    struct {
+        int32_t n = 0;                   // 0: a plain context
+        StaggerDev dev{};
+        std::vector<void *> allocs;      // the two histograms, one allocation of 2 * (n + 1) words
+        bool env_general = false;        // what F2Q_FORCE_GENERAL said before the context was sent down the raw-record road
+    } stagger;
     // pair libraries with each part matched alone (f2q_set_parts): the two part libraries (indices of their own, as the
     // assign library has one), the pair table, parts_counts / the marginals / the six class counters (one allocation) and
     // the recombinant set, which outlives the pieces of a file; parts_reserve sizes it before every launch
@@ -612,6 +620,7 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     strand_drop(c);
     if (c->trace && c->parts.on) fprintf(stderr, "[f2q trace] recombinant set: %llu slots, %llu rehashes\n", (unsigned long long)c->parts.n_slots, (unsigned long long)c->parts.rehashes);
     parts_drop(c);
+    free_all(c, c->stagger.allocs);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
@@ -673,6 +682,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (c->demux.on) { demux_drop(c); if ((rc = demux_alloc(c))) return rc; }      // ... and a new matrix: a row has a word per feature
     if (c->strand.mode) { strand_drop(c); if ((rc = strand_alloc(c))) return rc; }  // ... and reverse-strand counts that start afresh
     if (c->parts.on && (rc = parts_install(c, seqs ? seqs : "", offs, n))) return rc;   // ... and part libraries, a pair table and a set of its own
+    if (c->stagger.n) HIPC(c, hipMemsetAsync(c->stagger.dev.hist, 0, 2 * ((size_t)c->stagger.n + 1) * sizeof(unsigned long long), c->stream));   // ... and offsets that start afresh
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
     // symbol of any feature), every other odd symbol still sends the read to the byte-exact routine
@@ -697,6 +707,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
     if (c->demux.on && c->demux.dev.matrix) if (int rc = demux_clear(c)) return rc;
     if (c->strand.mode && c->strand.dev.rev_counts) HIPC(c, hipMemsetAsync(c->strand.dev.rev_counts, 0, c->strand.words * sizeof(unsigned long long), c->stream));
     if (c->parts.on && c->parts.dev.counts) if (int rc = parts_clear(c)) return rc;
+    if (c->stagger.n) HIPC(c, hipMemsetAsync(c->stagger.dev.hist, 0, 2 * ((size_t)c->stagger.n + 1) * sizeof(unsigned long long), c->stream));
     c->reads_seen = 0;
     c->ec_gen++;
     // no host synchronisation: the clear is ordered on the context's stream like every launch and read-back after it
@@ -730,6 +741,7 @@ extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 }
 
 // ---- distinct UMIs per feature: the ABI ---------------------------------------------------------------------------
+static const char *const STAGGER_NO_UMI = "a stagger context (f2q_set_stagger) takes no UMIs: the two are not combined";
 static const char *const STRAND_NO_UMI = "a context with a strand mode (f2q_set_strand: rev / both) takes no UMIs: the two are not combined";
 static const char *const PARTS_NO_UMI = "a parts context (f2q_set_parts) takes no UMIs: the two are not combined";
 static const char *const DEMUX_NO_UMI = "a demultiplexing context (f2q_set_sample_barcodes) takes no UMIs: the two are not combined";
@@ -750,6 +762,7 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) takes f2q_set_umi_paired");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
+    if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
     if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
     if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
@@ -768,6 +781,7 @@ extern "C" int f2q_set_umi_header(f2q_ctx *c, int32_t sep, int32_t length)
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_header takes a Counter context: Extract+Count assigns no read to a feature");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
+    if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
     if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_header comes once, in place of f2q_set_umi / f2q_set_umi_paired and before counting");
     const bool alnum = (sep >= '0' && sep <= '9') || (sep >= 'A' && sep <= 'Z') || (sep >= 'a' && sep <= 'z');
@@ -789,6 +803,7 @@ extern "C" int f2q_set_umi_paired(f2q_ctx *c, int32_t start1, int32_t length1, i
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a Counter context: Extract+Count assigns no pair to a feature");
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
+    if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
     if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (!c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a paired context: call f2q_set_mate2 first (single reads: f2q_set_umi)");
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired comes once, after f2q_set_mate2 and before counting");
@@ -837,6 +852,7 @@ extern "C" int f2q_set_sample_barcodes(f2q_ctx *c, const char *seqs, uint32_t n,
     if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes takes single reads: a paired context (f2q_set_mate2) is not demultiplexed");
     if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a UMI context: sample barcodes and UMIs are not combined");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
+    if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a stagger context (f2q_set_stagger): the two are not combined");
     if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a parts context (f2q_set_parts): the two are not combined");
     if (c->demux.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes comes once, after f2q_create and before counting");
     std::string up, err;
@@ -895,6 +911,7 @@ extern "C" int f2q_set_strand(f2q_ctx *c, int32_t mode)
     if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a UMI context: a strand mode and UMIs are not combined");
     if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
     if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a parts context (f2q_set_parts): the two are not combined");
+    if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a stagger context (f2q_set_stagger): the two are not combined");
     if (c->strand.mode || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) comes once, after f2q_create and before counting");
     HIPC(c, hipSetDevice(c->device));
     c->strand.mode = mode; c->strand.dev = StrandDev{}; c->strand.dev.mode = mode;
@@ -924,6 +941,73 @@ extern "C" int f2q_read_strands(f2q_ctx *c, int64_t *rev_counts, int64_t extra[4
     return F2Q_OK;
 }
 
+// ---- staggered libraries: the ABI (include/f2q.h) ---------------------------------------------------------------------
+// the plan of a context that leaves the stagger road again: what f2q_create and f2q_set_features would have made of it
+static int stagger_replan(f2q_ctx *c)
+{
+    if (!c->have_lib) return setup_run(c);
+    const std::string bytes((const char *)c->ix.feat_bytes.data(), c->ix.feat_bytes.size());      // (build_index rewrites c->ix)
+    const std::vector<uint32_t> offs(c->ix.feat_off.begin(), c->ix.feat_off.end());
+    return f2q_set_features(c, bytes.data(), offs.data(), c->ix.n_features);
+}
+
+extern "C" int f2q_set_stagger(f2q_ctx *c, int32_t n)
+{
+    if (!c) return F2Q_EINVAL;
+    if (n < 0 || n > F2Q_STAGGER_MAX) return fail(c, F2Q_EINVAL, "f2q_set_stagger takes 0 .. 32 extra starts, not " + std::to_string(n));
+    if (n == 0 && !c->stagger.n) return F2Q_OK;              // a plain context stays one: accepted at any time
+    if (c->counted) return fail(c, F2Q_ESTATE, "f2q_set_stagger comes before counting");
+    if (n == 0) {                                            // a plain context again
+        HIPC(c, hipSetDevice(c->device));
+        free_all(c, c->stagger.allocs);
+        c->stagger.n = 0; c->stagger.dev = StaggerDev{};
+        c->force_general = c->stagger.env_general;
+        return stagger_replan(c);
+    }
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes a Counter context: Extract+Count with a stagger is not implemented");
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes single reads: a paired context (f2q_set_mate2) is not staggered");
+    if (!c->run_h.fixed) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes a fixed window (--st): an anchored run (--us/--ds) finds its window itself");
+    if (c->run_h.n_iter != 1) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes exactly one window (--st with one value), not " + std::to_string(c->run_h.n_iter));
+    if (c->run_h.start[0] < 0) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes a window that starts at or after the first base (--st >= 0)");
+    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a UMI context: a stagger and UMIs are not combined");
+    if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
+    if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
+    if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a parts context (f2q_set_parts): the two are not combined");
+    HIPC(c, hipSetDevice(c->device));
+    unsigned long long *w = nullptr; std::vector<void *> owner;
+    if (dev_alloc(c, 2 * ((size_t)n + 1), &w, owner, 0)) {
+        free_all(c, owner);
+        return fail(c, F2Q_ENOMEM, "no device memory for the offset histograms: " + c->err);
+    }
+    if (!c->stagger.n) c->stagger.env_general = c->force_general;
+    free_all(c, c->stagger.allocs);
+    c->stagger.allocs = owner;
+    c->stagger.n = n; c->stagger.dev.n = n; c->stagger.dev.hist = w;
+    { const char *e = getenv("F2Q_STAGGER_WALK"); c->stagger.dev.walk = e && e[0] == '1'; }
+    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
+    c->force_general = true;
+    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
+    c->plan.inband_n = false; c->plan.n_only = false;
+    if (c->trace) fprintf(stderr, "[f2q trace] stagger %d: every read takes k_count_stagger (%s layout)\n", n, c->stagger.dev.walk ? "walk" : "span");
+    return F2Q_OK;
+}
+
+extern "C" int f2q_read_stagger(f2q_ctx *c, int64_t *perfect, int64_t *imperfect, int32_t n_offsets)
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->stagger.n) return fail(c, F2Q_ESTATE, "not a stagger context: call f2q_set_stagger with 1 .. 32 first");
+    if (n_offsets != c->stagger.n + 1) return fail(c, F2Q_EINVAL, "f2q_read_stagger takes n_offsets = n + 1 = " + std::to_string(c->stagger.n + 1) + ", not " + std::to_string(n_offsets));
+    HIPC(c, hipSetDevice(c->device));
+    unsigned long long h[2 * (F2Q_STAGGER_MAX + 1)];
+    HIPC(c, hipMemcpyAsync(h, c->stagger.dev.hist, 2 * (size_t)n_offsets * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    for (int32_t d = 0; d < n_offsets; d++) {
+        if (perfect) perfect[d] = (int64_t)h[d];
+        if (imperfect) imperfect[d] = (int64_t)h[n_offsets + d];
+    }
+    return F2Q_OK;
+}
+
 // ---- pair libraries, each part matched alone: the ABI (include/f2q.h) -------------------------------------------------
 extern "C" int f2q_set_parts(f2q_ctx *c)
 {
@@ -936,6 +1020,7 @@ extern "C" int f2q_set_parts(f2q_ctx *c)
     if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on a UMI context: part verdicts and UMIs are not combined");
     if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_parts on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
+    if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_parts on a stagger context (f2q_set_stagger): the two are not combined");
     if (c->parts.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_parts comes once, after f2q_create (and f2q_set_mate2) and before counting");
     HIPC(c, hipSetDevice(c->device));
     { const char *e = getenv("F2Q_PARTS_SLOTS"); if (e && atol(e) > 0) { c->parts.min_slots = 2; while (c->parts.min_slots < (uint64_t)atol(e) && c->parts.min_slots < (1ull << 32)) c->parts.min_slots <<= 1; } }
@@ -1763,6 +1848,13 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
         EC_POINT(c, c->strand.mode == F2Q_STRAND_BOTH ? "k_count_strand<both>" : "k_count_strand<rev>");
         return F2Q_OK;
     }
+    if (c->stagger.n) {                                          // the same road with the window tried at n + 1 starts (f2q_set_stagger)
+        hipLaunchKernelGGL(k_count_stagger, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, rb, acc, c->stagger.dev);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, "k_count_stagger");
+        return F2Q_OK;
+    }
     if (c->parts.on) {                                           // the same road with the part verdicts, the tables and the recombinant set (f2q_set_parts)
         if (!c->parts.dev.counts) return fail(c, F2Q_ESTATE, "a parts context without its tables: f2q_set_features failed");
         if ((rc = parts_reserve(c, rb.n))) return rc;
@@ -1912,6 +2004,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
     if (!k0) { k0 = c->ev_k0; k1 = c->ev_k1; }          // (a queued step brings its own pair)
     if (c->prm.mode == 0 && !c->have_lib) return fail(c, F2Q_ESTATE, "f2q_set_features must be called before counting in Counter mode");
     if (c->umi.on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
+    if (c->stagger.n && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_stagger: a stagger context counts single raw records only");
     if (c->strand.mode && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_strand: a context with a strand mode counts single raw records only");
     if (c->demux.on && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_sample_barcodes: a demultiplexing context counts single raw records only");
     if (c->parts.on && (b->pb.n_tiles || (b->rb.n && (b->rb.len1 != nullptr) != (c->n_mate1 != 0))))
@@ -2441,6 +2534,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
     if (c->umi.on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only: f2q_set_mate2 comes first, then f2q_set_umi_paired");
     if (c->demux.on) return fail(c, F2Q_ESTATE, "a demultiplexing context (f2q_set_sample_barcodes) counts single reads only");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts single reads only");
+    if (c->stagger.n) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts single reads only");
     if (c->parts.on) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) keeps its windows: f2q_set_mate2 comes first, then f2q_set_parts");
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
@@ -3120,6 +3214,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
     if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
     if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
+    if (c->stagger.n && world > 1) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts whole files: the offset histograms of several ranks are not merged");
     if (c->parts.on && world > 1) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) counts whole files: the tables and sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     size_t CH = file_chunk_bytes((size_t)256 << 20);
@@ -3407,6 +3502,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
     if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
     if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
     if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
+    if (c->stagger.n && world > 1) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts whole files: the offset histograms of several ranks are not merged");
     if (c->parts.on && world > 1) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) counts whole files: the tables and sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     TextSource src;

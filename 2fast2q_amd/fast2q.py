@@ -169,6 +169,8 @@ def _counter_kwargs(param):
         kwargs['strand'] = param['strand']
     if param.get('parts'):                          # --parts: each part of a pair library matched alone (f2q_set_parts); part of the key too
         kwargs['parts'] = True
+    if param.get('stagger'):                        # --stagger N: the window tried at N + 1 starts (f2q_set_stagger); part of the key too
+        kwargs['stagger'] = param['stagger']
     return kwargs
 
 
@@ -314,6 +316,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         raise RuntimeError("--strand: the reverse-strand counts are not merged across several ranks; run one process")
     if param.get('parts') and sharding.world().size > 1:
         raise RuntimeError("--parts: the part tables and recombinant sets are not merged across several ranks; run one process")
+    if param.get('stagger') and sharding.world().size > 1:
+        raise RuntimeError("--stagger: the offset histograms are not merged across several ranks; run one process")
     ctx =_context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
@@ -357,6 +361,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             param.setdefault('demux_counted', {})[raw] = ctx.read_demux()
         if param.get('strand'):                     # --strand rev / both: reads assigned on the reverse strand, the strand counters (f2q_read_strands)
             param.setdefault('strand_counted', {})[raw] = ctx.read_strands()
+        if param.get('stagger'):                    # --stagger N: reads assigned without / with mismatches at each offset (f2q_read_stagger)
+            param.setdefault('stagger_counted', {})[raw] = ctx.read_stagger()
         if param.get('parts'):                      # --parts: counts by the part rule, the marginals, the six classes (f2q_read_parts) and the recombinant pairs
             param.setdefault('parts_counted', {})[raw] = (ctx.read_parts(), ctx.parts_recombinants())
     except BaseException:
@@ -465,6 +471,9 @@ def aligner(i, raw, features, param, reads_stats):
         columns = [SampleResult(f"{sample.name}:fwd", value, unit, _sample_rows((name, fwd) for name, fwd, _ in split), {}),
                    SampleResult(f"{sample.name}:rev", value, unit, _sample_rows((name, rev) for name, _, rev in split), {})]
         param.setdefault("strand_samples", {})[sample.name] = (columns, [int(n) for n in extra])
+    if raw in param.get('stagger_counted', {}):      # --stagger N: the sample's two columns of <name>_stagger.csv
+        perfect, imperfect = param['stagger_counted'].pop(raw)
+        param.setdefault("stagger_samples", {})[sample.name] = ([int(n) for n in perfect], [int(n) for n in imperfect])
     if raw in param.get('parts_counted', {}):        # --parts: the same rows holding parts_counts; the recombinant pairs by their texts; the classes
         (parts_counts, part1, part2, classes), (i1, i2, reads) = param['parts_counted'].pop(raw)
         names = [f.name for f in features.values()]
@@ -553,6 +562,9 @@ def initializer(cmd):
     if param.get('strand'):
         print(f" Reads are counted on {'the reverse strand' if param['strand'] == 'rev' else 'the forward strand, else on the reverse strand'}")
         print(f" {strand_header(param)[1:]}")
+    if param.get('stagger'):
+        print(f" The feature window is tried at the starts {param['start']} .. {int(param['start']) + param['stagger']}: the earliest exact one counts, else the earliest within --m")
+        print(f" {stagger_header(param)[1:]}")
     if param.get('parts'):
         print(" Each of the two feature parts is also matched on its own; recombinant reads are counted per pair of parts")
         print(f" {PARTS_HEADER[1:]}")
@@ -613,6 +625,11 @@ def sample_barcodes_header(param):
     """the line a --sb run adds to the parameter print-out and to the head of <name>_stats.csv"""
     sb = param['sample_barcodes']
     return f"#Sample barcodes, start, length, mismatches: {sb['start']},{len(sb['barcodes'][0])},{sb['miss']}"
+
+
+def stagger_header(param):
+    """the line a --stagger N run (N > 0) adds to the parameter print-out and to the head of <name>_stats.csv"""
+    return f"#Stagger: {param['stagger']}"
 
 
 def strand_header(param):
@@ -683,6 +700,7 @@ def input_parser(argv=None):
     ap.add_argument("--sbs", help="With --sb: the start position of the sample barcode within the read (default = 0)")
     ap.add_argument("--sbm", help="With --sb: mismatches allowed in the sample barcode, 0 or 1 (default = 0)")
     ap.add_argument("--strand", help="fwd (default), rev or both: the orientation the reads are counted in. rev: every read is reverse-complemented first; both: a read that is assigned no feature as sequenced is tried reverse-complemented (<name>_strand.csv). Counter mode, single reads, one process")
+    ap.add_argument("--stagger", help="N (0-32): the one fixed window (--st s --l L) is tried at the starts s .. s+N; a read counts at the earliest start that reads a feature exactly, else at the earliest one within --m (<name>_stagger.csv). 0 (default): off. Counter mode, single reads, one --st value, one process")
     ap.add_argument("--parts", nargs='?', const=True, help="Pair libraries (features A:B over exactly two windows: --st a,b, or --pe --st a --st2 b): each part is also matched on its own with --m mismatches per part; reads whose two parts the library does not pair are counted as recombinants (<name>_parts.csv, <name>_recombinants.csv). Counter mode, one process")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
@@ -848,6 +866,26 @@ def input_parser(argv=None):
                                       f"--st {p['start']}" + (f" --st2 {args.st2}" if args.pe is not None else "") + f" names {' + '.join(str(n) for n in windows)}.")
             sys.exit(2)
         p['parts'] = True
+    if args.stagger is not None:
+        if not re.fullmatch(r"[0-9]{1,3}", str(args.stagger)) or int(args.stagger) > 32:
+            colourful_errors("FATAL", f"--stagger {args.stagger}: expected a number of extra starts, 0 to 32.")
+            sys.exit(2)
+        if int(args.stagger):                                    # (0 is a run without the flag)
+            if p['Running Mode'] != "C":
+                colourful_errors("FATAL", f"--stagger {args.stagger} only has a meaning in Counter mode: it cannot be combined with --mo EC.")
+                sys.exit(2)
+            others = [f for f, v in (("--pe", args.pe), ("--us", args.us), ("--ds", args.ds), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2),
+                                     ("--umih", args.umih), ("--sb", args.sb), ("--parts", args.parts)) if v is not None]
+            if args.strand in ("rev", "both"):
+                others.append(f"--strand {args.strand}")
+            if others:
+                colourful_errors("FATAL", f"--stagger {args.stagger} cannot be combined with {' / '.join(others)}: one fixed window of single reads is tried at "
+                                          "several starts, without anchors, UMIs, sample barcodes, a strand mode or parts.")
+                sys.exit(2)
+            if not re.fullmatch(r"[0-9]+", str(p['start']).strip()):
+                colourful_errors("FATAL", f"--stagger {args.stagger} needs exactly one window start at or after the first base: --st {p['start']} does not name one.")
+                sys.exit(2)
+            p['stagger'] = int(args.stagger)
     if args.assign is not None:
         if p['Running Mode'] != "EC":
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
@@ -886,6 +924,9 @@ def file_sizer_split(param):
         sys.exit(2)
     if param.get('strand') and sharding.world().size > 1:
         colourful_errors("FATAL", "--strand: the reverse-strand counts are not merged across several ranks; run one process.")
+        sys.exit(2)
+    if param.get('stagger') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--stagger: the offset histograms are not merged across several ranks; run one process.")
         sys.exit(2)
     if param.get('parts') and sharding.world().size > 1:
         colourful_errors("FATAL", "--parts: the part tables and recombinant sets are not merged across several ranks; run one process.")
@@ -1001,6 +1042,8 @@ def run_headers(param):
         lines.append(sample_barcodes_header(param))
     if param.get('strand'):
         lines.append(strand_header(param))
+    if param.get('stagger'):
+        lines.append(stagger_header(param))
     if param.get('parts'):
         lines.append(PARTS_HEADER)
     return lines
@@ -1055,6 +1098,12 @@ def compiling(param):
         shead, stable = _table_of([column for s in ordered for column in param["strand_samples"].get(s.name, ((), ()))[0]])
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_strand.csv"),
                    [shead] + [[feature] + counts for feature, counts in stable.items()])
+    if param.get("stagger_samples"):                 # --stagger N: a row per offset; per file, in <name>.csv's column order, its perfect and its imperfect reads
+        stag = param["stagger_samples"]
+        names = [s.name for s in ordered if s.name in stag]
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stagger.csv"),
+                   [["#Offset", "Start"] + [f"{name}:{kind}" for name in names for kind in ("perfect", "imperfect")]] +
+                   [[d, int(param['start']) + d] + [stag[name][k][d] for name in names for k in (0, 1)] for d in range(param['stagger'] + 1)])
     if param.get("parts_samples"):                   # --parts: <name>.csv's layout and row order holding parts_counts; the recombinant pairs of any sample
         parts = param["parts_samples"]
         _, phead, ptable = compile_table({name: rec[0] for name, rec in parts.items()})
@@ -1104,6 +1153,9 @@ STRAND_STATS_HEAD = ["#Sample name (strands)", "Number of reads assigned on the 
                      "Number of reads assigned on the reverse strand with mismatches", "Number of reads whose reverse strand was examined"]
 
 
+STAGGER_STATS_HEAD = ["#Sample name (stagger)", "Number of reads assigned at offset 0", "Number of reads assigned at a later offset", "Offset with the most assigned reads"]
+
+
 PARTS_STATS_HEAD = ["#Sample name (parts)", "Number of reads whose two parts are a library pair, both without mismatches",
                     "Number of reads whose two parts are a library pair, at least one with mismatches", "Number of recombinant reads (two assigned parts the library does not pair)",
                     "Number of distinct recombinant pairs", "Number of reads with part 1 assigned only", "Number of reads with part 2 assigned only",
@@ -1131,6 +1183,13 @@ def run_stats(headers, param, compiled, head, ordered):
     strands = param.get("strand_samples", {})
     if strands:                                                  # --strand rev / both: the four strand counters per file
         global_stat += [STRAND_STATS_HEAD] + [[s.name] + strands[s.name][1] for s in ordered if s.name in strands]
+    stag = param.get("stagger_samples", {})
+    if stag:                                                     # --stagger N: where the reads of each file were assigned
+        global_stat.append(STAGGER_STATS_HEAD)
+        for s in ordered:
+            if s.name in stag:
+                both = [a + b for a, b in zip(*stag[s.name])]
+                global_stat.append([s.name, both[0], sum(both[1:]), both.index(max(both))])
     parts = param.get("parts_samples", {})
     if parts:                                                    # --parts: the six read classes per file, the distinct recombinant pairs next to their reads
         global_stat += [PARTS_STATS_HEAD] + [

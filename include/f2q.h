@@ -622,6 +622,49 @@ int f2q_parts_info(f2q_ctx *ctx, uint32_t *n1, uint32_t *n2);
 int f2q_read_parts(f2q_ctx *ctx, int64_t *parts_counts /* n_features */, int64_t *part1_reads /* n1 */, int64_t *part2_reads /* n2 */, int64_t classes[6]);
 int f2q_parts_recombinants(f2q_ctx *ctx, uint64_t cap, uint64_t *n, uint32_t *part1, uint32_t *part2, uint32_t *reads);
 
+/* ---- staggered libraries: one fixed window tried at a range of starts ------------------------------
+ * Stagger primers put 0 .. 8 extra bases in front of the amplicon, a different number for each read, so the feature
+ * starts at s + d with d unknown.  f2q_set_stagger(ctx, n) makes a single-end Counter context with exactly one fixed
+ * window (--st s --l L) try that window at the starts s, s + 1, .. s + n.
+ *
+ * The rule.  V(d) is what the reference decides for the read (its rstrip()-ed lines 2 and 4) in a run with --st s+d --l L
+ * and the run's --m and --ph: PERFECT (feature), IMPERFECT (feature), NON_ALIGNED or QUALITY_FAILED.  Clipped windows,
+ * lower case, 'N', features of other lengths and the unique-nearest rule all follow from that.
+ *
+ *     def stagger_verdict(V, n):                           # -> (verdict, offset or None)
+ *         for d in range(n + 1):
+ *             if V(d).kind == PERFECT:                     # the earliest exact start; it outranks a window with
+ *                 return V(d), d                           # mismatches at an earlier start
+ *         for d in range(n + 1):
+ *             if V(d).kind == IMPERFECT:                   # else the earliest start within --m; a start whose window is
+ *                 return V(d), d                           # ambiguous is NON_ALIGNED there and is passed over
+ *         return V(0), None                                # nobody assigns it: counted as start s counts it
+ *
+ * counts and the five counters hold the reads by that rule.  Consequences: a read that the plain run (start s) assigns
+ * perfectly keeps that verdict; n on a sample whose features all sit at s gives the plain run's perfect reads at offset 0.
+ *
+ * f2q_set_stagger comes after f2q_create and before the first counting call, before or after f2q_set_features; it may be
+ * repeated with another n.  n = 0 makes the context a plain one again (on a plain context it is accepted at any time
+ * and changes nothing): it then launches the kernels it launched before.  F2Q_EINVAL for n outside 0 .. 32.  With
+ * n > 0, F2Q_ESTATE with a message that names the cause: an Extract+Count context, a paired context (f2q_set_mate2),
+ * --us/--ds, several windows, a window that starts before the first base, a UMI context of any kind, a demultiplexing
+ * context, a non-zero strand mode, a parts context, or after a counting call; afterwards f2q_set_mate2, f2q_set_umi,
+ * f2q_set_umi_paired, f2q_set_umi_header, f2q_set_sample_barcodes, f2q_set_strand with a non-zero mode, f2q_set_parts
+ * and the sharded calls with world > 1 are F2Q_ESTATE in turn.  From then on every read takes the raw-record road
+ * (k_count_stagger) through f2q_count_block, f2q_block_from_fastq + f2q_count_resident / f2q_count_resident_queued,
+ * f2q_count_text and f2q_count_file (plain, gzip, BGZF, F2Q_DEVICE_INFLATE=1, F2Q_HOST_PACK=1).  F2Q_STAGGER_WALK=1
+ * (read by f2q_set_stagger) decides every start by the byte-exact routine instead of from registers: same results.
+ *
+ * f2q_read_stagger: perfect[d] / imperfect[d] = reads assigned without / with mismatches at offset d, d = 0 .. n;
+ * n_offsets must be n + 1 (F2Q_EINVAL otherwise); either pointer may be NULL; F2Q_ESTATE on a plain context.  It
+ * synchronises as f2q_read_counts does.  f2q_reset_counts zeroes it; a new library starts it afresh.  Invariants:
+ *   sum(perfect) == stats[F2Q_PERFECT];  sum(imperfect) == stats[F2Q_IMPERFECT].
+ * Not implemented: Extract+Count, paired samples, anchored runs, several windows, UMIs / sample barcodes / a strand mode /
+ * part verdicts with a stagger, several ranks, the packed-tile kernels. */
+#define F2Q_STAGGER_MAX_N 32
+int f2q_set_stagger(f2q_ctx *ctx, int32_t n);
+int f2q_read_stagger(f2q_ctx *ctx, int64_t *perfect /* n + 1 */, int64_t *imperfect /* n + 1 */, int32_t n_offsets);
+
 #ifdef __cplusplus
 }
 #endif
