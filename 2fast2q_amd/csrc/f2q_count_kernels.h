@@ -537,11 +537,12 @@ __device__ __forceinline__ bool lt_count_passed(uint32_t old, uint32_t inc) { re
 __device__ __forceinline__ bool lt_count_maybe_passed(uint32_t old_or) { return (old_or & 0x40004000u) != 0u; }
 // exactly one adder sees the counter pass 0x7FFF -> 0x8000; it takes 0x8000 out again (no borrow: the counter only
 // grows until then, and by far less than another 0x8000 -- also when the adder tests its old value some LDS operations
-// later) and credits the feature's global counter
+// later) and credits the feature's word of acc.carry, which k_reduce_slabs folds into its sum: the kernels that count
+// this way leave the accumulators themselves to the reduce
 __device__ __forceinline__ void lt_count_handoff(uint32_t *cnt, uint32_t bucket, uint32_t inc, const Accum &acc, const LtDesc &lt)
 {
     atomicSub(&cnt[bucket], inc << 15);
-    acc_add(&acc.counts[gp(lt.feat_of)[2u * bucket + (inc >> 16)]], 0x8000ull);
+    acc_add(&acc.carry[gp(lt.feat_of)[2u * bucket + (inc >> 16)]], 0x8000ull);
 }
 __device__ __forceinline__ void lt_count(uint32_t *cnt, uint32_t slot, const Accum &acc, const LtDesc &lt)
 {
@@ -1825,41 +1826,94 @@ __global__ __launch_bounds__(1024) void k_hist_ranges(const uint32_t *__restrict
     for (uint32_t i = threadIdx.x; i < fn; i += 1024u) row[i] = rh[i];
 }
 
-// counts[f] += sum over workgroups of slab[w][f].  Block = 64 features x 4 row lanes; grid.y splits
-// the rows further so that every thread has ~16 independent loads in flight.
-#define F2Q_RED_SPLIT 8u
+// counts[f] (+)= carry[f] + sum over workgroups of slab[w][f], in one pass: a workgroup owns F2Q_RED_FEATS features over
+// all rows, so nobody else writes its counts[] and no atomic is needed.  Thread = a column of 4 features (one 16-byte
+// load per row) x one of 16 row lanes, up to 16 loads in flight; the row lanes meet in LDS and one thread per feature
+// writes.  store: the accumulators are to be cleared (f2q_reset_counts left that pending), the result is stored and the
+// clear is no work at all; else it is added.  carry[] (lt_count_handoff) is folded in and left zero.  The last workgroup
+// of the grid has the five reference counters instead (rows of 8).
+#define F2Q_RED_FEATS 64u
 __global__ __launch_bounds__(256) void k_reduce_slabs(const uint32_t *__restrict__ slab, uint32_t n_rows, uint32_t nf,
-                                                       unsigned long long *__restrict__ counts,
+                                                       unsigned long long *__restrict__ counts, unsigned long long *__restrict__ carry,
                                                        const unsigned long long *__restrict__ stat_slab, uint32_t n_stat_rows,
-                                                       unsigned long long *__restrict__ stats)
+                                                       unsigned long long *__restrict__ stats, uint32_t store)
 {
-    __shared__ unsigned long long part[256];
-    if (blockIdx.x == 0 && blockIdx.y == 0 && stat_slab) {          // the 5 reference counters: rows of 8
+    __shared__ unsigned long long part[16][F2Q_RED_FEATS];
+    if (blockIdx.x == gridDim.x - 1u) {                             // the 5 reference counters
         const uint32_t k = threadIdx.x & 7u, sub = threadIdx.x >> 3;   // 32 row lanes x 8 columns
         unsigned long long sv = 0;
-        if (k < 5) for (uint32_t w = sub; w < n_stat_rows; w += 32u) sv += stat_slab[(uint64_t)w * 8u + k];
-        part[threadIdx.x] = sv;
+        if (k < 5)
+#pragma unroll 8
+            for (uint32_t w = sub; w < n_stat_rows; w += 32u) sv += gp(stat_slab)[(uint64_t)w * 8u + k];
+        (&part[0][0])[threadIdx.x] = sv;                            // (part[0 .. 3] hold the 256 partial sums)
         __syncthreads();
         if (threadIdx.x < 5) {
             unsigned long long tot = 0;
-            for (uint32_t q = 0; q < 32u; q++) tot += part[q * 8u + threadIdx.x];
-            if (tot) atomicAdd(&stats[threadIdx.x], tot);
+            for (uint32_t q = 0; q < 32u; q++) tot += (&part[0][0])[q * 8u + threadIdx.x];
+            if (store) gpw(stats)[threadIdx.x] = tot;
+            else if (tot) gpw(stats)[threadIdx.x] += tot;
         }
-        __syncthreads();
+        return;
     }
-    const uint32_t fx = threadIdx.x & 63u, ry = threadIdx.x >> 6;
-    const uint32_t f = blockIdx.x * 64u + fx;
-    unsigned long long sum = 0;
-    if (f < nf) {
-        const uint32_t step = F2Q_RED_SPLIT * 4u;
-#pragma unroll 8
-        for (uint32_t w = blockIdx.y * 4u + ry; w < n_rows; w += step) sum += slab[(uint64_t)w * nf + f];
+    // All loads of a round are unconditional (a row past the last is the last row again, a feature past the last the
+    // last feature: read, not summed), so that the 16 rows of a round are requested before the first is summed.
+    // A round is 16 row lanes x R = 256 rows: one round for the kernels that run a workgroup per CU (k_count_fixed4_lds,
+    // k_count_anchor_lt), two for k_count_fixed4 and k_count_multi4, whose grids go up to two workgroups per CU.
+    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+    constexpr uint32_t R = 16u;                                     // rows a thread has in flight
+    const uint32_t col = threadIdx.x & 15u, rl = threadIdx.x >> 4;
+    const uint32_t fb = blockIdx.x * F2Q_RED_FEATS, last_row = n_rows - 1u;
+    // n_features a multiple of 4: every row starts 16-byte aligned (the slab does) and the thread's features are
+    // 4 col .. 4 col + 3, one 16-byte load per row.  Else rows are aligned to 4 bytes only: the features are col,
+    // col + 16, col + 32, col + 48, four 4-byte loads per row, each contiguous over the 16 columns
+    const bool wide = (nf & 3u) == 0u;
+    unsigned long long s[4] = {0, 0, 0, 0};
+    if (wide && fb + 4u * col < nf) {
+        const auto p = gp(slab) + (fb + 4u * col);
+        for (uint32_t w0 = rl; w0 < n_rows; w0 += 16u * R) {
+            v4 v[R];
+#pragma unroll
+            for (uint32_t i = 0; i < R; i++) v[i] = *reinterpret_cast<const v4 F2Q_GLOBAL *>(p + (uint64_t)min(w0 + 16u * i, last_row) * nf);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (uint32_t i = 0; i < R; i++) {
+                const bool live = w0 + 16u * i < n_rows;
+                s[0] += live ? v[i].x : 0u; s[1] += live ? v[i].y : 0u; s[2] += live ? v[i].z : 0u; s[3] += live ? v[i].w : 0u;
+            }
+        }
+    } else if (!wide) {
+        uint32_t fk[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) fk[k] = min(fb + col + 16u * k, nf - 1u);
+        for (uint32_t w0 = rl; w0 < n_rows; w0 += 16u * R) {
+            uint32_t v[R][4];
+#pragma unroll
+            for (uint32_t i = 0; i < R; i++) {
+                const auto row = gp(slab) + (uint64_t)min(w0 + 16u * i, last_row) * nf;
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) v[i][k] = row[fk[k]];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (uint32_t i = 0; i < R; i++) {
+                const bool live = w0 + 16u * i < n_rows;
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) s[k] += live ? v[i][k] : 0u;
+            }
+        }
     }
-    part[threadIdx.x] = sum;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) part[rl][wide ? 4u * col + k : col + 16u * k] = s[k];
     __syncthreads();
-    if (ry == 0 && f < nf) {
-        sum = part[fx] + part[64 + fx] + part[128 + fx] + part[192 + fx];
-        if (sum) atomicAdd(&counts[f], sum);
+    const uint32_t f = blockIdx.x * F2Q_RED_FEATS + threadIdx.x;
+    if (threadIdx.x < F2Q_RED_FEATS && f < nf) {
+        unsigned long long sum = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < 16u; r++) sum += part[r][threadIdx.x];
+        const unsigned long long cv = gp(carry)[f];
+        if (cv) { gpw(carry)[f] = 0; sum += cv; }
+        if (store) gpw(counts)[f] = sum;
+        else if (sum) gpw(counts)[f] += sum;
     }
 }
 

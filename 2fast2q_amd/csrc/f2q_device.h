@@ -188,6 +188,8 @@ struct Accum {
     unsigned long long *stat_slab;     // [gridDim.x][8] per-workgroup stats (or nullptr)
     unsigned long long *stamp;         // diagnostic builds (-DF2Q_STAMP): per-phase cycle sums, else nullptr
     uint32_t *hit_buf;                 // large libraries: feature index per read slot (0xFFFFFFFF = none), histogrammed by k_hist_ranges
+    unsigned long long *carry;         // [n_features] what a u16 LDS counter handed off (lt_count_handoff); zero between launches:
+                                       // k_reduce_slabs folds it into its sum and writes the zero back
 };
 
 struct EcDev {

@@ -78,6 +78,11 @@ struct f2q_ctx {
     // accumulators: counts[n_features] then stats[5]
     unsigned long long *acc_d = nullptr;
     uint64_t acc_n = 0;
+    // f2q_reset_counts leaves the clear of acc_d pending: the step's first k_reduce_slabs stores instead of adding
+    // (reduce_slabs), whatever else reads or writes acc_d first clears it (acc_ready).  acc_eager: the raw pointer is out
+    // (f2q_counts_device_ptr), whoever holds it may read at any time, so a reset clears at once
+    bool acc_pending = false, acc_eager = false;
+    unsigned long long *carry_d = nullptr;   // Accum::carry, max(n_features, 1) words, zero between launches
     uint32_t *slab_d = nullptr;          // per-workgroup histogram rows of the v2 kernel
     size_t slab_n = 0;
     unsigned long long *stat_slab_d = nullptr;   // per-workgroup stats rows of 8
@@ -383,10 +388,24 @@ static int upload_lib(f2q_ctx *c) { return upload_index(c, c->ix, c->lib_h, &c->
 static int alloc_acc(f2q_ctx *c, uint64_t n_features)
 {
     if (c->acc_d) { (void)hipFree(c->acc_d); c->acc_d = nullptr; }
+    if (c->carry_d) { (void)hipFree(c->carry_d); c->carry_d = nullptr; }
     c->acc_n = n_features + 5;
+    const size_t carry_n = (size_t)std::max<uint64_t>(n_features, 1);
     HIPC(c, hipMalloc((void **)&c->acc_d, c->acc_n * sizeof(unsigned long long)));
+    HIPC(c, hipMalloc((void **)&c->carry_d, carry_n * sizeof(unsigned long long)));
     HIPC(c, hipMemsetAsync(c->acc_d, 0, c->acc_n * sizeof(unsigned long long), c->stream));
+    HIPC(c, hipMemsetAsync(c->carry_d, 0, carry_n * sizeof(unsigned long long), c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
+    c->acc_pending = false;
+    return F2Q_OK;
+}
+
+// the clear a reset left pending, now: before anything but a storing k_reduce_slabs reads or writes acc_d
+static int acc_ready(f2q_ctx *c)
+{
+    if (!c->acc_pending) return F2Q_OK;
+    HIPC(c, hipMemsetAsync(c->acc_d, 0, c->acc_n * sizeof(unsigned long long), c->stream));
+    c->acc_pending = false;
     return F2Q_OK;
 }
 
@@ -626,6 +645,7 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
     c->dev_idle.clear(); c->dev_size.clear();
     if (c->acc_d) (void)hipFree(c->acc_d);
+    if (c->carry_d) (void)hipFree(c->carry_d);
     if (c->synth_keys_d) (void)hipFree(c->synth_keys_d);
     if (c->slab_d) (void)hipFree(c->slab_d);
     if (c->stat_slab_d) (void)hipFree(c->stat_slab_d);
@@ -696,7 +716,10 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
 {
     if (!c) return F2Q_EINVAL;
     HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipMemsetAsync(c->acc_d, 0, c->acc_n * sizeof(unsigned long long), c->stream));
+    // the accumulators are cleared by whoever touches them next: a storing k_reduce_slabs, which needs no clear at all, or
+    // acc_ready.  A context whose raw pointer is out clears here and now
+    c->acc_pending = true;
+    if (c->acc_eager) if (int rc = acc_ready(c)) return rc;
     if (c->prm.mode == 1) {
         if (c->aux_stream) HIPC(c, hipStreamSynchronize(c->aux_stream));
         c->aux_busy = false;
@@ -725,6 +748,7 @@ extern "C" int f2q_read_counts(f2q_ctx *c, int64_t *counts, int64_t stats[5])
 {
     if (!c) return F2Q_EINVAL;
     HIPC(c, hipSetDevice(c->device));
+    if (int rc = acc_ready(c)) return rc;
     std::vector<unsigned long long> h(c->acc_n);
     HIPC(c, hipMemcpyAsync(h.data(), c->acc_d, c->acc_n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
@@ -736,6 +760,9 @@ extern "C" int f2q_read_counts(f2q_ctx *c, int64_t *counts, int64_t stats[5])
 extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 {
     if (!c || !dptr || !n_int64) return F2Q_EINVAL;
+    HIPC(c, hipSetDevice(c->device));
+    if (int rc = acc_ready(c)) return rc;            // (queued on the stream, as the reset's own clear used to be)
+    c->acc_eager = true;
     *dptr = c->acc_d; *n_int64 = c->acc_n;
     return F2Q_OK;
 }
@@ -1242,14 +1269,31 @@ static int slab_rows(f2q_ctx *c, size_t rows, size_t stat_rows, Accum &acc)
     acc.slab = c->slab_d; acc.stat_slab = c->stat_slab_d;
     return F2Q_OK;
 }
-// k_reduce_slabs: the launch's `rows` histogram rows and `stat_rows` stats rows into the accumulators
+// k_reduce_slabs: the launch's `rows` histogram rows and `stat_rows` stats rows into the accumulators.  Where a reset
+// left the clear pending the reduce stores and the clear is no work at all; the caller has made sure (acc_ready) that no
+// kernel queued since that reset has added to the accumulators
 static int reduce_slabs(f2q_ctx *c, const Accum &acc, uint32_t rows, uint32_t stat_rows, uint32_t &launches)
 {
     const uint32_t nf = c->lib_h.n_features;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(std::max<uint32_t>(1u, (nf + 63) / 64), F2Q_RED_SPLIT), dim3(256), 0, c->stream,
-                       c->slab_d, rows, nf, acc.counts, c->stat_slab_d, stat_rows, acc.stats);
+    const uint32_t store = c->acc_pending ? 1u : 0u;
+    // a workgroup per F2Q_RED_FEATS features, and one more for the five counters
+    hipLaunchKernelGGL(k_reduce_slabs, dim3((nf + F2Q_RED_FEATS - 1) / F2Q_RED_FEATS + 1u), dim3(256), 0, c->stream,
+                       c->slab_d, rows, nf, acc.counts, acc.carry, c->stat_slab_d, stat_rows, acc.stats, store);
     HIPC(c, hipGetLastError());
+    c->acc_pending = false;                          // (only now: a launch that failed has cleared nothing)
     launches++;
+    return F2Q_OK;
+}
+// hipFuncAttributeMaxDynamicSharedMemorySize of a kernel: set once per device and kernel, again only for a larger size
+static int dyn_lds(f2q_ctx *c, const void *kern, size_t shmem)
+{
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> set;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &have = set[{c->device, kern}];
+    if (shmem <= have) return F2Q_OK;
+    HIPC(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    have = shmem;
     return F2Q_OK;
 }
 static bool same_q(const RunDev &r) { return r.thr_up == r.thr && r.thr_down == r.thr; }
@@ -1361,9 +1405,10 @@ static int launch_anchor_lds(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint
     // (this path is taken with sameq only: the kernel has no SAMEQ = false instance)
     anchored_geom(pb.planar_nw, c->plan.kb, true, [&](auto NW, auto KB, auto) {
         auto kern = near ? k_count_anchor_lt<NW, KB, true, true> : k_count_anchor_lt<NW, KB, true, false>;
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        if ((rc = dyn_lds(c, (const void *)kern, shmem))) return;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_ALT_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
     });
+    if (rc) return rc;
     HIPC(c, hipGetLastError());
     launches++;
     return reduce_slabs(c, acc, grid, grid, launches);
@@ -1434,15 +1479,16 @@ static int launch_part(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32_t &
     const size_t shmem1 = (size_t)pw * P * F2Q_PS_RING * 8 + (size_t)(pw + 1) * P * 4;
     const size_t shmem2 = ((size_t)F2Q_LT_SLOTS + F2Q_LT_BUCKETS) * 4 + (near ? (size_t)cw * (F2Q_PC_RING * 8 + F2Q_PC_VIA * 4) : 0);
     auto kern2 = near ? k_part_count<true> : k_part_count<false>;
-    (void)hipFuncSetAttribute((const void *)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem2);
+    if ((rc = dyn_lds(c, (const void *)kern2, shmem2))) return rc;
     for (uint32_t t0 = 0; t0 < pb.n_tiles; t0 += chunk_tiles) {
         const uint32_t t1 = std::min<uint32_t>(pb.n_tiles, t0 + chunk_tiles);
         auto scatter = [&](auto PW) {
             auto k1 = fv == FV_A20 ? k_part_scatter<5, 2, true, PW> : fv == FV_SPEC52 ? k_part_scatter<5, 2, false, PW> : k_part_scatter<0, 0, false, PW>;
-            (void)hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem1);
+            if ((rc = dyn_lds(c, (const void *)k1, shmem1))) return;
             hipLaunchKernelGGL(k1, dim3(grid1), dim3(64 * PW), shmem1, c->stream, c->run_d, c->lib_d, pb, a1, ps, t0, t1);
         };
         if (pw == 16) scatter(int_c<16>()); else if (pw == 8) scatter(int_c<8>()); else scatter(int_c<4>());
+        if (rc) return rc;
         HIPC(c, hipGetLastError());
         hipLaunchKernelGGL(kern2, dim3(grid2), dim3(64 * cw), shmem2, c->stream, c->run_d, c->lib_d, a2, ps, c->pt_slab0_d, c->pt_slab1_d);
         HIPC(c, hipGetLastError());
@@ -1473,7 +1519,7 @@ static int launch_fixed_lds(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint3
     auto kern = mw ? fixed_lds_kernel<true>(near, fv) : fixed_lds_kernel<false>(near, fv);
     int rc = slab_rows(c, grid, grid, acc);
     if (rc) return rc;
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if ((rc = dyn_lds(c, (const void *)kern, shmem))) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_LT_THREADS), shmem, c->stream, c->run_d, c->lib_d, pb, acc);
     HIPC(c, hipGetLastError());
     launches++;
@@ -1506,7 +1552,7 @@ static int launch_fixed_packed(f2q_ctx *c, const PackedBlock &pb, Accum &acc, ui
     HIPC(c, hipGetLastError());
     launches++;
     if (!lds && nf) {
-        (void)hipFuncSetAttribute((const void *)k_hist_ranges, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(F2Q_HIST_RANGE * 4));
+        if ((rc = dyn_lds(c, (const void *)k_hist_ranges, (size_t)F2Q_HIST_RANGE * 4))) return rc;
         hipLaunchKernelGGL(k_hist_ranges, dim3(n_ranges * n_parts), dim3(1024), (size_t)F2Q_HIST_RANGE * 4, c->stream,
                            c->hit_buf_d, (uint64_t)pb.n_slots, nf, n_parts, c->slab_d);
         HIPC(c, hipGetLastError());
@@ -1779,7 +1825,15 @@ extern "C" int f2q_umi_pairs(f2q_ctx *c, uint64_t cap, uint64_t *n, uint32_t *fe
 static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, Accum &acc, uint32_t &launches)
 {
     int rc = F2Q_OK;
-    if (pb.n_tiles) switch (c->last_path = choose_path(c, pb)) {
+    if (pb.n_tiles) {
+        c->last_path = choose_path(c, pb);
+        // k_count_fixed4_lds and k_count_fixed4 meet the accumulators in k_reduce_slabs only, which consumes a pending
+        // clear by storing; the kernels of every other path add to them (if only for a read their slow routine decides)
+        const bool slab_only = c->prm.mode == 0 && c->lib_h.n_features &&
+                               (c->last_path == F2Q_PATH_FIXED_LDS || c->last_path == F2Q_PATH_MULTI_LDS || c->last_path == F2Q_PATH_FIXED_PACKED);
+        if (!slab_only && (rc = acc_ready(c))) return rc;
+    }
+    if (pb.n_tiles) switch (c->last_path) {
         case F2Q_PATH_PAIRS:        rc = launch_pairs(c, pb, acc, launches); break;
         case F2Q_PATH_ANCHOR:       rc = launch_anchor(c, pb, acc, launches); break;
         case F2Q_PATH_ANCHOR_LDS:   rc = launch_anchor_lds(c, pb, acc, launches); break;
@@ -1792,6 +1846,7 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
         default:                    rc = launch_fixed_v1(c, pb, acc, launches); break;
     }
     if (rc || !rbv.n) return rc;
+    if ((rc = acc_ready(c))) return rc;                          // the raw-record kernels add to the accumulators directly
     RawBlock rb = rbv;
     rb.first_index += c->reads_seen;
     const uint64_t wg = (rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS;
@@ -1946,7 +2001,7 @@ static int launch_hot(f2q_ctx *c, const PackedBlock &v, uint64_t slot_base, Accu
         uint32_t fgrid = std::min<uint32_t>(wgs, (uint32_t)c->n_cu);
         if (c->lt_max_wgs) fgrid = std::min<uint32_t>(fgrid, c->lt_max_wgs);
         auto kern = learning ? k_extract_fixed4_hot<true> : k_extract_fixed4_hot<false>;
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        if ((rc = dyn_lds(c, (const void *)kern, shmem))) return rc;
         hipLaunchKernelGGL(kern, dim3(fgrid), dim3(F2Q_FH_THREADS), shmem, c->stream, c->run_d, c->ec, c->hot, v, acc, c->reads_seen,
                            c->defer_d, slot_base, (uint64_t)c->defer_cap);
     } else {
@@ -1955,10 +2010,11 @@ static int launch_hot(f2q_ctx *c, const PackedBlock &v, uint64_t slot_base, Accu
         if (c->lt_max_wgs) grid = std::min<uint32_t>(grid, c->lt_max_wgs);
         anchored_geom(v.planar_nw, c->plan.kb, same_q(c->run_h), [&](auto NW, auto KB, auto SQ) {
             auto kern = learning ? k_extract_anchor_hot<NW, KB, SQ, true> : k_extract_anchor_hot<NW, KB, SQ, false>;
-            (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+            if ((rc = dyn_lds(c, (const void *)kern, shmem))) return;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_HOT_THREADS), shmem, c->stream, c->run_d, c->ec, c->hot, v, acc,
                                c->reads_seen, c->defer_d, slot_base, (uint64_t)c->defer_cap);
         });
+        if (rc) return rc;
     }
     HIPC(c, hipGetLastError());
     launches++;
@@ -2011,7 +2067,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
         return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_parts: a parts context counts raw records only");
     if (c->umi.hdr_sep && b->rb.n && !b->rb.hdr_umi) return fail(c, F2Q_ESTATE, "the block was made before f2q_set_umi_header (or without headers): its records carry no header UMI");
     c->counted = true;
-    Accum acc{c->acc_d, c->acc_d + (c->acc_n - 5), nullptr, nullptr, nullptr, nullptr};
+    Accum acc{c->acc_d, c->acc_d + (c->acc_n - 5), nullptr, nullptr, nullptr, nullptr, c->carry_d};
 #ifdef F2Q_STAMP
     static unsigned long long *stamp_d = nullptr;
     if (!stamp_d) { (void)hipMalloc((void **)&stamp_d, 64); (void)hipMemset(stamp_d, 0, 64); }
@@ -2024,6 +2080,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
         int rc = launch_view(c, b->pb, b->rb, acc, launches);
         if (rc) return rc;
     } else if (b->n_reads) {
+        if (int rc = acc_ready(c)) return rc;            // every Extract+Count kernel adds its five counters directly
         // Extract+Count: the tables must have room for "every read of the launch is a new key".  Sizing them for the
         // whole block (50 M reads -> 2^28 slots) makes the table many GiB and every probe a DRAM access, so the block
         // is walked in steps of F2Q_EC_STEP reads: room for one step beyond the keys already there is enough, and the
@@ -3902,6 +3959,7 @@ extern "C" int f2q_ec_assign(f2q_ctx *c, int64_t *counts, int64_t stats[5], f2q_
     }
     HIPC(c, hipEventRecord(c->ev_k1, c->stream));
     // reads and quality_failed are the context's own (fast2q.py:389-393 do not depend on the library)
+    if (int rc = acc_ready(c)) return rc;
     HIPC(c, hipMemcpyAsync(st_d + F2Q_READS, c->acc_d + (c->acc_n - 5) + F2Q_READS, 8, hipMemcpyDeviceToDevice, c->stream));
     HIPC(c, hipMemcpyAsync(st_d + F2Q_QUALITY_FAILED, c->acc_d + (c->acc_n - 5) + F2Q_QUALITY_FAILED, 8, hipMemcpyDeviceToDevice, c->stream));
     std::vector<unsigned long long> h(nf + 6);

@@ -254,6 +254,9 @@ int f2q_synth_library(uint64_t seed, uint32_t n, uint32_t length, char *out);
 int f2q_set_read_base(f2q_ctx *ctx, uint64_t first_read_index);
 
 /* ---- results -------------------------------------------------------------------------------- */
+/* A new job: every result reads zero from here on.  No host synchronisation.  The clear of counts + stats is left to
+ * whatever touches them next on the context's stream (the step's first slab reduce stores over them instead); once
+ * f2q_counts_device_ptr has handed the raw pointer out, the clear is queued here and now. */
 int f2q_reset_counts(f2q_ctx *ctx);
 /* Counter mode: counts[n_features] + stats[5] (device -> host, synchronises the stream). */
 int f2q_read_counts(f2q_ctx *ctx, int64_t *counts, int64_t stats[5]);
