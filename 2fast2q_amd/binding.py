@@ -29,6 +29,7 @@ EXPORTS = (
     "f2q_set_strand", "f2q_read_strands",
     "f2q_set_parts", "f2q_parts_info", "f2q_read_parts", "f2q_parts_recombinants",
     "f2q_set_stagger", "f2q_read_stagger",
+    "f2q_set_indel", "f2q_read_indels",
 )
 
 STRANDS = ("fwd", "rev", "both")            # F2Q_STRAND_FWD / _REV / _BOTH
@@ -197,6 +198,8 @@ def load(path=None):
     L.f2q_set_parts.argtypes = [vp]
     L.f2q_set_stagger.argtypes = [vp, C.c_int32]
     L.f2q_read_stagger.argtypes = [vp, i64p, i64p, C.c_int32]
+    L.f2q_set_indel.argtypes = [vp, C.c_int32]
+    L.f2q_read_indels.argtypes = [vp, i64p, i64p, i64p, i64p, C.c_int32, i64p]
     L.f2q_parts_info.argtypes = [vp, u32p, u32p]
     L.f2q_read_parts.argtypes = [vp, i64p, i64p, i64p, i64p]
     L.f2q_parts_recombinants.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), u32p, u32p, u32p]
@@ -301,10 +304,16 @@ class Counter:
     wins, else the earliest start within ``miss``.  Counter mode, single reads, one ``start``, no UMIs, sample barcodes,
     strand mode or parts; ``read_stagger()`` returns the reads assigned perfectly / imperfectly at each offset.  0: a plain
     context.
+
+    ``indel=True`` reports the reads whose feature carries one inserted or deleted base (f2q_set_indel): a read the plain rule
+    assigns nothing is tried as a one-base deletion and as a one-base insertion of every feature of exactly ``length`` bases.
+    Counts and the five counters stay what they are without it.  Counter mode, single reads, one ``start``, ``length`` 2 .. 31,
+    no UMIs, sample barcodes, strand mode, parts or stagger; ``read_indels()`` returns the deletion and insertion reads per
+    feature and per position and the four totals.
     """
 
     def __init__(self, features=None, lib_path=None, start2=None, rc2=False, umi=None, umi_reads=False, umi_paired=None, umi_header=None,
-                 sample_barcodes=None, barcode_mismatch=0, strand="fwd", parts=False, stagger=0, **params):
+                 sample_barcodes=None, barcode_mismatch=0, strand="fwd", parts=False, stagger=0, indel=False, **params):
         self._L = load(lib_path)
         self._p, self._keep = make_params(**params)
         self.mode = "C" if self._p.mode == 0 else "EC"
@@ -326,6 +335,7 @@ class Counter:
         self.strand = "fwd"              # the strand mode of the context (set_strand)
         self.parts = False               # each part of a pair library matched alone (set_parts)
         self.stagger = 0                 # extra starts the window is tried at (set_stagger)
+        self.indel = False               # one-base insertions and deletions are reported (set_indel)
         try:
             self.set_strand(strand)
             if sample_barcodes is not None:
@@ -346,6 +356,8 @@ class Counter:
                 self.set_parts()
             if stagger:
                 self.set_stagger(stagger)
+            if indel:
+                self.set_indel(True)
         except BaseException:
             self.close()
             raise
@@ -464,6 +476,20 @@ class Counter:
         out = [np.zeros(self.stagger + 1, dtype=np.int64) for _ in range(2)]
         i64p = C.POINTER(C.c_int64)
         self._check(self._L.f2q_read_stagger(self._h, out[0].ctypes.data_as(i64p), out[1].ctypes.data_as(i64p), self.stagger + 1))
+        return tuple(out)
+
+    def set_indel(self, on=True):
+        """report reads whose feature carries one inserted or deleted base (f2q_set_indel); before counting; False clears it"""
+        self._check(self._L.f2q_set_indel(self._h, 1 if on else 0))
+        self.indel = bool(on)
+
+    def read_indels(self):
+        """(del_counts[n_features], ins_counts[n_features], del_pos[L], ins_pos[L], totals[4]) as int64 arrays
+        (f2q_read_indels); totals = reads tried, deletion reads, insertion reads, ambiguous reads"""
+        L = int(self._p.length)
+        out = [np.zeros(n, dtype=np.int64) for n in (self.n_features, self.n_features, L, L, 4)]
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.f2q_read_indels(self._h, *(a.ctypes.data_as(i64p) for a in out[:4]), L, out[4].ctypes.data_as(i64p)))
         return tuple(out)
 
     def parts_info(self):

@@ -3141,4 +3141,137 @@ F2Q_HD int stagger_read(const RunDev &run, const LibDev &lib, const StaggerDev &
     return v0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// one-base insertions and deletions inside the feature (f2q_set_indel): reads the plain rule leaves unassigned
+// ---------------------------------------------------------------------------------------------
+// The rule is stated in include/f2q.h (indel_verdict).  V0 is general_read, unchanged; a read it assigns nothing is tried
+// against the candidates (the regular features of length group L = run.length): the deletion window of L - 1 bases is ONE
+// probe of the host-built variant table (indel_build, f2q_host.h), the insertion window of L + 1 bases is up to L
+// lib_exact probes with one base removed.  Both come from three registers: the 2-bit codes of [s, s + L + 1) (L + 1 <= 32
+// bases in one u64; a non-ACGT symbol stored as 0), one bit per non-ACGT symbol and one per quality byte that fails.
+// A staged record builds them with stagger_span, any other byte by byte through the accessor: one decision routine.
+#define F2Q_INDEL_NOT_TRIED (-1)     // the plain rule assigned the read
+#define F2Q_INDEL_NONE 0             // tried, no candidate
+#define F2Q_INDEL_DEL 1
+#define F2Q_INDEL_INS 2
+#define F2Q_INDEL_AMBIGUOUS 3        // two or more candidates
+#define F2Q_INDEL_TOTALS 4           // tried, deletions, insertions, ambiguous
+#define F2Q_INDEL_SHARED (~0ull)     // value of a variant two features share
+#define F2Q_INDEL_NOBODY 0xFFFFFFFFu
+struct IndelDev {
+    const uint64_t *var_keys;        // deletion-variant table: 2-bit code of the L - 1 bases of a variant, KEY_EMPTY = free
+    const uint64_t *var_vals;        // (feature << 8) | smallest removed position, or F2Q_INDEL_SHARED
+    uint32_t var_bits, pad;          // 1 << var_bits slots
+    unsigned long long *del_counts, *ins_counts;   // [n_features]
+    unsigned long long *del_pos, *ins_pos;         // [L]
+    unsigned long long *totals;                    // [F2Q_INDEL_TOTALS]
+};
+F2Q_HD uint64_t indel_low2(int n) { return n >= 32 ? ~0ull : (1ull << (2 * n)) - 1ull; }
+// the key of the L bases that stay when base p (0 <= p <= 30) leaves the L + 1 bases of w
+F2Q_HD uint64_t indel_removed(uint64_t w, int p, int L)
+{
+    return ((w & indel_low2(p)) | ((w >> (2 * (p + 1))) << (2 * p))) & indel_low2(L);
+}
+// positions [s, s + lim) of a record where it lies: what stagger_span gives for a staged one (lim <= 32)
+template <class P>
+F2Q_HD void indel_span_bytes(P seq, P qual, int s, int lim, int thr, uint64_t &w, uint64_t &nmask, uint64_t &qmask)
+{
+    w = 0; nmask = 0; qmask = 0;
+    for (int p = 0; p < lim; p++) {
+        uint32_t c = base_code(up8(seq[s + p]));
+        if (c > 3u) { nmask |= 1ull << p; c = 0; }
+        w |= (uint64_t)c << (2 * p);
+        if (q_fails(qual[s + p], thr)) qmask |= 1ull << p;
+    }
+}
+#define F2Q_INDEL_BATCH 4            // insertion probes whose first loads are in flight together
+// the trial of one unassigned read from its registers; lim = bases and quality bytes present from s on, at most L + 1
+F2Q_HD int indel_decide(const LibDev &lib, const IndelDev &d, int L, int lim, uint64_t w, uint64_t nmask, uint64_t qmask, uint32_t &id, int &pos)
+{
+    uint32_t fd = F2Q_INDEL_NOBODY, fi = F2Q_INDEL_NOBODY; int pd = 0, pi = 0;
+    if (lim >= L - 1 && d.var_keys && ((nmask | qmask) & ((1ull << (L - 1)) - 1ull)) == 0) {          // the deletion window: one probe
+        const uint64_t key = w & indel_low2(L - 1);
+        const uint32_t m = (1u << d.var_bits) - 1u;
+        const auto keys = gp(d.var_keys);
+        uint32_t s = hash_slot(key, d.var_bits);
+        for (;;) {
+            const uint64_t k = keys[s];
+            if (k == key) {
+                const uint64_t v = gp(d.var_vals)[s];
+                if (v == F2Q_INDEL_SHARED) return F2Q_INDEL_AMBIGUOUS;
+                fd = (uint32_t)(v >> 8); pd = (int)(v & 255u);
+                break;
+            }
+            if (k == KEY_EMPTY) break;
+            s = (s + 1u) & m;
+        }
+    }
+    const LenGroup &g = lib.grp[L];
+    const uint64_t wm = (1ull << (L + 1)) - 1ull, nm = nmask & wm;
+    if (lim >= L + 1 && g.n != 0 && (qmask & wm) == 0 && (nm & (nm - 1ull)) == 0) {                      // the insertion window: up to L probes
+        const uint32_t m = (1u << g.exact.bits) - 1u;
+        const auto tab_keys = gp(lib.tab_keys) + g.exact.off;
+        int hits = 0;
+        for (int p0 = 0; p0 < L && hits < 2; p0 += F2Q_INDEL_BATCH) {
+            uint64_t key[F2Q_INDEL_BATCH], k0[F2Q_INDEL_BATCH];
+            uint32_t slot[F2Q_INDEL_BATCH];
+#pragma unroll
+            for (int j = 0; j < F2Q_INDEL_BATCH; j++) {
+                const int p = p0 + j;
+                // one non-ACGT byte: it is the inserted one or nothing is; else a base equal to the one before it gives
+                // the key again and the smaller p stands
+                const bool live = p < L && (nm ? ((nm >> p) & 1ull) != 0 : (p == 0 || ((w >> (2 * p)) & 3ull) != ((w >> (2 * p - 2)) & 3ull)));
+                key[j] = live ? indel_removed(w, p, L) : 0;
+                slot[j] = hash_slot(key[j], g.exact.bits);
+                k0[j] = live ? tab_keys[slot[j]] : KEY_EMPTY;
+            }
+#pragma unroll
+            for (int j = 0; j < F2Q_INDEL_BATCH; j++) {
+                uint64_t k = k0[j]; uint32_t s = slot[j];
+                while (hits < 2 && k != KEY_EMPTY) {
+                    if (k == key[j]) {
+                        const uint32_t f = gp(lib.tab_idx)[g.exact.off + s];
+                        if (hits == 0) { fi = f; pi = p0 + j; hits = 1; }
+                        else if (f != fi) hits = 2;                                  // a second distinct feature: nothing more to learn
+                        break;
+                    }
+                    s = (s + 1u) & m;
+                    k = tab_keys[s];
+                }
+            }
+        }
+        if (hits == 2) return F2Q_INDEL_AMBIGUOUS;
+    }
+    if (fi != F2Q_INDEL_NOBODY && fd != F2Q_INDEL_NOBODY && fi != fd) return F2Q_INDEL_AMBIGUOUS;
+    if (fi != F2Q_INDEL_NOBODY) { id = fi; pos = pi; return F2Q_INDEL_INS; }
+    if (fd != F2Q_INDEL_NOBODY) { id = fd; pos = pd; return F2Q_INDEL_DEL; }
+    return F2Q_INDEL_NONE;
+}
+// One record of an indel context: a lane of k_count_indel.  sw / qw: the words the two lines are staged in (their bytes at
+// offsets ms / mq), or nullptr: the record is read where it lies (gseq / gqual).  The plain verdict goes into counts and
+// st[] as general_read leaves it; returns F2Q_INDEL_* with the feature in id and the position in pos.
+template <class G>
+F2Q_HD int indel_read(const RunDev &run, const LibDev &lib, const EcDev &ec, const Accum &acc, const IndelDev &d,
+                      const uint32_t *sw, const uint32_t *qw, uint32_t ms, uint32_t mq, G gseq, G gqual, int r, int qn,
+                      unsigned long long read_index, unsigned long long st[5], uint32_t &id, int &pos)
+{
+    unsigned long long one[5] = {0, 0, 0, 0, 0};
+    if (sw) general_read<const uint8_t *, true, false>(run, lib, ec, acc, reinterpret_cast<const uint8_t *>(sw) + ms, r,
+                                                       reinterpret_cast<const uint8_t *>(qw) + mq, qn, read_index, one);
+    else general_read<G, true, false>(run, lib, ec, acc, gseq, r, gqual, qn, read_index, one);
+#pragma unroll
+    for (int k = 0; k < 5; k++) st[k] += one[k];
+    if (one[1] | one[2]) return F2Q_INDEL_NOT_TRIED;
+    const int s = run.start[0], L = run.length;
+    const int have = (r < qn ? r : qn) - s;
+    const int lim = have < 0 ? 0 : have > L + 1 ? L + 1 : have;
+    uint64_t w, nmask, qmask;
+    if (sw) {
+        StaggerSpan sp;
+        stagger_span(sw, qw, ms, mq, s, lim, run.thr, sp);
+        w = sp.lo; nmask = sp.nmask; qmask = sp.qmask;
+    } else indel_span_bytes(gseq, gqual, s, lim, run.thr, w, nmask, qmask);
+    return indel_decide(lib, d, L, lim, w, nmask, qmask, id, pos);
+}
+
 } // namespace f2q

@@ -860,4 +860,49 @@ inline void parts_build(PartsTable &t)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// one-base deletions (f2q_set_indel): the deletion-variant table of the candidates
+// ---------------------------------------------------------------------------------------------
+// The candidates are the regular features of exactly L bases (a repeated sequence stays with its first feature, as the
+// exact hit of the plain rule does).  A variant is the L - 1 bases left when base p leaves a candidate; the variant that
+// equals the candidate's own first L - 1 bases is left out (it cannot be told from a substitution of the last base).
+// Open addressing like the library tables, at most half full: key = the variant's 2-bit code (at most 60 bits, so never
+// KEY_EMPTY), value = (feature << 8) | the smallest p, or F2Q_INDEL_SHARED when two candidates share the variant.
+struct IndelTable {
+    std::vector<uint64_t> keys, vals;
+    uint32_t bits = 0;
+    uint64_t candidates = 0, variants = 0, shared = 0;       // features taking part, distinct variants held, of those shared
+};
+inline void indel_build(const HostIndex &ix, int L, IndelTable &t)
+{
+    t = IndelTable();
+    std::vector<uint32_t> cand;
+    if (L >= 2 && L <= F2Q_REG_MAXLEN && ix.grp[L].n) {
+        const LenGroup &g = ix.grp[L];
+        const uint32_t m = (1u << g.exact.bits) - 1u;
+        for (uint32_t f = 0; f < ix.n_features; f++) {
+            uint64_t k;
+            if (ix.feat_off[f + 1] - ix.feat_off[f] != (uint32_t)L || !feature_key(ix.feat_bytes.data() + ix.feat_off[f], (uint32_t)L, k)) continue;
+            uint32_t s = hash_slot(k, g.exact.bits);
+            while (ix.tab_keys[g.exact.off + s] != k) s = (s + 1u) & m;      // (every candidate is in its group's exact table)
+            if (ix.tab_idx[g.exact.off + s] == f) cand.push_back(f);
+        }
+    }
+    t.candidates = cand.size();
+    t.bits = table_bits((uint32_t)std::min<uint64_t>((uint64_t)cand.size() * (uint64_t)(L > 0 ? L : 1), 0x40000000ull));
+    t.keys.assign((size_t)1 << t.bits, KEY_EMPTY); t.vals.assign((size_t)1 << t.bits, 0ull);
+    const uint32_t m = (1u << t.bits) - 1u;
+    for (uint32_t f : cand) {
+        const uint64_t k = ix.key2[f], own = k & indel_low2(L - 1);
+        for (int p = 0; p < L; p++) {
+            const uint64_t v = indel_removed(k, p, L - 1);
+            if (v == own) continue;
+            uint32_t s = hash_slot(v, t.bits);
+            while (t.keys[s] != KEY_EMPTY && t.keys[s] != v) s = (s + 1u) & m;
+            if (t.keys[s] == KEY_EMPTY) { t.keys[s] = v; t.vals[s] = ((uint64_t)f << 8) | (uint64_t)p; t.variants++; }
+            else if (t.vals[s] != F2Q_INDEL_SHARED && (uint32_t)(t.vals[s] >> 8) != f) { t.vals[s] = F2Q_INDEL_SHARED; t.shared++; }
+        }
+    }
+}
+
 } // namespace f2q

@@ -37,6 +37,7 @@ using namespace f2q;
 #include "f2q_demux_kernels.h"
 #include "f2q_strand_kernels.h"
 #include "f2q_stagger_kernels.h"
+#include "f2q_indel_kernels.h"
 #include "f2q_parts_kernels.h"
 
 // ===============================================================================================
@@ -158,6 +159,15 @@ struct f2q_ctx {
         std::vector<void *> allocs;      // the two histograms, one allocation of 2 * (n + 1) words
         bool env_general = false;        // what F2Q_FORCE_GENERAL said before the context was sent down the raw-record road
     } stagger;
+    // one-base insertions and deletions (f2q_set_indel): the deletion-variant table, the per-feature counts, the two position
+    // histograms and the four totals; built once the flag and a library are both known (indel_install)
+    struct {
+        bool on = false;
+        IndelDev dev{};
+        std::vector<void *> allocs;      // the table's two arrays; the counters, one allocation of `words` words
+        uint64_t words = 0;              // 2 * max(n_features, 1) + 2 * L + 4
+        bool env_general = false;        // what F2Q_FORCE_GENERAL said before the context was sent down the raw-record road
+    } indel;
     // pair libraries with each part matched alone (f2q_set_parts): the two part libraries (indices of their own, as the
     // assign library has one), the pair table, parts_counts / the marginals / the six class counters (one allocation) and
     // the recombinant set, which outlives the pieces of a file; parts_reserve sizes it before every launch
@@ -553,6 +563,41 @@ static int strand_alloc(f2q_ctx *c)
     return F2Q_OK;
 }
 
+// ---- one-base insertions and deletions: the variant table and the counters -----------------------------------------------
+static void indel_drop(f2q_ctx *c)
+{
+    free_all(c, c->indel.allocs);
+    c->indel.dev = IndelDev{}; c->indel.words = 0;
+}
+
+// The deletion-variant table of the context's library and zeroed counters, built next to what the context holds and
+// swapped in at the end: a failure leaves the context as it was.  Without a library there is nothing to build yet.
+static int indel_install(f2q_ctx *c, bool lib_known)
+{
+    if (!c->indel.on || !lib_known) return F2Q_OK;
+    const int L = c->run_h.length;
+    const uint64_t nf = std::max<uint64_t>(c->ix.n_features, 1);
+    if ((uint64_t)c->ix.grp[L].n * (uint64_t)L > 0x40000000ull) return fail(c, F2Q_ENOMEM, "f2q_set_indel: the deletion-variant table of " + std::to_string(c->ix.grp[L].n) + " features is not built");
+    IndelTable t;
+    indel_build(c->ix, L, t);
+    std::vector<void *> owner; IndelDev d{};
+    uint64_t *keys = nullptr, *vals = nullptr; unsigned long long *w = nullptr;
+    const uint64_t words = 2 * nf + 2 * (uint64_t)L + F2Q_INDEL_TOTALS;
+    if (dev_upload(c, t.keys.data(), t.keys.size(), &keys, owner) || dev_upload(c, t.vals.data(), t.vals.size(), &vals, owner) ||
+        dev_alloc(c, (size_t)words, &w, owner, 0)) {
+        free_all(c, owner);
+        return fail(c, F2Q_ENOMEM, "no device memory for the deletion-variant table (" + std::to_string(t.keys.size()) + " slots) and the indel counters: " + c->err);
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));                    // (the uploads read t)
+    indel_drop(c);
+    d.var_keys = keys; d.var_vals = vals; d.var_bits = t.bits;
+    d.del_counts = w; d.ins_counts = w + nf; d.del_pos = w + 2 * nf; d.ins_pos = w + 2 * nf + L; d.totals = w + 2 * nf + 2 * L;
+    c->indel.dev = d; c->indel.allocs = owner; c->indel.words = words;
+    if (c->trace) fprintf(stderr, "[f2q trace] indel: every read takes k_count_indel; deletion-variant table %zu slots (%llu variants of %llu candidates, %llu shared)\n",
+                          t.keys.size(), (unsigned long long)t.variants, (unsigned long long)t.candidates, (unsigned long long)t.shared);
+    return F2Q_OK;
+}
+
 // ---- pair libraries, each part matched alone: tables, counters and the recombinant set ---------------------------------
 // everything given back: f2q_destroy, and a new library
 static void parts_drop(f2q_ctx *c)
@@ -640,6 +685,7 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     if (c->trace && c->parts.on) fprintf(stderr, "[f2q trace] recombinant set: %llu slots, %llu rehashes\n", (unsigned long long)c->parts.n_slots, (unsigned long long)c->parts.rehashes);
     parts_drop(c);
     free_all(c, c->stagger.allocs);
+    indel_drop(c);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
@@ -703,6 +749,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (c->strand.mode) { strand_drop(c); if ((rc = strand_alloc(c))) return rc; }  // ... and reverse-strand counts that start afresh
     if (c->parts.on && (rc = parts_install(c, seqs ? seqs : "", offs, n))) return rc;   // ... and part libraries, a pair table and a set of its own
     if (c->stagger.n) HIPC(c, hipMemsetAsync(c->stagger.dev.hist, 0, 2 * ((size_t)c->stagger.n + 1) * sizeof(unsigned long long), c->stream));   // ... and offsets that start afresh
+    if (c->indel.on && (rc = indel_install(c, true))) return rc;      // ... and a variant table and indel counters of its own
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
     // symbol of any feature), every other odd symbol still sends the read to the byte-exact routine
@@ -731,6 +778,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
     if (c->strand.mode && c->strand.dev.rev_counts) HIPC(c, hipMemsetAsync(c->strand.dev.rev_counts, 0, c->strand.words * sizeof(unsigned long long), c->stream));
     if (c->parts.on && c->parts.dev.counts) if (int rc = parts_clear(c)) return rc;
     if (c->stagger.n) HIPC(c, hipMemsetAsync(c->stagger.dev.hist, 0, 2 * ((size_t)c->stagger.n + 1) * sizeof(unsigned long long), c->stream));
+    if (c->indel.on && c->indel.dev.del_counts) HIPC(c, hipMemsetAsync(c->indel.dev.del_counts, 0, c->indel.words * sizeof(unsigned long long), c->stream));
     c->reads_seen = 0;
     c->ec_gen++;
     // no host synchronisation: the clear is ordered on the context's stream like every launch and read-back after it
@@ -768,6 +816,7 @@ extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 }
 
 // ---- distinct UMIs per feature: the ABI ---------------------------------------------------------------------------
+static const char *const INDEL_NO_UMI = "an indel context (f2q_set_indel) takes no UMIs: the two are not combined";
 static const char *const STAGGER_NO_UMI = "a stagger context (f2q_set_stagger) takes no UMIs: the two are not combined";
 static const char *const STRAND_NO_UMI = "a context with a strand mode (f2q_set_strand: rev / both) takes no UMIs: the two are not combined";
 static const char *const PARTS_NO_UMI = "a parts context (f2q_set_parts) takes no UMIs: the two are not combined";
@@ -790,6 +839,7 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
     if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
+    if (c->indel.on) return fail(c, F2Q_ESTATE, INDEL_NO_UMI);
     if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
     if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
@@ -809,6 +859,7 @@ extern "C" int f2q_set_umi_header(f2q_ctx *c, int32_t sep, int32_t length)
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
     if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
+    if (c->indel.on) return fail(c, F2Q_ESTATE, INDEL_NO_UMI);
     if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_header comes once, in place of f2q_set_umi / f2q_set_umi_paired and before counting");
     const bool alnum = (sep >= '0' && sep <= '9') || (sep >= 'A' && sep <= 'Z') || (sep >= 'a' && sep <= 'z');
@@ -831,6 +882,7 @@ extern "C" int f2q_set_umi_paired(f2q_ctx *c, int32_t start1, int32_t length1, i
     if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
     if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
     if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
+    if (c->indel.on) return fail(c, F2Q_ESTATE, INDEL_NO_UMI);
     if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
     if (!c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a paired context: call f2q_set_mate2 first (single reads: f2q_set_umi)");
     if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired comes once, after f2q_set_mate2 and before counting");
@@ -880,6 +932,7 @@ extern "C" int f2q_set_sample_barcodes(f2q_ctx *c, const char *seqs, uint32_t n,
     if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a UMI context: sample barcodes and UMIs are not combined");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
     if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a stagger context (f2q_set_stagger): the two are not combined");
+    if (c->indel.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on an indel context (f2q_set_indel): the two are not combined");
     if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a parts context (f2q_set_parts): the two are not combined");
     if (c->demux.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes comes once, after f2q_create and before counting");
     std::string up, err;
@@ -939,6 +992,7 @@ extern "C" int f2q_set_strand(f2q_ctx *c, int32_t mode)
     if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
     if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a parts context (f2q_set_parts): the two are not combined");
     if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a stagger context (f2q_set_stagger): the two are not combined");
+    if (c->indel.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on an indel context (f2q_set_indel): the two are not combined");
     if (c->strand.mode || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) comes once, after f2q_create and before counting");
     HIPC(c, hipSetDevice(c->device));
     c->strand.mode = mode; c->strand.dev = StrandDev{}; c->strand.dev.mode = mode;
@@ -1000,6 +1054,7 @@ extern "C" int f2q_set_stagger(f2q_ctx *c, int32_t n)
     if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
     if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a parts context (f2q_set_parts): the two are not combined");
+    if (c->indel.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on an indel context (f2q_set_indel): the two are not combined");
     HIPC(c, hipSetDevice(c->device));
     unsigned long long *w = nullptr; std::vector<void *> owner;
     if (dev_alloc(c, 2 * ((size_t)n + 1), &w, owner, 0)) {
@@ -1035,6 +1090,66 @@ extern "C" int f2q_read_stagger(f2q_ctx *c, int64_t *perfect, int64_t *imperfect
     return F2Q_OK;
 }
 
+// ---- one-base insertions and deletions: the ABI (include/f2q.h) ---------------------------------------------------------
+extern "C" int f2q_set_indel(f2q_ctx *c, int32_t on)
+{
+    if (!c) return F2Q_EINVAL;
+    if (!on && !c->indel.on) return F2Q_OK;                  // a plain context stays one: accepted at any time
+    if (c->counted) return fail(c, F2Q_ESTATE, "f2q_set_indel comes before counting");
+    if (!on) {                                               // a plain context again
+        HIPC(c, hipSetDevice(c->device));
+        indel_drop(c);
+        c->indel.on = false;
+        c->force_general = c->indel.env_general;
+        return stagger_replan(c);
+    }
+    if (c->indel.on) return F2Q_OK;
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_indel takes a Counter context: Extract+Count with indel reads is not implemented");
+    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_indel takes single reads: a paired context (f2q_set_mate2) is not examined for indels");
+    if (!c->run_h.fixed) return fail(c, F2Q_ESTATE, "f2q_set_indel takes a fixed window (--st): an anchored run (--us/--ds) finds its window itself");
+    if (c->run_h.n_iter != 1) return fail(c, F2Q_ESTATE, "f2q_set_indel takes exactly one window (--st with one value), not " + std::to_string(c->run_h.n_iter));
+    if (c->run_h.start[0] < 0) return fail(c, F2Q_ESTATE, "f2q_set_indel takes a window that starts at or after the first base (--st >= 0)");
+    if (c->run_h.length < 2 || c->run_h.length > F2Q_REG_MAXLEN) return fail(c, F2Q_ESTATE, "f2q_set_indel takes a window length (--l) of 2 .. 31 bases, not " + std::to_string(c->run_h.length));
+    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_indel on a UMI context: indel reads and UMIs are not combined");
+    if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_indel on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
+    if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_indel on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
+    if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_indel on a parts context (f2q_set_parts): the two are not combined");
+    if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_indel on a stagger context (f2q_set_stagger): the two are not combined");
+    HIPC(c, hipSetDevice(c->device));
+    c->indel.on = true;
+    if (int rc = indel_install(c, c->have_lib)) { c->indel.on = false; return rc; }
+    c->indel.env_general = c->force_general;
+    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
+    c->force_general = true;
+    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
+    c->plan.inband_n = false; c->plan.n_only = false;
+    if (c->trace && !c->have_lib) fprintf(stderr, "[f2q trace] indel: every read takes k_count_indel; the deletion-variant table is built with the library\n");
+    return F2Q_OK;
+}
+
+extern "C" int f2q_read_indels(f2q_ctx *c, int64_t *del_counts, int64_t *ins_counts, int64_t *del_pos, int64_t *ins_pos, int32_t n_pos, int64_t totals[4])
+{
+    if (!c) return F2Q_EINVAL;
+    if (!c->indel.on) return fail(c, F2Q_ESTATE, "not an indel context: call f2q_set_indel first");
+    const int32_t L = c->run_h.length;
+    if (n_pos != L) return fail(c, F2Q_EINVAL, "f2q_read_indels takes n_pos = L = " + std::to_string(L) + ", not " + std::to_string(n_pos));
+    HIPC(c, hipSetDevice(c->device));
+    const uint64_t nf = c->have_lib ? c->ix.n_features : 0, nfw = std::max<uint64_t>(nf, 1);
+    std::vector<unsigned long long> h((size_t)(2 * nfw + 2 * (uint64_t)L + F2Q_INDEL_TOTALS), 0ull);
+    if (c->indel.dev.del_counts) HIPC(c, hipMemcpyAsync(h.data(), c->indel.dev.del_counts, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    for (uint64_t f = 0; f < nf; f++) {
+        if (del_counts) del_counts[f] = (int64_t)h[f];
+        if (ins_counts) ins_counts[f] = (int64_t)h[nfw + f];
+    }
+    for (int32_t p = 0; p < L; p++) {
+        if (del_pos) del_pos[p] = (int64_t)h[2 * nfw + p];
+        if (ins_pos) ins_pos[p] = (int64_t)h[2 * nfw + L + p];
+    }
+    if (totals) for (int k = 0; k < F2Q_INDEL_TOTALS; k++) totals[k] = (int64_t)h[2 * nfw + 2 * L + k];
+    return F2Q_OK;
+}
+
 // ---- pair libraries, each part matched alone: the ABI (include/f2q.h) -------------------------------------------------
 extern "C" int f2q_set_parts(f2q_ctx *c)
 {
@@ -1048,6 +1163,7 @@ extern "C" int f2q_set_parts(f2q_ctx *c)
     if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_parts on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
     if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_parts on a stagger context (f2q_set_stagger): the two are not combined");
+    if (c->indel.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on an indel context (f2q_set_indel): the two are not combined");
     if (c->parts.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_parts comes once, after f2q_create (and f2q_set_mate2) and before counting");
     HIPC(c, hipSetDevice(c->device));
     { const char *e = getenv("F2Q_PARTS_SLOTS"); if (e && atol(e) > 0) { c->parts.min_slots = 2; while (c->parts.min_slots < (uint64_t)atol(e) && c->parts.min_slots < (1ull << 32)) c->parts.min_slots <<= 1; } }
@@ -1910,6 +2026,15 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
         EC_POINT(c, "k_count_stagger");
         return F2Q_OK;
     }
+    if (c->indel.on) {                                           // the same road with the indel trial of the unassigned reads (f2q_set_indel)
+        if (!c->indel.dev.del_counts && (rc = indel_install(c, true))) return rc;      // (only after an allocation that failed: a retry)
+        if (!c->indel.dev.del_counts) return fail(c, F2Q_ESTATE, "an indel context without its table: f2q_set_features failed");
+        hipLaunchKernelGGL(k_count_indel, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->indel.dev);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, "k_count_indel");
+        return F2Q_OK;
+    }
     if (c->parts.on) {                                           // the same road with the part verdicts, the tables and the recombinant set (f2q_set_parts)
         if (!c->parts.dev.counts) return fail(c, F2Q_ESTATE, "a parts context without its tables: f2q_set_features failed");
         if ((rc = parts_reserve(c, rb.n))) return rc;
@@ -2061,6 +2186,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
     if (c->prm.mode == 0 && !c->have_lib) return fail(c, F2Q_ESTATE, "f2q_set_features must be called before counting in Counter mode");
     if (c->umi.on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
     if (c->stagger.n && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_stagger: a stagger context counts single raw records only");
+    if (c->indel.on && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_indel: an indel context counts single raw records only");
     if (c->strand.mode && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_strand: a context with a strand mode counts single raw records only");
     if (c->demux.on && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_sample_barcodes: a demultiplexing context counts single raw records only");
     if (c->parts.on && (b->pb.n_tiles || (b->rb.n && (b->rb.len1 != nullptr) != (c->n_mate1 != 0))))
@@ -2592,6 +2718,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
     if (c->demux.on) return fail(c, F2Q_ESTATE, "a demultiplexing context (f2q_set_sample_barcodes) counts single reads only");
     if (c->strand.mode) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts single reads only");
     if (c->stagger.n) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts single reads only");
+    if (c->indel.on) return fail(c, F2Q_ESTATE, "an indel context (f2q_set_indel) counts single reads only");
     if (c->parts.on) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) keeps its windows: f2q_set_mate2 comes first, then f2q_set_parts");
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
@@ -3272,6 +3399,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
     if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
     if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
     if (c->stagger.n && world > 1) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts whole files: the offset histograms of several ranks are not merged");
+    if (c->indel.on && world > 1) return fail(c, F2Q_ESTATE, "an indel context (f2q_set_indel) counts whole files: the indel counts of several ranks are not merged");
     if (c->parts.on && world > 1) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) counts whole files: the tables and sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     size_t CH = file_chunk_bytes((size_t)256 << 20);
@@ -3560,6 +3688,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
     if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
     if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
     if (c->stagger.n && world > 1) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts whole files: the offset histograms of several ranks are not merged");
+    if (c->indel.on && world > 1) return fail(c, F2Q_ESTATE, "an indel context (f2q_set_indel) counts whole files: the indel counts of several ranks are not merged");
     if (c->parts.on && world > 1) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) counts whole files: the tables and sets of several ranks are not merged");
     HIPC(c, hipSetDevice(c->device));
     TextSource src;

@@ -171,6 +171,8 @@ def _counter_kwargs(param):
         kwargs['parts'] = True
     if param.get('stagger'):                        # --stagger N: the window tried at N + 1 starts (f2q_set_stagger); part of the key too
         kwargs['stagger'] = param['stagger']
+    if param.get('indel'):                          # --indel: one-base insertions and deletions reported (f2q_set_indel); part of the key too
+        kwargs['indel'] = True
     return kwargs
 
 
@@ -318,6 +320,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         raise RuntimeError("--parts: the part tables and recombinant sets are not merged across several ranks; run one process")
     if param.get('stagger') and sharding.world().size > 1:
         raise RuntimeError("--stagger: the offset histograms are not merged across several ranks; run one process")
+    if param.get('indel') and sharding.world().size > 1:
+        raise RuntimeError("--indel: the indel counts are not merged across several ranks; run one process")
     ctx =_context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
     try:
         world = sharding.world()
@@ -363,6 +367,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             param.setdefault('strand_counted', {})[raw] = ctx.read_strands()
         if param.get('stagger'):                    # --stagger N: reads assigned without / with mismatches at each offset (f2q_read_stagger)
             param.setdefault('stagger_counted', {})[raw] = ctx.read_stagger()
+        if param.get('indel'):                      # --indel: deletion and insertion reads per feature and per position, the four totals (f2q_read_indels)
+            param.setdefault('indel_counted', {})[raw] = ctx.read_indels()
         if param.get('parts'):                      # --parts: counts by the part rule, the marginals, the six classes (f2q_read_parts) and the recombinant pairs
             param.setdefault('parts_counted', {})[raw] = (ctx.read_parts(), ctx.parts_recombinants())
     except BaseException:
@@ -474,6 +480,12 @@ def aligner(i, raw, features, param, reads_stats):
     if raw in param.get('stagger_counted', {}):      # --stagger N: the sample's two columns of <name>_stagger.csv
         perfect, imperfect = param['stagger_counted'].pop(raw)
         param.setdefault("stagger_samples", {})[sample.name] = ([int(n) for n in perfect], [int(n) for n in imperfect])
+    if raw in param.get('indel_counted', {}):        # --indel: the sample's two columns of <name>_indel.csv and of <name>_indel_positions.csv, its totals
+        dels, inss, del_pos, ins_pos, totals = param['indel_counted'].pop(raw)
+        names = [f.name for f in features.values()]
+        columns = [SampleResult(f"{sample.name}:del", value, unit, _sample_rows(zip(names, (int(n) for n in dels))), {}),
+                   SampleResult(f"{sample.name}:ins", value, unit, _sample_rows(zip(names, (int(n) for n in inss))), {})]
+        param.setdefault("indel_samples", {})[sample.name] = (columns, [int(n) for n in del_pos], [int(n) for n in ins_pos], [int(n) for n in totals])
     if raw in param.get('parts_counted', {}):        # --parts: the same rows holding parts_counts; the recombinant pairs by their texts; the classes
         (parts_counts, part1, part2, classes), (i1, i2, reads) = param['parts_counted'].pop(raw)
         names = [f.name for f in features.values()]
@@ -565,6 +577,9 @@ def initializer(cmd):
     if param.get('stagger'):
         print(f" The feature window is tried at the starts {param['start']} .. {int(param['start']) + param['stagger']}: the earliest exact one counts, else the earliest within --m")
         print(f" {stagger_header(param)[1:]}")
+    if param.get('indel'):
+        print(" Reads that are assigned no feature are tried as one-base deletions and insertions of every feature; they are reported, not counted")
+        print(f" {INDEL_HEADER[1:]}")
     if param.get('parts'):
         print(" Each of the two feature parts is also matched on its own; recombinant reads are counted per pair of parts")
         print(f" {PARTS_HEADER[1:]}")
@@ -630,6 +645,9 @@ def sample_barcodes_header(param):
 def stagger_header(param):
     """the line a --stagger N run (N > 0) adds to the parameter print-out and to the head of <name>_stats.csv"""
     return f"#Stagger: {param['stagger']}"
+
+
+INDEL_HEADER = "#Indel reads reported: 1"      # the line an --indel run adds to the parameter print-out and to the head of <name>_stats.csv
 
 
 def strand_header(param):
@@ -701,6 +719,7 @@ def input_parser(argv=None):
     ap.add_argument("--sbm", help="With --sb: mismatches allowed in the sample barcode, 0 or 1 (default = 0)")
     ap.add_argument("--strand", help="fwd (default), rev or both: the orientation the reads are counted in. rev: every read is reverse-complemented first; both: a read that is assigned no feature as sequenced is tried reverse-complemented (<name>_strand.csv). Counter mode, single reads, one process")
     ap.add_argument("--stagger", help="N (0-32): the one fixed window (--st s --l L) is tried at the starts s .. s+N; a read counts at the earliest start that reads a feature exactly, else at the earliest one within --m (<name>_stagger.csv). 0 (default): off. Counter mode, single reads, one --st value, one process")
+    ap.add_argument("--indel", nargs='?', const=True, help="Reads that the one fixed window (--st s --l L, L 2-31) assigns to no feature are tried as a one-base deletion and as a one-base insertion of every feature of L bases; they are reported per feature and per position (<name>_indel.csv, <name>_indel_positions.csv) and change no count. Counter mode, single reads, one --st value, one process")
     ap.add_argument("--parts", nargs='?', const=True, help="Pair libraries (features A:B over exactly two windows: --st a,b, or --pe --st a --st2 b): each part is also matched on its own with --m mismatches per part; reads whose two parts the library does not pair are counted as recombinants (<name>_parts.csv, <name>_recombinants.csv). Counter mode, one process")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
     args = ap.parse_args(argv)
@@ -886,6 +905,30 @@ def input_parser(argv=None):
                 colourful_errors("FATAL", f"--stagger {args.stagger} needs exactly one window start at or after the first base: --st {p['start']} does not name one.")
                 sys.exit(2)
             p['stagger'] = int(args.stagger)
+    if args.indel is not None:
+        if args.indel is not True:
+            colourful_errors("FATAL", f"--indel takes no value: --indel {args.indel} is not understood.")
+            sys.exit(2)
+        if p['Running Mode'] != "C":
+            colourful_errors("FATAL", "--indel only has a meaning in Counter mode: it cannot be combined with --mo EC.")
+            sys.exit(2)
+        others = [f for f, v in (("--pe", args.pe), ("--us", args.us), ("--ds", args.ds), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2),
+                                 ("--umih", args.umih), ("--sb", args.sb), ("--parts", args.parts)) if v is not None]
+        if args.strand in ("rev", "both"):
+            others.append(f"--strand {args.strand}")
+        if p.get('stagger'):
+            others.append(f"--stagger {p['stagger']}")
+        if others:
+            colourful_errors("FATAL", f"--indel cannot be combined with {' / '.join(others)}: the unassigned reads of one fixed window of single reads are "
+                                      "examined, without anchors, UMIs, sample barcodes, a strand mode, parts or a stagger.")
+            sys.exit(2)
+        if not re.fullmatch(r"[0-9]+", str(p['start']).strip()):
+            colourful_errors("FATAL", f"--indel needs exactly one window start at or after the first base: --st {p['start']} does not name one.")
+            sys.exit(2)
+        if not 2 <= p['length'] <= 31:
+            colourful_errors("FATAL", f"--indel needs a window of 2 to 31 bases: --l {p['length']} is outside that range.")
+            sys.exit(2)
+        p['indel'] = True
     if args.assign is not None:
         if p['Running Mode'] != "EC":
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
@@ -927,6 +970,9 @@ def file_sizer_split(param):
         sys.exit(2)
     if param.get('stagger') and sharding.world().size > 1:
         colourful_errors("FATAL", "--stagger: the offset histograms are not merged across several ranks; run one process.")
+        sys.exit(2)
+    if param.get('indel') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--indel: the indel counts are not merged across several ranks; run one process.")
         sys.exit(2)
     if param.get('parts') and sharding.world().size > 1:
         colourful_errors("FATAL", "--parts: the part tables and recombinant sets are not merged across several ranks; run one process.")
@@ -1044,6 +1090,8 @@ def run_headers(param):
         lines.append(strand_header(param))
     if param.get('stagger'):
         lines.append(stagger_header(param))
+    if param.get('indel'):
+        lines.append(INDEL_HEADER)
     if param.get('parts'):
         lines.append(PARTS_HEADER)
     return lines
@@ -1104,6 +1152,15 @@ def compiling(param):
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stagger.csv"),
                    [["#Offset", "Start"] + [f"{name}:{kind}" for name in names for kind in ("perfect", "imperfect")]] +
                    [[d, int(param['start']) + d] + [stag[name][k][d] for name in names for k in (0, 1)] for d in range(param['stagger'] + 1)])
+    if param.get("indel_samples"):                   # --indel: per file, in <name>.csv's column order, its deletion and its insertion column; a row per position
+        ind = param["indel_samples"]
+        ihead, itable = _table_of([column for s in ordered for column in ind.get(s.name, ((),))[0]])
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_indel.csv"),
+                   [ihead] + [[feature] + counts for feature, counts in itable.items()])
+        names = [s.name for s in ordered if s.name in ind]
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_indel_positions.csv"),
+                   [["#Position"] + [f"{name}:{kind}" for name in names for kind in ("del", "ins")]] +
+                   [[p] + [ind[name][k][p] for name in names for k in (1, 2)] for p in range(param['length'])])
     if param.get("parts_samples"):                   # --parts: <name>.csv's layout and row order holding parts_counts; the recombinant pairs of any sample
         parts = param["parts_samples"]
         _, phead, ptable = compile_table({name: rec[0] for name, rec in parts.items()})
@@ -1156,6 +1213,10 @@ STRAND_STATS_HEAD = ["#Sample name (strands)", "Number of reads assigned on the 
 STAGGER_STATS_HEAD = ["#Sample name (stagger)", "Number of reads assigned at offset 0", "Number of reads assigned at a later offset", "Offset with the most assigned reads"]
 
 
+INDEL_STATS_HEAD = ["#Sample name (indel)", "Number of reads that were assigned no feature and tried", "Number of reads with a one-base deletion of a feature",
+                    "Number of reads with a one-base insertion into a feature", "Number of reads that fit two or more features with one indel"]
+
+
 PARTS_STATS_HEAD = ["#Sample name (parts)", "Number of reads whose two parts are a library pair, both without mismatches",
                     "Number of reads whose two parts are a library pair, at least one with mismatches", "Number of recombinant reads (two assigned parts the library does not pair)",
                     "Number of distinct recombinant pairs", "Number of reads with part 1 assigned only", "Number of reads with part 2 assigned only",
@@ -1190,6 +1251,9 @@ def run_stats(headers, param, compiled, head, ordered):
             if s.name in stag:
                 both = [a + b for a, b in zip(*stag[s.name])]
                 global_stat.append([s.name, both[0], sum(both[1:]), both.index(max(both))])
+    ind = param.get("indel_samples", {})
+    if ind:                                                      # --indel: the four totals per file
+        global_stat += [INDEL_STATS_HEAD] + [[s.name] + ind[s.name][3] for s in ordered if s.name in ind]
     parts = param.get("parts_samples", {})
     if parts:                                                    # --parts: the six read classes per file, the distinct recombinant pairs next to their reads
         global_stat += [PARTS_STATS_HEAD] + [

@@ -487,7 +487,8 @@ int f2q_set_umi_header(f2q_ctx *ctx, int32_t sep, int32_t length);
  *   sum over b of matrix[b][f] == counts[f];  sum over b of sample_stats[b][k] == stats[k];
  *   sum(verdicts) == stats[F2Q_READS];  verdicts[EXACT] + verdicts[ONE_MISMATCH] == sum over b < n of sample_stats[b][F2Q_READS].
  * Not implemented: barcodes in the header comment, in mate 2 or on paired samples, with UMIs, with Extract+Count, on
- * several ranks, indels or staggers, distance 2, the packed-tile kernels. */
+ * several ranks, indels or staggers in the barcode (one-base indels in the FEATURE are reported by f2q_set_indel, without
+ * sample barcodes), distance 2, the packed-tile kernels. */
 #define F2Q_BC_EXACT 0
 #define F2Q_BC_ONE_MISMATCH 1
 #define F2Q_BC_AMBIGUOUS 2
@@ -667,6 +668,72 @@ int f2q_parts_recombinants(f2q_ctx *ctx, uint64_t cap, uint64_t *n, uint32_t *pa
 #define F2Q_STAGGER_MAX_N 32
 int f2q_set_stagger(f2q_ctx *ctx, int32_t n);
 int f2q_read_stagger(f2q_ctx *ctx, int64_t *perfect /* n + 1 */, int64_t *imperfect /* n + 1 */, int32_t n_offsets);
+
+/* ---- reads whose feature carries one inserted or deleted base ---------------------------------------
+ * Single-base deletions are the dominant error of oligo-pool synthesis, insertions follow.  Such a read compares badly
+ * at every fixed window, so the plain rule calls it non-aligned.  f2q_set_indel(ctx, 1) makes a single-end Counter context
+ * with exactly one fixed window (--st s --l L, 2 <= L <= 31) REPORT these reads next to everything it counts: counts and
+ * the five counters stay what they are without the call.
+ *
+ * The rule.  seq / qual are the rstrip()-ed lines 2 and 4 of the record.  V0 is what the reference decides for the read
+ * with the run's --st s --l L --m --ph.  The candidates are the library's features of exactly L bases, all A/C/G/T (a
+ * sequence the library holds twice takes part once, under its first index); features of other lengths or with other
+ * symbols take part in V0 only.  passes(q) is the Phred test of a feature window: no byte c of q with
+ * 33 <= c <= min(max(ph, 1) + 31, 126) when ph > 1, and always true when ph <= 1.
+ *
+ *     def indel_verdict(V0, seq, qual, s, L, candidates, passes):   # -> (kind, feature, position) or "ambiguous" or None
+ *         if V0.kind in (PERFECT, IMPERFECT):              # a substitution match is never re-examined, even where an
+ *             return None                                  # indel would explain the read better
+ *         D, I = {}, {}                                    # feature -> smallest position
+ *         Wd, Qd = seq[s:s + L - 1].upper(), qual[s:s + L - 1]          # the deletion window: L - 1 bases
+ *         if len(Wd) == L - 1 and len(Qd) == L - 1 and passes(Qd):
+ *             for f in candidates:
+ *                 for p in range(L):
+ *                     variant = f[:p] + f[p + 1:]
+ *                     if variant == f[:L - 1]:             # only says that the window's last base is unknown: it cannot
+ *                         continue                         # be told from a substitution of the last base
+ *                     if variant == Wd:
+ *                         D.setdefault(f, p)
+ *         Wi, Qi = seq[s:s + L + 1].upper(), qual[s:s + L + 1]          # the insertion window: L + 1 bases
+ *         if len(Wi) == L + 1 and len(Qi) == L + 1 and passes(Qi):
+ *             for p in range(L):                           # bytes are compared: one 'N' can be the inserted base and
+ *                 f = Wi[:p] + Wi[p + 1:]                  # nothing else; p == L would make the plain window exact
+ *                 if f in candidates:
+ *                     I.setdefault(f, p)
+ *         both = set(D) | set(I)
+ *         if len(both) >= 2:
+ *             return "ambiguous"                           # counted as such, assigned nothing
+ *         for f in both:
+ *             return ("ins", f, I[f]) if f in I else ("del", f, D[f])      # L + 1 bases of evidence outrank L - 1
+ *         return None
+ *
+ * --m plays no part in the trial: an indel read has exactly one indel and no substitution.  A read is "tried" when V0
+ * assigned it nothing (non-aligned or quality failed), whether or not a window was usable.
+ *
+ * f2q_set_indel comes after f2q_create and before the first counting call, before or after f2q_set_features (the
+ * deletion-variant table is built when both the flag and a library are known).  0 makes the context a plain one again (on a
+ * plain context it is accepted at any time and changes nothing): it then launches the kernels it launched before.  With a
+ * non-zero value, F2Q_ESTATE with a message that names the cause: an Extract+Count context, a paired context
+ * (f2q_set_mate2), --us/--ds, several windows, a window that starts before the first base, L outside 2 .. 31, a UMI context
+ * of any kind, a demultiplexing context, a non-zero strand mode, a parts context, a stagger context, or after a counting
+ * call; afterwards f2q_set_mate2, f2q_set_umi, f2q_set_umi_paired, f2q_set_umi_header, f2q_set_sample_barcodes,
+ * f2q_set_strand with a non-zero mode, f2q_set_parts, f2q_set_stagger with n > 0 and the sharded calls with world > 1 are
+ * F2Q_ESTATE in turn.  From then on every read takes the raw-record road (k_count_indel) through f2q_count_block,
+ * f2q_block_from_fastq + f2q_count_resident / f2q_count_resident_queued, f2q_count_text and f2q_count_file (plain, gzip,
+ * BGZF, F2Q_DEVICE_INFLATE=1, F2Q_HOST_PACK=1).
+ *
+ * f2q_read_indels: del_counts[f] / ins_counts[f] = deletion / insertion reads of feature f; del_pos[p] / ins_pos[p] =
+ * those reads by position p = 0 .. L - 1; totals = reads tried, deletion reads, insertion reads, ambiguous reads.  n_pos
+ * must be L (F2Q_EINVAL otherwise); any pointer may be NULL; F2Q_ESTATE on a plain context.  It synchronises as
+ * f2q_read_counts does.  f2q_reset_counts zeroes it; a new library starts it afresh.  Invariants:
+ *   sum(del_counts) == sum(del_pos) == totals[1];  sum(ins_counts) == sum(ins_pos) == totals[2];
+ *   totals[0] == stats[F2Q_NON_ALIGNED] + stats[F2Q_QUALITY_FAILED];  totals[1] + totals[2] + totals[3] <= totals[0].
+ * Not implemented: Extract+Count, paired samples, anchored runs, several windows, UMIs / sample barcodes / a strand mode /
+ * part verdicts / a stagger with indel reads, several ranks, two edits, an indel next to a substitution, adding indel
+ * reads to the counts, the packed-tile kernels. */
+int f2q_set_indel(f2q_ctx *ctx, int32_t on);
+int f2q_read_indels(f2q_ctx *ctx, int64_t *del_counts /* n_features */, int64_t *ins_counts /* n_features */, int64_t *del_pos /* L */,
+                    int64_t *ins_pos /* L */, int32_t n_pos, int64_t totals[4]);
 
 #ifdef __cplusplus
 }
