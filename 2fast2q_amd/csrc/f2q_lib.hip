@@ -51,6 +51,42 @@ struct f2q_block {
     uint64_t raw_key_bytes = 0;            // upper bound of the key bytes the raw records can produce (Extract+Count arena sizing)
 };
 
+// The raw-record modes of a Counter context.  They exclude each other: f2q_ctx::raw_mode names the one in place, and what
+// is said when a call meets it is built from its row of RAW_MODES (raw_mode_enter and the raw_mode_* refusals below).
+enum RawMode { RAW_NONE, RAW_UMI, RAW_DEMUX, RAW_STRAND, RAW_STAGGER, RAW_INDEL, RAW_PARTS };
+struct RawModeRow {
+    const char *phrase;      // the context in messages
+    const char *setter;      // the call that made it one
+    const char *what;        // what the mode adds, in "X and Y are not combined"
+    bool pairs_ok;           // merged pairs are counted too (else single reads, single raw records only)
+    bool once;               // the setter comes once (else it may be called again, and with 0 to take the mode back)
+    const char *mate2;       // what f2q_set_mate2 says of such a context
+    const char *unmerged;    // what several ranks cannot merge
+};
+static const RawModeRow RAW_MODES[] = {
+    {"a plain context", "", "", true, false, "", ""},
+    {"a UMI context (f2q_set_umi / f2q_set_umi_header / f2q_set_umi_paired)", "f2q_set_umi", "UMIs", true, true,
+     "counts single reads only: f2q_set_mate2 comes first, then f2q_set_umi_paired", "the sets"},
+    {"a demultiplexing context (f2q_set_sample_barcodes)", "f2q_set_sample_barcodes", "sample barcodes", false, true, "counts single reads only", "the matrices"},
+    {"a context with a strand mode (f2q_set_strand: rev / both)", "f2q_set_strand", "a strand mode", false, true, "counts single reads only", "the reverse-strand counts"},
+    {"a stagger context (f2q_set_stagger)", "f2q_set_stagger", "a stagger", false, false, "counts single reads only", "the offset histograms"},
+    {"an indel context (f2q_set_indel)", "f2q_set_indel", "indel reads", false, false, "counts single reads only", "the indel counts"},
+    {"a parts context (f2q_set_parts)", "f2q_set_parts", "part verdicts", true, true,
+     "keeps its windows: f2q_set_mate2 comes first, then f2q_set_parts", "the tables and sets"},
+};
+
+// A set of pairs in device memory that grows with what is counted: (feature, UMI) of a UMI context, (part 1, part 2) of
+// the recombinants of a parts context.  *dev is the kernels' view of it, inside the owner's device struct.
+struct PairSet {
+    UmiDev *dev;
+    const char *name;                    // "<name> set" in messages and traces
+    bool keep_reads;                     // dev->reads[] lives and dies with dev->slots[]
+    std::vector<void *> set_allocs;      // slots[] (and reads[])
+    uint64_t n_slots = 0, min_slots = (uint64_t)1 << 16;     // F2Q_UMI_SLOTS / F2Q_PARTS_SLOTS: the first set's size (tests: growth from a small one)
+    uint64_t held_ub = 0;                // pairs held, an upper bound: every record launched since the last exact reading taken as new
+    uint64_t rehashes = 0;
+};
+
 struct f2q_ctx {
     f2q_params prm{};
     std::vector<std::string> up_s, down_s;
@@ -120,67 +156,60 @@ struct f2q_ctx {
     AssignDev asg{};
     uint64_t asg_nb = 0, asg_nw = 0;     // entries / slots the per-key arrays cover
     uint64_t ec_gen = 1, asg_gen = 0;    // ec_gen: bumped by every count call, reset and table growth
+    // The raw-record modes (RAW_MODES): at most one is in place.  Each sends every read down the raw-record road
+    // (raw_road_enter) to a kernel of its own; its parameters and device memory live in its struct below
+    RawMode raw_mode = RAW_NONE;
+    bool env_general = false;            // what F2Q_FORCE_GENERAL said before the context was sent down the raw-record road
     // distinct UMIs per feature (f2q_set_umi): the set of (feature, UMI) pairs, umis[n_features] and the counters.  The set
-    // outlives the pieces of a file; umi_reserve sizes it before every launch
+    // outlives the pieces of a file; pairset_reserve sizes it before every launch
     struct {
-        bool on = false;
         UmiDev dev{};
-        std::vector<void *> set_allocs, fix_allocs;          // the slots / umis[] and the counters
-        uint64_t n_slots = 0, min_slots = (uint64_t)1 << 16;     // F2Q_UMI_SLOTS: the first set's size (tests: growth from a small one)
-        uint64_t held_ub = 0;            // pairs held, an upper bound: every record launched since the last exact reading taken as new
-        uint64_t rehashes = 0;
-        bool reads_on = false;           // f2q_set_umi_reads: dev.reads[] lives and dies with dev.slots[] (set_allocs)
+        PairSet set{&dev, "UMI", false};     // keep_reads: f2q_set_umi_reads
+        std::vector<void *> fix_allocs;  // umis[] and the counters
         bool pair_stage = false;         // f2q_set_umi_paired: k_count_umi_pair<.., true> (F2Q_UMI_PAIR_STAGE)
         int32_t hdr_sep = 0;             // f2q_set_umi_header: the separator byte (0: the UMI is not in the header); the length is dev.length
     } umi;
     // inline sample barcodes (f2q_set_sample_barcodes): the barcode table, the count matrix [(n + 1)][n_features], the five
     // reference counters per sample and the five verdict counters; they live across pieces and counting calls
     struct {
-        bool on = false;
         DemuxDev dev{};
         DemuxTable tab;                  // the host's copy of the table (uploaded once, with the first allocation)
         std::vector<void *> allocs;      // table, matrix, sstats + verdicts
         uint64_t matrix_n = 0;           // words of dev.matrix
         bool lds_table = false;          // k_count_demux<true> (F2Q_DEMUX_TABLE=lds, and the table fits)
-        bool shmem_set = false;          // the instance has been told its dynamic LDS size
     } demux;
     // read orientation (f2q_set_strand): reads assigned on the reverse strand per feature and the four strand counters; they
     // live across pieces and counting calls
     struct {
-        int32_t mode = 0;                // F2Q_STRAND_FWD (a plain context) / _REV / _BOTH
+        int32_t mode = 0;                // F2Q_STRAND_REV / _BOTH of a RAW_STRAND context
         StrandDev dev{};
         std::vector<void *> allocs;      // rev_counts + extra, one allocation
         uint64_t words = 0;              // of that allocation: max(n_features, 1) + 4
     } strand;
     // staggered libraries (f2q_set_stagger): the window tried at the starts s .. s + n, the reads assigned at each offset
     struct {
-        int32_t n = 0;                   // 0: a plain context
+        int32_t n = 0;                   // 1 .. 32 on a RAW_STAGGER context
         StaggerDev dev{};
         std::vector<void *> allocs;      // the two histograms, one allocation of 2 * (n + 1) words
-        bool env_general = false;        // what F2Q_FORCE_GENERAL said before the context was sent down the raw-record road
     } stagger;
     // one-base insertions and deletions (f2q_set_indel): the deletion-variant table, the per-feature counts, the two position
     // histograms and the four totals; built once the flag and a library are both known (indel_install)
     struct {
-        bool on = false;
         IndelDev dev{};
         std::vector<void *> allocs;      // the table's two arrays; the counters, one allocation of `words` words
         uint64_t words = 0;              // 2 * max(n_features, 1) + 2 * L + 4
-        bool env_general = false;        // what F2Q_FORCE_GENERAL said before the context was sent down the raw-record road
     } indel;
     // pair libraries with each part matched alone (f2q_set_parts): the two part libraries (indices of their own, as the
     // assign library has one), the pair table, parts_counts / the marginals / the six class counters (one allocation) and
-    // the recombinant set, which outlives the pieces of a file; parts_reserve sizes it before every launch
+    // the recombinant set, which outlives the pieces of a file; pairset_reserve sizes it before every launch
     struct {
-        bool on = false;
         PartsDev dev{};
+        PairSet set{&dev.rec, "recombinant", true};
         PartsTable tab;                  // the host's copy: part texts, feature -> ids, the pair table
         HostIndex ix[2];
         LibDev lib_h[2]{};
-        std::vector<void *> lib_allocs[2], fix_allocs, set_allocs;   // the part libraries / tables and counters / the set
+        std::vector<void *> lib_allocs[2], fix_allocs;   // the part libraries / tables and counters
         uint64_t words = 0;              // of the counters' allocation: nf + n1 + n2 + 6 (each count at least 1)
-        uint64_t n_slots = 0, min_slots = (uint64_t)1 << 16;         // F2Q_PARTS_SLOTS: the first set's size (tests: growth from a small one)
-        uint64_t held_ub = 0, rehashes = 0;
     } parts;
     bool counted = false;                // a counting launch has been made (f2q_set_umi comes before the first)
     uint32_t last_path = 0;              // F2Q_PATH_* of the last packed-tile launch (f2q_timing.path)
@@ -304,6 +333,68 @@ static int hip_rc(f2q_ctx *c, hipError_t e) { return e == hipSuccess ? F2Q_OK : 
 // the calls for single reads refuse a paired context, and the other way round
 static int single_only(f2q_ctx *c) { return c->n_mate1 ? fail(c, F2Q_ESTATE, "a paired context (f2q_set_mate2) counts pairs only: use the f2q_*_paired calls") : F2Q_OK; }
 static int paired_only(f2q_ctx *c) { return c->n_mate1 ? F2Q_OK : fail(c, F2Q_ESTATE, "not a paired context: call f2q_set_mate2 first"); }
+
+// ---- the raw-record modes: one refusal path -----------------------------------------------------------------------------
+// What every setter of a mode asks before it changes anything (`who`: the setter as it is named in messages).  All of these
+// are F2Q_ESTATE; where several apply the first of this order speaks: a Counter context; single reads (a mode that takes no
+// merged pairs); the setter's own shape requirement (`shape`: its complaint about windows or reads, empty when there is none); no other mode
+// in place; the mode not in place already (once); nothing counted yet.  f2q_set_stagger and f2q_set_indel, which can be
+// called again and with 0, ask the last question themselves, first of all.
+static int raw_mode_enter(f2q_ctx *c, RawMode mode, const char *who, const std::string &shape = std::string())
+{
+    const RawModeRow &in_place = RAW_MODES[c->raw_mode], &mine = RAW_MODES[mode];
+    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, std::string(who) + " takes a Counter context, not Extract+Count");
+    if (!mine.pairs_ok && c->n_mate1) return fail(c, F2Q_ESTATE, std::string(who) + " takes single reads, not a paired context (f2q_set_mate2)");
+    if (!shape.empty()) return fail(c, F2Q_ESTATE, std::string(who) + " " + shape);
+    if (c->raw_mode != RAW_NONE && c->raw_mode != mode)
+        return fail(c, F2Q_ESTATE, std::string(who) + " on " + in_place.phrase + ": " + mine.what + " and " + in_place.what + " are not combined");
+    if (mine.once && c->raw_mode == mode) return fail(c, F2Q_ESTATE, std::string(who) + " comes once: this is " + in_place.phrase + " already");
+    if (c->counted) return fail(c, F2Q_ESTATE, std::string(who) + " comes before counting");
+    return F2Q_OK;
+}
+// f2q_set_mate2 on a context with a mode in place
+static int raw_mode_no_mate2(f2q_ctx *c)
+{
+    if (c->raw_mode == RAW_NONE) return F2Q_OK;
+    return fail(c, F2Q_ESTATE, std::string(RAW_MODES[c->raw_mode].phrase) + " " + RAW_MODES[c->raw_mode].mate2);
+}
+// a share of a file (rank of world > 1) on a context with a mode in place: what the mode gathers is not merged
+static int raw_mode_one_rank(f2q_ctx *c, uint32_t world)
+{
+    if (c->raw_mode == RAW_NONE || world <= 1) return F2Q_OK;
+    return fail(c, F2Q_ESTATE, std::string(RAW_MODES[c->raw_mode].phrase) + " counts whole files: " + RAW_MODES[c->raw_mode].unmerged + " of several ranks are not merged");
+}
+// a block on a context with a mode in place (launch_block): packed tiles, or records of the wrong kind, say that the block
+// was made before the mode was set
+static int raw_mode_block(f2q_ctx *c, const f2q_block *b)
+{
+    const RawModeRow &row = RAW_MODES[c->raw_mode];
+    bool stale = b->pb.n_tiles != 0;
+    if (!row.pairs_ok) stale = stale || b->rb.len1;
+    else if (c->raw_mode == RAW_PARTS) stale = stale || (b->rb.n && (b->rb.len1 != nullptr) != (c->n_mate1 != 0));
+    if (stale) return fail(c, F2Q_ESTATE, std::string("the block was packed before ") + row.setter + ": " + row.phrase + " counts " + (row.pairs_ok ? "" : "single ") + "raw records only");
+    if (c->raw_mode == RAW_UMI && c->umi.hdr_sep && b->rb.n && !b->rb.hdr_umi)
+        return fail(c, F2Q_ESTATE, "the block was made before f2q_set_umi_header (or without headers): its records carry no header UMI");
+    return F2Q_OK;
+}
+// Every read takes the raw-record road, as F2Q_FORCE_GENERAL=1 sends it, to the kernel of `mode` (launch_raw);
+// f2q_set_features keeps it that way.  Last in a setter: whatever can fail has been done.
+static void raw_road_enter(f2q_ctx *c, RawMode mode)
+{
+    if (c->raw_mode == RAW_NONE) c->env_general = c->force_general;
+    c->raw_mode = mode;
+    c->force_general = true;
+    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
+    c->plan.inband_n = false; c->plan.n_only = false;
+}
+// the first size of a pair set: F2Q_UMI_SLOTS / F2Q_PARTS_SLOTS rounded up to a power of two
+static uint64_t pairset_min_slots_from_env(const char *name)
+{
+    uint64_t slots = (uint64_t)1 << 16;
+    const char *e = getenv(name);
+    if (e && atol(e) > 0) { slots = 2; while (slots < (uint64_t)atol(e) && slots < (1ull << 32)) slots <<= 1; }
+    return slots;
+}
 // bytes of text per piece of a streamed file; F2Q_FILE_CHUNK overrides (tests)
 static size_t file_chunk_bytes(size_t dflt) { const char *e = getenv("F2Q_FILE_CHUNK"); return e && atol(e) >= 4096 ? (size_t)atol(e) : dflt; }
 
@@ -479,31 +570,45 @@ extern "C" int f2q_create(const f2q_params *p, f2q_ctx **out)
 }
 
 // the (feature, UMI) set given back: f2q_destroy, and a new library (umis[] has a word per feature)
+static void pairset_drop(f2q_ctx *c, PairSet &s)
+{
+    free_all(c, s.set_allocs);
+    s.dev->slots = nullptr; s.dev->reads = nullptr; s.n_slots = 0; s.held_ub = 0;
+}
 static void umi_drop(f2q_ctx *c)
 {
-    free_all(c, c->umi.set_allocs); free_all(c, c->umi.fix_allocs);
-    c->umi.dev.slots = nullptr; c->umi.dev.reads = nullptr; c->umi.dev.umis = nullptr; c->umi.dev.ctr = nullptr; c->umi.n_slots = 0; c->umi.held_ub = 0;
+    pairset_drop(c, c->umi.set); free_all(c, c->umi.fix_allocs);
+    c->umi.dev.umis = nullptr; c->umi.dev.ctr = nullptr;
 }
 
-// the set, umis[] and the counters cleared (f2q_reset_counts), the set's size kept
+// the set and its counters (which the owner has allocated) cleared, the set's size kept
+static int pairset_clear(f2q_ctx *c, PairSet &s)
+{
+    if (s.dev->slots) HIPC(c, hipMemsetAsync(s.dev->slots, 0xFF, s.n_slots * sizeof(unsigned long long), c->stream));
+    if (s.dev->reads) HIPC(c, hipMemsetAsync(s.dev->reads, 0, s.n_slots * sizeof(uint32_t), c->stream));
+    HIPC(c, hipMemsetAsync(s.dev->ctr, 0, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), c->stream));
+    s.held_ub = 0;
+    return F2Q_OK;
+}
+// the set, umis[] and the counters cleared (f2q_reset_counts)
 static int umi_clear(f2q_ctx *c)
 {
-    if (c->umi.dev.slots) HIPC(c, hipMemsetAsync(c->umi.dev.slots, 0xFF, c->umi.n_slots * sizeof(unsigned long long), c->stream));
-    if (c->umi.dev.reads) HIPC(c, hipMemsetAsync(c->umi.dev.reads, 0, c->umi.n_slots * sizeof(uint32_t), c->stream));
     HIPC(c, hipMemsetAsync(c->umi.dev.umis, 0, std::max<uint64_t>(c->lib_h.n_features, 1) * sizeof(unsigned long long), c->stream));
-    HIPC(c, hipMemsetAsync(c->umi.dev.ctr, 0, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), c->stream));
-    c->umi.held_ub = 0;
-    return F2Q_OK;
+    return pairset_clear(c, c->umi.set);
 }
 
 // the set's counters after everything on the stream (all zero before the first launch); waits for the stream
-static int umi_read_ctr(f2q_ctx *c, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
+static int pairset_read_ctr(f2q_ctx *c, const PairSet &s, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
 {
     for (int i = 0; i < F2Q_UMI_CTR_WORDS; i++) ctr[i] = 0;
-    if (c->umi.dev.ctr) HIPC(c, hipMemcpyAsync(ctr, c->umi.dev.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (s.dev->ctr) HIPC(c, hipMemcpyAsync(ctr, s.dev->ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
-    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "UMI set overflow (internal sizing error)");
+    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, std::string(s.name) + " set overflow (internal sizing error)");
     return F2Q_OK;
+}
+static void pairset_trace(const f2q_ctx *c, const PairSet &s)
+{
+    if (c->trace) fprintf(stderr, "[f2q trace] %s set: %llu slots, %llu rehashes\n", s.name, (unsigned long long)s.n_slots, (unsigned long long)s.rehashes);
 }
 
 // the barcode table, the matrix and the counters given back: f2q_destroy, and a new library
@@ -517,7 +622,7 @@ static void demux_drop(f2q_ctx *c)
 // failure gives back what this call got and leaves the context as it was: the call that led here may simply be repeated.
 static int demux_alloc(f2q_ctx *c)
 {
-    if (!c->demux.on || c->demux.dev.matrix) return F2Q_OK;
+    if (c->demux.dev.matrix) return F2Q_OK;
     DemuxDev d = c->demux.dev; std::vector<void *> owner;
     const uint64_t nf = std::max<uint64_t>(c->lib_h.n_features, 1), rows = (uint64_t)d.n + 1;
     unsigned long long *tab = nullptr, *ctr = nullptr;
@@ -552,7 +657,7 @@ static void strand_drop(f2q_ctx *c)
 // it was: the call that led here may simply be repeated.
 static int strand_alloc(f2q_ctx *c)
 {
-    if (!c->strand.mode || c->strand.dev.rev_counts) return F2Q_OK;
+    if (c->strand.dev.rev_counts) return F2Q_OK;
     const uint64_t nf = std::max<uint64_t>(c->lib_h.n_features, 1);
     unsigned long long *w = nullptr; std::vector<void *> owner;
     if (dev_alloc(c, (size_t)(nf + 4), &w, owner, 0)) {
@@ -574,7 +679,7 @@ static void indel_drop(f2q_ctx *c)
 // swapped in at the end: a failure leaves the context as it was.  Without a library there is nothing to build yet.
 static int indel_install(f2q_ctx *c, bool lib_known)
 {
-    if (!c->indel.on || !lib_known) return F2Q_OK;
+    if (!lib_known) return F2Q_OK;
     const int L = c->run_h.length;
     const uint64_t nf = std::max<uint64_t>(c->ix.n_features, 1);
     if ((uint64_t)c->ix.grp[L].n * (uint64_t)L > 0x40000000ull) return fail(c, F2Q_ENOMEM, "f2q_set_indel: the deletion-variant table of " + std::to_string(c->ix.grp[L].n) + " features is not built");
@@ -603,13 +708,13 @@ static int indel_install(f2q_ctx *c, bool lib_known)
 static void parts_drop(f2q_ctx *c)
 {
     for (int k = 0; k < 2; k++) free_all(c, c->parts.lib_allocs[k]);
-    free_all(c, c->parts.fix_allocs); free_all(c, c->parts.set_allocs);
-    c->parts.dev = PartsDev{}; c->parts.words = 0; c->parts.n_slots = 0; c->parts.held_ub = 0;
+    free_all(c, c->parts.fix_allocs); pairset_drop(c, c->parts.set);
+    c->parts.dev = PartsDev{}; c->parts.words = 0;
 }
 
 // The part libraries, the pair table and zeroed counters for the library seqs / offs / n (f2q_set_features' arguments),
 // built next to what the context holds and swapped in at the end: a failure (F2Q_EINVAL: a feature that is not two parts,
-// named in the message; F2Q_ENOMEM) leaves the context as it was.  The set starts empty (parts_reserve allocates it).
+// named in the message; F2Q_ENOMEM) leaves the context as it was.  The set starts empty (pairset_reserve allocates it).
 static int parts_install(f2q_ctx *c, const char *seqs, const uint32_t *offs, uint32_t n)
 {
     PartsTable t; std::string err;
@@ -649,23 +754,51 @@ static int parts_install(f2q_ctx *c, const char *seqs, const uint32_t *offs, uin
 static int parts_clear(f2q_ctx *c)
 {
     HIPC(c, hipMemsetAsync(c->parts.dev.counts, 0, c->parts.words * sizeof(unsigned long long), c->stream));
-    HIPC(c, hipMemsetAsync(c->parts.dev.rec.ctr, 0, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), c->stream));
-    if (c->parts.dev.rec.slots) {
-        HIPC(c, hipMemsetAsync(c->parts.dev.rec.slots, 0xFF, c->parts.n_slots * sizeof(unsigned long long), c->stream));
-        HIPC(c, hipMemsetAsync(c->parts.dev.rec.reads, 0, c->parts.n_slots * sizeof(uint32_t), c->stream));
-    }
-    c->parts.held_ub = 0;
-    return F2Q_OK;
+    return pairset_clear(c, c->parts.set);
 }
 
-// the set's counters after everything on the stream; waits for the stream
-static int parts_read_ctr(f2q_ctx *c, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
+// ---- the raw-record modes: one life cycle ---------------------------------------------------------------------------------
+// f2q_set_features has a new library in place (seqs / offs / n: its arguments): what the mode holds per feature starts afresh
+static int mode_on_library(f2q_ctx *c, const char *seqs, const uint32_t *offs, uint32_t n)
 {
-    for (int i = 0; i < F2Q_UMI_CTR_WORDS; i++) ctr[i] = 0;
-    if (c->parts.dev.rec.ctr) HIPC(c, hipMemcpyAsync(ctr, c->parts.dev.rec.ctr, F2Q_UMI_CTR_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipStreamSynchronize(c->stream));
-    if (ctr[F2Q_UMI_OVERFLOW]) return fail(c, F2Q_EHIP, "recombinant set overflow (internal sizing error)");
+    switch (c->raw_mode) {
+        case RAW_NONE:    break;
+        case RAW_UMI:     umi_drop(c); break;                             // a new set; umis[] has a word per feature
+        case RAW_DEMUX:   demux_drop(c); return demux_alloc(c);           // a new matrix: a row has a word per feature
+        case RAW_STRAND:  strand_drop(c); return strand_alloc(c);
+        case RAW_STAGGER: HIPC(c, hipMemsetAsync(c->stagger.dev.hist, 0, 2 * ((size_t)c->stagger.n + 1) * sizeof(unsigned long long), c->stream)); break;
+        case RAW_INDEL:   return indel_install(c, true);                  // a variant table and indel counters of its own
+        case RAW_PARTS:   return parts_install(c, seqs, offs, n);         // part libraries, a pair table and a set of its own
+    }
     return F2Q_OK;
+}
+// f2q_reset_counts: what the mode has counted cleared, tables and sizes kept (nothing to clear before the first allocation)
+static int mode_clear(f2q_ctx *c)
+{
+    switch (c->raw_mode) {
+        case RAW_NONE:    break;
+        case RAW_UMI:     if (c->umi.dev.umis) return umi_clear(c); break;
+        case RAW_DEMUX:   if (c->demux.dev.matrix) return demux_clear(c); break;
+        case RAW_STRAND:  if (c->strand.dev.rev_counts) HIPC(c, hipMemsetAsync(c->strand.dev.rev_counts, 0, c->strand.words * sizeof(unsigned long long), c->stream)); break;
+        case RAW_STAGGER: HIPC(c, hipMemsetAsync(c->stagger.dev.hist, 0, 2 * ((size_t)c->stagger.n + 1) * sizeof(unsigned long long), c->stream)); break;
+        case RAW_INDEL:   if (c->indel.dev.del_counts) HIPC(c, hipMemsetAsync(c->indel.dev.del_counts, 0, c->indel.words * sizeof(unsigned long long), c->stream)); break;
+        case RAW_PARTS:   if (c->parts.dev.counts) return parts_clear(c); break;
+    }
+    return F2Q_OK;
+}
+// everything the mode holds given back: f2q_destroy (the two pair sets say how far they grew: F2Q_TRACE), and a stagger or
+// an indel context that becomes a plain one again.  No other mode holds device memory.
+static void mode_drop(f2q_ctx *c)
+{
+    switch (c->raw_mode) {
+        case RAW_NONE:    break;
+        case RAW_UMI:     pairset_trace(c, c->umi.set); umi_drop(c); break;
+        case RAW_DEMUX:   demux_drop(c); break;
+        case RAW_STRAND:  strand_drop(c); break;
+        case RAW_STAGGER: free_all(c, c->stagger.allocs); c->stagger.n = 0; c->stagger.dev = StaggerDev{}; break;
+        case RAW_INDEL:   indel_drop(c); break;
+        case RAW_PARTS:   pairset_trace(c, c->parts.set); parts_drop(c); break;
+    }
 }
 
 extern "C" void f2q_destroy(f2q_ctx *c)
@@ -678,14 +811,7 @@ extern "C" void f2q_destroy(f2q_ctx *c)
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
     free_all(c, c->lib_allocs); free_all(c, c->ec_allocs); free_all(c, c->ec_allocs64); free_all(c, c->ec_allocs_ctr); free_all(c, c->hot_allocs);
     free_all(c, c->asg_lib_allocs); free_all(c, c->asg_allocs);
-    if (c->trace && c->umi.on) fprintf(stderr, "[f2q trace] UMI set: %llu slots, %llu rehashes\n", (unsigned long long)c->umi.n_slots, (unsigned long long)c->umi.rehashes);
-    umi_drop(c);
-    demux_drop(c);
-    strand_drop(c);
-    if (c->trace && c->parts.on) fprintf(stderr, "[f2q trace] recombinant set: %llu slots, %llu rehashes\n", (unsigned long long)c->parts.n_slots, (unsigned long long)c->parts.rehashes);
-    parts_drop(c);
-    free_all(c, c->stagger.allocs);
-    indel_drop(c);
+    mode_drop(c);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
     for (auto &kv : c->dev_idle) (void)hipFree(kv.second);
@@ -722,7 +848,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "Extract+Count mode takes no feature library (fast2q.py:1701)");
     HIPC(c, hipSetDevice(c->device));
     for (uint32_t i = 0; i < n; i++) if (offs[i + 1] < offs[i]) return fail(c, F2Q_EINVAL, "offsets must be non-decreasing");
-    if (c->parts.on) {                                // a parts context takes A:B libraries only: refused before anything changes
+    if (c->raw_mode == RAW_PARTS) {                   // a parts context takes A:B libraries only: refused before anything changes
         PartsTable t; std::string err;
         if (int rc = parts_validate(seqs ? seqs : "", offs, n, t, err)) return fail(c, rc, "f2q_set_features on a parts context (f2q_set_parts): " + err);
     }
@@ -744,12 +870,7 @@ extern "C" int f2q_set_features(f2q_ctx *c, const char *seqs, const uint32_t *of
     if (rc) return rc;
     rc = alloc_acc(c, n);
     if (rc) return rc;
-    if (c->umi.on) umi_drop(c);                       // a new library starts a new set
-    if (c->demux.on) { demux_drop(c); if ((rc = demux_alloc(c))) return rc; }      // ... and a new matrix: a row has a word per feature
-    if (c->strand.mode) { strand_drop(c); if ((rc = strand_alloc(c))) return rc; }  // ... and reverse-strand counts that start afresh
-    if (c->parts.on && (rc = parts_install(c, seqs ? seqs : "", offs, n))) return rc;   // ... and part libraries, a pair table and a set of its own
-    if (c->stagger.n) HIPC(c, hipMemsetAsync(c->stagger.dev.hist, 0, 2 * ((size_t)c->stagger.n + 1) * sizeof(unsigned long long), c->stream));   // ... and offsets that start afresh
-    if (c->indel.on && (rc = indel_install(c, true))) return rc;      // ... and a variant table and indel counters of its own
+    if ((rc = mode_on_library(c, seqs ? seqs : "", offs, n))) return rc;
     c->plan.inband_n = (c->plan.fast_fixed || c->plan.fast_anchor) && c->ix.n_irregular == 0;
     // two pairs against a pure A:B library (pair tables): an 'N' travels as a flag bit (a forced mismatch; it equals no
     // symbol of any feature), every other odd symbol still sends the read to the byte-exact routine
@@ -773,12 +894,7 @@ extern "C" int f2q_reset_counts(f2q_ctx *c)
         free_all(c, c->ec_allocs); free_all(c, c->ec_allocs64); free_all(c, c->ec_allocs_ctr);
         memset(&c->ec, 0, sizeof c->ec); c->ec_slots = 0; c->hot_valid = false; c->ec_learned = 0;
     }
-    if (c->umi.on && c->umi.dev.umis) if (int rc = umi_clear(c)) return rc;
-    if (c->demux.on && c->demux.dev.matrix) if (int rc = demux_clear(c)) return rc;
-    if (c->strand.mode && c->strand.dev.rev_counts) HIPC(c, hipMemsetAsync(c->strand.dev.rev_counts, 0, c->strand.words * sizeof(unsigned long long), c->stream));
-    if (c->parts.on && c->parts.dev.counts) if (int rc = parts_clear(c)) return rc;
-    if (c->stagger.n) HIPC(c, hipMemsetAsync(c->stagger.dev.hist, 0, 2 * ((size_t)c->stagger.n + 1) * sizeof(unsigned long long), c->stream));
-    if (c->indel.on && c->indel.dev.del_counts) HIPC(c, hipMemsetAsync(c->indel.dev.del_counts, 0, c->indel.words * sizeof(unsigned long long), c->stream));
+    if (int rc = mode_clear(c)) return rc;
     c->reads_seen = 0;
     c->ec_gen++;
     // no host synchronisation: the clear is ordered on the context's stream like every launch and read-back after it
@@ -816,32 +932,16 @@ extern "C" int f2q_counts_device_ptr(f2q_ctx *c, void **dptr, uint64_t *n_int64)
 }
 
 // ---- distinct UMIs per feature: the ABI ---------------------------------------------------------------------------
-static const char *const INDEL_NO_UMI = "an indel context (f2q_set_indel) takes no UMIs: the two are not combined";
-static const char *const STAGGER_NO_UMI = "a stagger context (f2q_set_stagger) takes no UMIs: the two are not combined";
-static const char *const STRAND_NO_UMI = "a context with a strand mode (f2q_set_strand: rev / both) takes no UMIs: the two are not combined";
-static const char *const PARTS_NO_UMI = "a parts context (f2q_set_parts) takes no UMIs: the two are not combined";
-static const char *const DEMUX_NO_UMI = "a demultiplexing context (f2q_set_sample_barcodes) takes no UMIs: the two are not combined";
-// what f2q_set_umi and f2q_set_umi_paired share once the window is in umi.dev
+// what the three UMI setters share once the window is in umi.dev
 static void umi_enable(f2q_ctx *c)
 {
-    c->umi.on = true;
-    { const char *e = getenv("F2Q_UMI_SLOTS"); if (e && atol(e) > 0) { c->umi.min_slots = 2; while (c->umi.min_slots < (uint64_t)atol(e) && c->umi.min_slots < (1ull << 32)) c->umi.min_slots <<= 1; } }
-    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
-    c->force_general = true;
-    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
-    c->plan.inband_n = false; c->plan.n_only = false;
+    c->umi.set.min_slots = pairset_min_slots_from_env("F2Q_UMI_SLOTS");
+    raw_road_enter(c, RAW_UMI);
 }
 extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
 {
     if (!c) return F2Q_EINVAL;
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi takes a Counter context: Extract+Count assigns no read to a feature");
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi takes single reads: a paired context (f2q_set_mate2) takes f2q_set_umi_paired");
-    if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
-    if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
-    if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
-    if (c->indel.on) return fail(c, F2Q_ESTATE, INDEL_NO_UMI);
-    if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
-    if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi comes once, after f2q_create and before counting");
+    if (int rc = raw_mode_enter(c, RAW_UMI, "f2q_set_umi", c->n_mate1 ? "takes single reads: a paired context (f2q_set_mate2) takes f2q_set_umi_paired" : "")) return rc;
     if (start < 0 || start > 0x3FFFFFFF || length < 1 || length > F2Q_UMI_MAXLEN)
         return fail(c, F2Q_EINVAL, "the UMI window needs a start >= 0 and a length of 1 .. 16 bases");
     c->umi.dev.start = start; c->umi.dev.length = length;
@@ -855,13 +955,7 @@ extern "C" int f2q_set_umi(f2q_ctx *c, int32_t start, int32_t length)
 extern "C" int f2q_set_umi_header(f2q_ctx *c, int32_t sep, int32_t length)
 {
     if (!c) return F2Q_EINVAL;
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_header takes a Counter context: Extract+Count assigns no read to a feature");
-    if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
-    if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
-    if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
-    if (c->indel.on) return fail(c, F2Q_ESTATE, INDEL_NO_UMI);
-    if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
-    if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_header comes once, in place of f2q_set_umi / f2q_set_umi_paired and before counting");
+    if (int rc = raw_mode_enter(c, RAW_UMI, "f2q_set_umi_header")) return rc;
     const bool alnum = (sep >= '0' && sep <= '9') || (sep >= 'A' && sep <= 'Z') || (sep >= 'a' && sep <= 'z');
     if (sep < 33 || sep > 126 || alnum || sep == '+' || length < 1 || length > F2Q_UMI_MAXLEN)
         return fail(c, F2Q_EINVAL, "the header UMI needs a separator that is one printable ASCII byte (33 .. 126), not alphanumeric and not '+', and a length of 1 .. 16 bases");
@@ -878,14 +972,9 @@ extern "C" int f2q_set_umi_header(f2q_ctx *c, int32_t sep, int32_t length)
 extern "C" int f2q_set_umi_paired(f2q_ctx *c, int32_t start1, int32_t length1, int32_t start2, int32_t length2)
 {
     if (!c) return F2Q_EINVAL;
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a Counter context: Extract+Count assigns no pair to a feature");
-    if (c->demux.on) return fail(c, F2Q_ESTATE, DEMUX_NO_UMI);
-    if (c->strand.mode) return fail(c, F2Q_ESTATE, STRAND_NO_UMI);
-    if (c->stagger.n) return fail(c, F2Q_ESTATE, STAGGER_NO_UMI);
-    if (c->indel.on) return fail(c, F2Q_ESTATE, INDEL_NO_UMI);
-    if (c->parts.on) return fail(c, F2Q_ESTATE, PARTS_NO_UMI);
+    // (a single-read context with another mode in place hears of the mode: the want of a second mate comes after)
+    if (int rc = raw_mode_enter(c, RAW_UMI, "f2q_set_umi_paired")) return rc;
     if (!c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired takes a paired context: call f2q_set_mate2 first (single reads: f2q_set_umi)");
-    if (c->umi.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_paired comes once, after f2q_set_mate2 and before counting");
     if (start1 < 0 || start1 > 0x3FFFFFFF || start2 < 0 || start2 > 0x3FFFFFFF || length1 < 0 || length2 < 0 ||
         length1 > F2Q_UMI_MAXLEN || length2 > F2Q_UMI_MAXLEN || length1 + length2 < 1 || length1 + length2 > F2Q_UMI_MAXLEN)
         return fail(c, F2Q_EINVAL, "the UMI parts need starts >= 0 and lengths >= 0 that add up to 1 .. 16 bases");
@@ -901,23 +990,23 @@ extern "C" int f2q_set_umi_paired(f2q_ctx *c, int32_t start1, int32_t length1, i
 extern "C" int f2q_set_umi_reads(f2q_ctx *c, int32_t on)
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->umi.on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (c->raw_mode != RAW_UMI) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
     if (c->counted) return fail(c, F2Q_ESTATE, "f2q_set_umi_reads comes after f2q_set_umi and before counting");
-    c->umi.reads_on = on != 0;
+    c->umi.set.keep_reads = on != 0;
     return F2Q_OK;
 }
 
 extern "C" int f2q_read_umis(f2q_ctx *c, int64_t *umis, int64_t extra[2])
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->umi.on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (c->raw_mode != RAW_UMI) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
     HIPC(c, hipSetDevice(c->device));
     const uint64_t nf = c->lib_h.n_features;
     std::vector<unsigned long long> h(nf, 0ull);
     unsigned long long ctr[F2Q_UMI_CTR_WORDS];
     if (c->umi.dev.umis && nf)                                   // (nothing counted yet: all zero)
         HIPC(c, hipMemcpyAsync(h.data(), c->umi.dev.umis, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    if (int rc = umi_read_ctr(c, ctr)) return rc;
+    if (int rc = pairset_read_ctr(c, c->umi.set, ctr)) return rc;
     if (umis) for (uint64_t i = 0; i < nf; i++) umis[i] = (int64_t)h[i];
     if (extra) { extra[0] = (int64_t)ctr[F2Q_UMI_READS]; extra[1] = (int64_t)ctr[F2Q_UMI_FAILED]; }
     return F2Q_OK;
@@ -927,14 +1016,7 @@ extern "C" int f2q_read_umis(f2q_ctx *c, int64_t *umis, int64_t extra[2])
 extern "C" int f2q_set_sample_barcodes(f2q_ctx *c, const char *seqs, uint32_t n, int32_t length, int32_t start, int32_t miss)
 {
     if (!c) return F2Q_EINVAL;
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes takes a Counter context: Extract+Count with sample barcodes is not implemented");
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes takes single reads: a paired context (f2q_set_mate2) is not demultiplexed");
-    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a UMI context: sample barcodes and UMIs are not combined");
-    if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
-    if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a stagger context (f2q_set_stagger): the two are not combined");
-    if (c->indel.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on an indel context (f2q_set_indel): the two are not combined");
-    if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes on a parts context (f2q_set_parts): the two are not combined");
-    if (c->demux.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_sample_barcodes comes once, after f2q_create and before counting");
+    if (int rc = raw_mode_enter(c, RAW_DEMUX, "f2q_set_sample_barcodes")) return rc;
     std::string up, err;
     if (int rc = demux_validate(seqs, n, length, start, miss, up, err)) return fail(c, rc, err);
     HIPC(c, hipSetDevice(c->device));
@@ -946,12 +1028,8 @@ extern "C" int f2q_set_sample_barcodes(f2q_ctx *c, const char *seqs, uint32_t n,
     const char *e = getenv("F2Q_DEMUX_TABLE");
     const bool want_lds = e && !strcmp(e, "lds") ? true : e && !strcmp(e, "global") ? false : F2Q_DEMUX_TABLE_LDS_DEFAULT;
     c->demux.lds_table = want_lds && c->demux.tab.slots.size() <= F2Q_DEMUX_LDS_SLOTS;
-    c->demux.on = true;
-    if (c->have_lib) if (int rc = demux_alloc(c)) { c->demux.on = false; return rc; }      // (nothing else was touched: as if the call had not been made)
-    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
-    c->force_general = true;
-    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
-    c->plan.inband_n = false; c->plan.n_only = false;
+    if (c->have_lib) if (int rc = demux_alloc(c)) return rc;     // (the mode is not in place: as if the call had not been made)
+    raw_road_enter(c, RAW_DEMUX);
     if (c->trace) fprintf(stderr, "[f2q trace] sample barcodes: %u of %d bases at %d, %d mismatches; table %zu slots, %u entries, %u ambiguous, %s\n",
                           n, length, start, miss, c->demux.tab.slots.size(), c->demux.tab.entries, c->demux.tab.ambiguous, c->demux.lds_table ? "LDS" : "global");
     return F2Q_OK;
@@ -960,7 +1038,7 @@ extern "C" int f2q_set_sample_barcodes(f2q_ctx *c, const char *seqs, uint32_t n,
 extern "C" int f2q_read_demux(f2q_ctx *c, int64_t *matrix, int64_t *sample_stats, int64_t verdicts[5])
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->demux.on) return fail(c, F2Q_ESTATE, "not a demultiplexing context: call f2q_set_sample_barcodes first");
+    if (c->raw_mode != RAW_DEMUX) return fail(c, F2Q_ESTATE, "not a demultiplexing context: call f2q_set_sample_barcodes first");
     HIPC(c, hipSetDevice(c->device));
     const DemuxDev &d = c->demux.dev;
     const uint64_t nf = c->have_lib ? c->lib_h.n_features : 0, rows = (uint64_t)d.n + 1;
@@ -986,21 +1064,12 @@ extern "C" int f2q_set_strand(f2q_ctx *c, int32_t mode)
     if (mode != F2Q_STRAND_FWD && mode != F2Q_STRAND_REV && mode != F2Q_STRAND_BOTH)
         return fail(c, F2Q_EINVAL, "the strand mode is F2Q_STRAND_FWD (0), F2Q_STRAND_REV (1) or F2Q_STRAND_BOTH (2), not " + std::to_string(mode));
     if (mode == F2Q_STRAND_FWD) return F2Q_OK;               // the record as written: what every context does
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) takes a Counter context: Extract+Count on the reverse strand is not implemented");
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) takes single reads: a paired context (f2q_set_mate2) has its own orientation (rc2)");
-    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a UMI context: a strand mode and UMIs are not combined");
-    if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
-    if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a parts context (f2q_set_parts): the two are not combined");
-    if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on a stagger context (f2q_set_stagger): the two are not combined");
-    if (c->indel.on) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) on an indel context (f2q_set_indel): the two are not combined");
-    if (c->strand.mode || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_strand (rev / both) comes once, after f2q_create and before counting");
+    if (int rc = raw_mode_enter(c, RAW_STRAND, "f2q_set_strand (rev / both)")) return rc;
     HIPC(c, hipSetDevice(c->device));
-    c->strand.mode = mode; c->strand.dev = StrandDev{}; c->strand.dev.mode = mode;
-    if (c->have_lib) if (int rc = strand_alloc(c)) { c->strand.mode = 0; return rc; }      // (nothing else was touched: as if the call had not been made)
-    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
-    c->force_general = true;
-    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
-    c->plan.inband_n = false; c->plan.n_only = false;
+    c->strand.dev = StrandDev{}; c->strand.dev.mode = mode;
+    if (c->have_lib) if (int rc = strand_alloc(c)) return rc;    // (the mode is not in place: as if the call had not been made)
+    c->strand.mode = mode;
+    raw_road_enter(c, RAW_STRAND);
     if (c->trace) fprintf(stderr, "[f2q trace] strand mode %s: every read takes k_count_strand<%s>\n", mode == F2Q_STRAND_BOTH ? "both" : "rev", mode == F2Q_STRAND_BOTH ? "true" : "false");
     return F2Q_OK;
 }
@@ -1008,7 +1077,7 @@ extern "C" int f2q_set_strand(f2q_ctx *c, int32_t mode)
 extern "C" int f2q_read_strands(f2q_ctx *c, int64_t *rev_counts, int64_t extra[4])
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->strand.mode) return fail(c, F2Q_ESTATE, "no strand mode: call f2q_set_strand with F2Q_STRAND_REV or F2Q_STRAND_BOTH first");
+    if (c->raw_mode != RAW_STRAND) return fail(c, F2Q_ESTATE, "no strand mode: call f2q_set_strand with F2Q_STRAND_REV or F2Q_STRAND_BOTH first");
     HIPC(c, hipSetDevice(c->device));
     const uint64_t nf = c->have_lib ? c->lib_h.n_features : 0;
     std::vector<unsigned long long> h;
@@ -1023,53 +1092,50 @@ extern "C" int f2q_read_strands(f2q_ctx *c, int64_t *rev_counts, int64_t extra[4
 }
 
 // ---- staggered libraries: the ABI (include/f2q.h) ---------------------------------------------------------------------
-// the plan of a context that leaves the stagger road again: what f2q_create and f2q_set_features would have made of it
-static int stagger_replan(f2q_ctx *c)
+// A stagger or an indel context becomes a plain one again: what the mode held goes back, F2Q_FORCE_GENERAL says again what
+// it said, and the plan is what f2q_create and f2q_set_features would have made of it
+static int raw_road_leave(f2q_ctx *c)
 {
+    mode_drop(c);
+    c->raw_mode = RAW_NONE;
+    c->force_general = c->env_general;
     if (!c->have_lib) return setup_run(c);
     const std::string bytes((const char *)c->ix.feat_bytes.data(), c->ix.feat_bytes.size());      // (build_index rewrites c->ix)
     const std::vector<uint32_t> offs(c->ix.feat_off.begin(), c->ix.feat_off.end());
     return f2q_set_features(c, bytes.data(), offs.data(), c->ix.n_features);
 }
 
+// the shape f2q_set_stagger and f2q_set_indel ask of the run: what is wrong with it, for raw_mode_enter ("" when nothing is)
+static std::string one_fixed_window(const f2q_ctx *c)
+{
+    if (!c->run_h.fixed) return "takes a fixed window (--st): an anchored run (--us/--ds) finds its window itself";
+    if (c->run_h.n_iter != 1) return "takes exactly one window (--st with one value), not " + std::to_string(c->run_h.n_iter);
+    if (c->run_h.start[0] < 0) return "takes a window that starts at or after the first base (--st >= 0)";
+    return "";
+}
+
 extern "C" int f2q_set_stagger(f2q_ctx *c, int32_t n)
 {
     if (!c) return F2Q_EINVAL;
     if (n < 0 || n > F2Q_STAGGER_MAX) return fail(c, F2Q_EINVAL, "f2q_set_stagger takes 0 .. 32 extra starts, not " + std::to_string(n));
-    if (n == 0 && !c->stagger.n) return F2Q_OK;              // a plain context stays one: accepted at any time
+    if (n == 0 && c->raw_mode != RAW_STAGGER) return F2Q_OK; // a plain context stays one: accepted at any time
     if (c->counted) return fail(c, F2Q_ESTATE, "f2q_set_stagger comes before counting");
     if (n == 0) {                                            // a plain context again
         HIPC(c, hipSetDevice(c->device));
-        free_all(c, c->stagger.allocs);
-        c->stagger.n = 0; c->stagger.dev = StaggerDev{};
-        c->force_general = c->stagger.env_general;
-        return stagger_replan(c);
+        return raw_road_leave(c);
     }
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes a Counter context: Extract+Count with a stagger is not implemented");
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes single reads: a paired context (f2q_set_mate2) is not staggered");
-    if (!c->run_h.fixed) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes a fixed window (--st): an anchored run (--us/--ds) finds its window itself");
-    if (c->run_h.n_iter != 1) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes exactly one window (--st with one value), not " + std::to_string(c->run_h.n_iter));
-    if (c->run_h.start[0] < 0) return fail(c, F2Q_ESTATE, "f2q_set_stagger takes a window that starts at or after the first base (--st >= 0)");
-    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a UMI context: a stagger and UMIs are not combined");
-    if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
-    if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
-    if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on a parts context (f2q_set_parts): the two are not combined");
-    if (c->indel.on) return fail(c, F2Q_ESTATE, "f2q_set_stagger on an indel context (f2q_set_indel): the two are not combined");
+    if (int rc = raw_mode_enter(c, RAW_STAGGER, "f2q_set_stagger", one_fixed_window(c))) return rc;
     HIPC(c, hipSetDevice(c->device));
     unsigned long long *w = nullptr; std::vector<void *> owner;
     if (dev_alloc(c, 2 * ((size_t)n + 1), &w, owner, 0)) {
         free_all(c, owner);
         return fail(c, F2Q_ENOMEM, "no device memory for the offset histograms: " + c->err);
     }
-    if (!c->stagger.n) c->stagger.env_general = c->force_general;
-    free_all(c, c->stagger.allocs);
+    free_all(c, c->stagger.allocs);                          // (of an earlier call with another n)
     c->stagger.allocs = owner;
     c->stagger.n = n; c->stagger.dev.n = n; c->stagger.dev.hist = w;
     { const char *e = getenv("F2Q_STAGGER_WALK"); c->stagger.dev.walk = e && e[0] == '1'; }
-    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
-    c->force_general = true;
-    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
-    c->plan.inband_n = false; c->plan.n_only = false;
+    raw_road_enter(c, RAW_STAGGER);
     if (c->trace) fprintf(stderr, "[f2q trace] stagger %d: every read takes k_count_stagger (%s layout)\n", n, c->stagger.dev.walk ? "walk" : "span");
     return F2Q_OK;
 }
@@ -1077,7 +1143,7 @@ extern "C" int f2q_set_stagger(f2q_ctx *c, int32_t n)
 extern "C" int f2q_read_stagger(f2q_ctx *c, int64_t *perfect, int64_t *imperfect, int32_t n_offsets)
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->stagger.n) return fail(c, F2Q_ESTATE, "not a stagger context: call f2q_set_stagger with 1 .. 32 first");
+    if (c->raw_mode != RAW_STAGGER) return fail(c, F2Q_ESTATE, "not a stagger context: call f2q_set_stagger with 1 .. 32 first");
     if (n_offsets != c->stagger.n + 1) return fail(c, F2Q_EINVAL, "f2q_read_stagger takes n_offsets = n + 1 = " + std::to_string(c->stagger.n + 1) + ", not " + std::to_string(n_offsets));
     HIPC(c, hipSetDevice(c->device));
     unsigned long long h[2 * (F2Q_STAGGER_MAX + 1)];
@@ -1094,35 +1160,19 @@ extern "C" int f2q_read_stagger(f2q_ctx *c, int64_t *perfect, int64_t *imperfect
 extern "C" int f2q_set_indel(f2q_ctx *c, int32_t on)
 {
     if (!c) return F2Q_EINVAL;
-    if (!on && !c->indel.on) return F2Q_OK;                  // a plain context stays one: accepted at any time
+    if (!on && c->raw_mode != RAW_INDEL) return F2Q_OK;      // a plain context stays one: accepted at any time
     if (c->counted) return fail(c, F2Q_ESTATE, "f2q_set_indel comes before counting");
     if (!on) {                                               // a plain context again
         HIPC(c, hipSetDevice(c->device));
-        indel_drop(c);
-        c->indel.on = false;
-        c->force_general = c->indel.env_general;
-        return stagger_replan(c);
+        return raw_road_leave(c);
     }
-    if (c->indel.on) return F2Q_OK;
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_indel takes a Counter context: Extract+Count with indel reads is not implemented");
-    if (c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_indel takes single reads: a paired context (f2q_set_mate2) is not examined for indels");
-    if (!c->run_h.fixed) return fail(c, F2Q_ESTATE, "f2q_set_indel takes a fixed window (--st): an anchored run (--us/--ds) finds its window itself");
-    if (c->run_h.n_iter != 1) return fail(c, F2Q_ESTATE, "f2q_set_indel takes exactly one window (--st with one value), not " + std::to_string(c->run_h.n_iter));
-    if (c->run_h.start[0] < 0) return fail(c, F2Q_ESTATE, "f2q_set_indel takes a window that starts at or after the first base (--st >= 0)");
-    if (c->run_h.length < 2 || c->run_h.length > F2Q_REG_MAXLEN) return fail(c, F2Q_ESTATE, "f2q_set_indel takes a window length (--l) of 2 .. 31 bases, not " + std::to_string(c->run_h.length));
-    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_indel on a UMI context: indel reads and UMIs are not combined");
-    if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_indel on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
-    if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_indel on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
-    if (c->parts.on) return fail(c, F2Q_ESTATE, "f2q_set_indel on a parts context (f2q_set_parts): the two are not combined");
-    if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_indel on a stagger context (f2q_set_stagger): the two are not combined");
+    if (c->raw_mode == RAW_INDEL) return F2Q_OK;
+    std::string shape = one_fixed_window(c);
+    if (shape.empty() && (c->run_h.length < 2 || c->run_h.length > F2Q_REG_MAXLEN)) shape = "takes a window length (--l) of 2 .. 31 bases, not " + std::to_string(c->run_h.length);
+    if (int rc = raw_mode_enter(c, RAW_INDEL, "f2q_set_indel", shape)) return rc;
     HIPC(c, hipSetDevice(c->device));
-    c->indel.on = true;
-    if (int rc = indel_install(c, c->have_lib)) { c->indel.on = false; return rc; }
-    c->indel.env_general = c->force_general;
-    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
-    c->force_general = true;
-    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
-    c->plan.inband_n = false; c->plan.n_only = false;
+    if (int rc = indel_install(c, c->have_lib)) return rc;       // (the mode is not in place: as if the call had not been made)
+    raw_road_enter(c, RAW_INDEL);
     if (c->trace && !c->have_lib) fprintf(stderr, "[f2q trace] indel: every read takes k_count_indel; the deletion-variant table is built with the library\n");
     return F2Q_OK;
 }
@@ -1130,7 +1180,7 @@ extern "C" int f2q_set_indel(f2q_ctx *c, int32_t on)
 extern "C" int f2q_read_indels(f2q_ctx *c, int64_t *del_counts, int64_t *ins_counts, int64_t *del_pos, int64_t *ins_pos, int32_t n_pos, int64_t totals[4])
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->indel.on) return fail(c, F2Q_ESTATE, "not an indel context: call f2q_set_indel first");
+    if (c->raw_mode != RAW_INDEL) return fail(c, F2Q_ESTATE, "not an indel context: call f2q_set_indel first");
     const int32_t L = c->run_h.length;
     if (n_pos != L) return fail(c, F2Q_EINVAL, "f2q_read_indels takes n_pos = L = " + std::to_string(L) + ", not " + std::to_string(n_pos));
     HIPC(c, hipSetDevice(c->device));
@@ -1154,32 +1204,22 @@ extern "C" int f2q_read_indels(f2q_ctx *c, int64_t *del_counts, int64_t *ins_cou
 extern "C" int f2q_set_parts(f2q_ctx *c)
 {
     if (!c) return F2Q_EINVAL;
-    if (c->prm.mode != 0) return fail(c, F2Q_ESTATE, "f2q_set_parts takes a Counter context: Extract+Count assigns no read to a feature");
-    if (!c->run_h.fixed) return fail(c, F2Q_ESTATE, "f2q_set_parts takes fixed windows (--st): anchored runs (--us/--ds) are not implemented");
-    if (c->n_mate1 ? (c->n_mate1 != 1 || c->run_h.n_iter != 2) : c->run_h.n_iter != 2)
-        return fail(c, F2Q_ESTATE, c->n_mate1 ? "f2q_set_parts on a paired context takes one window per mate, not " + std::to_string(c->n_mate1) + " + " + std::to_string(c->run_h.n_iter - c->n_mate1)
-                                              : "f2q_set_parts takes exactly two windows (--st a,b), not " + std::to_string(c->run_h.n_iter));
-    if (c->umi.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on a UMI context: part verdicts and UMIs are not combined");
-    if (c->demux.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on a demultiplexing context (f2q_set_sample_barcodes): the two are not combined");
-    if (c->strand.mode) return fail(c, F2Q_ESTATE, "f2q_set_parts on a context with a strand mode (f2q_set_strand: rev / both): the two are not combined");
-    if (c->stagger.n) return fail(c, F2Q_ESTATE, "f2q_set_parts on a stagger context (f2q_set_stagger): the two are not combined");
-    if (c->indel.on) return fail(c, F2Q_ESTATE, "f2q_set_parts on an indel context (f2q_set_indel): the two are not combined");
-    if (c->parts.on || c->counted) return fail(c, F2Q_ESTATE, "f2q_set_parts comes once, after f2q_create (and f2q_set_mate2) and before counting");
+    std::string shape;
+    if (!c->run_h.fixed) shape = "takes fixed windows (--st): anchored runs (--us/--ds) are not implemented";
+    else if (c->n_mate1 && (c->n_mate1 != 1 || c->run_h.n_iter != 2)) shape = "on a paired context takes one window per mate, not " + std::to_string(c->n_mate1) + " + " + std::to_string(c->run_h.n_iter - c->n_mate1);
+    else if (c->run_h.n_iter != 2) shape = "takes exactly two windows (--st a,b), not " + std::to_string(c->run_h.n_iter);
+    if (int rc = raw_mode_enter(c, RAW_PARTS, "f2q_set_parts", shape)) return rc;
     HIPC(c, hipSetDevice(c->device));
-    { const char *e = getenv("F2Q_PARTS_SLOTS"); if (e && atol(e) > 0) { c->parts.min_slots = 2; while (c->parts.min_slots < (uint64_t)atol(e) && c->parts.min_slots < (1ull << 32)) c->parts.min_slots <<= 1; } }
     if (c->have_lib) if (int rc = parts_install(c, (const char *)c->ix.feat_bytes.data(), c->ix.feat_off.data(), c->ix.n_features)) return rc;   // (nothing else was touched: as if the call had not been made)
-    c->parts.on = true;
-    // every read takes the raw-record road (as F2Q_FORCE_GENERAL=1 does); f2q_set_features keeps it that way
-    c->force_general = true;
-    c->plan.fast_fixed = false; c->plan.fast_anchor = false; c->plan.multi = false; c->plan.multi_pair = false;
-    c->plan.inband_n = false; c->plan.n_only = false;
+    c->parts.set.min_slots = pairset_min_slots_from_env("F2Q_PARTS_SLOTS");
+    raw_road_enter(c, RAW_PARTS);
     return F2Q_OK;
 }
 
 extern "C" int f2q_parts_info(f2q_ctx *c, uint32_t *n1, uint32_t *n2)
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->parts.on) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
+    if (c->raw_mode != RAW_PARTS) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
     if (n1) *n1 = c->parts.tab.n(0);
     if (n2) *n2 = c->parts.tab.n(1);
     return F2Q_OK;
@@ -1188,7 +1228,7 @@ extern "C" int f2q_parts_info(f2q_ctx *c, uint32_t *n1, uint32_t *n2)
 extern "C" int f2q_read_parts(f2q_ctx *c, int64_t *parts_counts, int64_t *part1_reads, int64_t *part2_reads, int64_t classes[6])
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->parts.on) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
+    if (c->raw_mode != RAW_PARTS) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
     HIPC(c, hipSetDevice(c->device));
     const PartsDev &d = c->parts.dev;
     std::vector<unsigned long long> h;
@@ -1197,7 +1237,7 @@ extern "C" int f2q_read_parts(f2q_ctx *c, int64_t *parts_counts, int64_t *part1_
         HIPC(c, hipMemcpyAsync(h.data(), d.counts, c->parts.words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     }
     unsigned long long ctr[F2Q_UMI_CTR_WORDS];
-    if (int rc = parts_read_ctr(c, ctr)) return rc;
+    if (int rc = pairset_read_ctr(c, c->parts.set, ctr)) return rc;
     if (h.empty()) { if (classes) for (int k = 0; k < F2Q_PARTS_CLASSES; k++) classes[k] = 0; return F2Q_OK; }
     const uint64_t nf = c->lib_h.n_features, n1 = c->parts.tab.n(0), n2 = c->parts.tab.n(1);
     if (parts_counts) for (uint64_t i = 0; i < nf; i++) parts_counts[i] = (int64_t)h[i];
@@ -1211,12 +1251,12 @@ extern "C" int f2q_read_parts(f2q_ctx *c, int64_t *parts_counts, int64_t *part1_
 extern "C" int f2q_parts_recombinants(f2q_ctx *c, uint64_t cap, uint64_t *n, uint32_t *part1, uint32_t *part2, uint32_t *reads)
 {
     if (!c || !n) return F2Q_EINVAL;
-    if (!c->parts.on) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
+    if (c->raw_mode != RAW_PARTS) return fail(c, F2Q_ESTATE, "not a parts context: call f2q_set_parts first");
     HIPC(c, hipSetDevice(c->device));
     const PartsDev &d = c->parts.dev;
     unsigned long long ctr[F2Q_UMI_CTR_WORDS], recombinant = 0;
     if (d.classes) HIPC(c, hipMemcpyAsync(&recombinant, d.classes + F2Q_PARTS_RECOMBINANT, sizeof recombinant, hipMemcpyDeviceToHost, c->stream));
-    if (int rc = parts_read_ctr(c, ctr)) return rc;
+    if (int rc = pairset_read_ctr(c, c->parts.set, ctr)) return rc;
     if (recombinant >= (1ull << 32))
         return fail(c, F2Q_EUNSUPPORTED, "f2q_parts_recombinants: 2^32 or more recombinant reads -- a pair's 32-bit count may have wrapped");
     *n = ctr[F2Q_UMI_HELD];
@@ -1225,13 +1265,13 @@ extern "C" int f2q_parts_recombinants(f2q_ctx *c, uint64_t cap, uint64_t *n, uin
     if (!*n || !d.rec.slots) return F2Q_OK;
     std::vector<unsigned long long> words; std::vector<uint32_t> cnt;
     std::vector<std::pair<unsigned long long, uint32_t>> held;
-    try { words.resize(c->parts.n_slots); cnt.resize(c->parts.n_slots); held.reserve((size_t)*n); }
-    catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy a recombinant set of " + std::to_string(c->parts.n_slots) + " slots"); }
-    HIPC(c, hipMemcpyAsync(words.data(), d.rec.slots, c->parts.n_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(cnt.data(), d.rec.reads, c->parts.n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    try { words.resize(c->parts.set.n_slots); cnt.resize(c->parts.set.n_slots); held.reserve((size_t)*n); }
+    catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy a recombinant set of " + std::to_string(c->parts.set.n_slots) + " slots"); }
+    HIPC(c, hipMemcpyAsync(words.data(), d.rec.slots, c->parts.set.n_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(cnt.data(), d.rec.reads, c->parts.set.n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     uint64_t occupied = 0;
-    for (uint64_t i = 0; i < c->parts.n_slots; i++) if (words[i] != KEY_EMPTY && occupied++ < *n) held.emplace_back(words[i], cnt[i]);      // (never past the reserve)
+    for (uint64_t i = 0; i < c->parts.set.n_slots; i++) if (words[i] != KEY_EMPTY && occupied++ < *n) held.emplace_back(words[i], cnt[i]);      // (never past the reserve)
     if (occupied != *n) return fail(c, F2Q_EHIP, "the recombinant set holds " + std::to_string(occupied) + " pairs, its counter says " + std::to_string(*n));
     std::sort(held.begin(), held.end());                         // the word is (i1 << 32) | i2
     for (size_t i = 0; i < held.size(); i++) {
@@ -1692,92 +1732,61 @@ static int launch_fixed_v1(f2q_ctx *c, const PackedBlock &pb, Accum &acc, uint32
     return F2Q_OK;
 }
 
-// ---- distinct UMIs per feature -------------------------------------------------------------------------------------
-// the (feature, UMI) set before a launch over n records: afterwards it is at most half full even if every record brings a
-// new pair, so k_count_umi always finds room.  The pairs held are read from the device only when the bound kept on the
-// host says the set might be too small; a set that is grows to hold twice what it must (amortised rehash).  The new set
-// is allocated before the old one is given back: a failed allocation leaves the context as it was.  With reads kept
-// (f2q_set_umi_reads) reads[] comes and goes with slots[]: allocated zeroed next to it, filled by the rehash.
-static int umi_reserve(f2q_ctx *c, uint64_t n)
+// ---- pair sets: the (feature, UMI) set of a UMI context, the recombinant set of a parts context -----------------------
+// The set before a launch over n records: afterwards it is at most half full even if every record brings a new pair, so
+// the counting kernel always finds room.  The pairs held are read from the device only when the bound kept on the host
+// says the set might be too small; a set that is grows to hold twice what it must (amortised rehash).  The new set is
+// allocated before the old one is given back: a failed allocation leaves the context as it was.  With reads kept
+// (f2q_set_umi_reads; always for recombinants) reads[] comes and goes with slots[]: allocated zeroed next to it, filled by
+// the rehash.
+static int pairset_reserve(f2q_ctx *c, PairSet &s, uint64_t n)
 {
     int rc;
-    if (!c->umi.dev.umis) {
-        UmiDev u = c->umi.dev; std::vector<void *> owner;
-        if ((rc = dev_alloc(c, (size_t)std::max<uint64_t>(c->lib_h.n_features, 1), &u.umis, owner, 0)) ||
-            (rc = dev_alloc(c, (size_t)F2Q_UMI_CTR_WORDS, &u.ctr, owner, 0))) {
-            free_all(c, owner);
-            return fail(c, F2Q_ENOMEM, "no device memory for the UMI counters: " + c->err);
-        }
-        c->umi.dev.umis = u.umis; c->umi.dev.ctr = u.ctr; c->umi.fix_allocs = owner;
-    }
-    if (c->umi.dev.slots && 2 * (c->umi.held_ub + n) <= c->umi.n_slots) { c->umi.held_ub += n; return F2Q_OK; }
-    unsigned long long ctr[F2Q_UMI_CTR_WORDS] = {0, 0, 0, 0};
-    if (c->umi.dev.slots) {
-        if ((rc = umi_read_ctr(c, ctr))) return rc;
-        if (2 * (ctr[F2Q_UMI_HELD] + n) <= c->umi.n_slots) { c->umi.held_ub = ctr[F2Q_UMI_HELD] + n; return F2Q_OK; }
-    }
-    const uint64_t held = ctr[F2Q_UMI_HELD];
-    uint64_t slots = std::max<uint64_t>(c->umi.min_slots, 2);
-    while (slots < 2 * (held + n) || slots < 4 * held) slots <<= 1;
-    if (slots > (1ull << 32)) return fail(c, F2Q_ENOMEM, "the UMI set would exceed 2^32 slots");
-    UmiDev fresh = c->umi.dev; std::vector<void *> owner;
-    if ((rc = dev_alloc(c, (size_t)slots, &fresh.slots, owner, 0xFF)) ||
-        (c->umi.reads_on && (rc = dev_alloc(c, (size_t)slots, &fresh.reads, owner, 0)))) {
-        free_all(c, owner);
-        return fail(c, F2Q_ENOMEM, "no device memory for a UMI set of " + std::to_string(slots) + " slots: " + c->err);
-    }
-    fresh.mask = (uint32_t)(slots - 1);
-    if (c->umi.dev.slots && held) {
-        if (c->umi.dev.reads) hipLaunchKernelGGL(k_umi_rehash<true>, dim3((unsigned)((c->umi.n_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi.dev, fresh);
-        else hipLaunchKernelGGL(k_umi_rehash<false>, dim3((unsigned)((c->umi.n_slots + 255) / 256)), dim3(256), 0, c->stream, c->umi.dev, fresh);
-        HIPC(c, hipGetLastError());
-        c->umi.rehashes++;
-        if (c->trace) fprintf(stderr, "[f2q trace] UMI set rehash %llu: %llu pairs, %llu -> %llu slots\n", (unsigned long long)c->umi.rehashes,
-                              (unsigned long long)held, (unsigned long long)c->umi.n_slots, (unsigned long long)slots);
-    }
-    free_all(c, c->umi.set_allocs);                              // (waits for the stream)
-    c->umi.set_allocs = owner;
-    c->umi.dev.slots = fresh.slots; c->umi.dev.reads = fresh.reads; c->umi.dev.mask = fresh.mask; c->umi.n_slots = slots;
-    c->umi.held_ub = held + n;
-    return F2Q_OK;
-}
-
-// umi_reserve for the recombinant set of a parts context (f2q_set_parts): before a launch over n records the set is made
-// large enough to be at most half full afterwards even if every record brings a new pair; the pairs held are read from the
-// device only when the host's bound says the set might be too small; a set that is grows to hold twice what it must
-// (amortised doubling); the rehash (k_umi_rehash<true>) carries the reads; the new set is allocated before the old one is
-// given back, so a failed allocation leaves the context as it was.
-static int parts_reserve(f2q_ctx *c, uint64_t n)
-{
-    int rc;
-    UmiDev &u = c->parts.dev.rec;
-    if (u.slots && 2 * (c->parts.held_ub + n) <= c->parts.n_slots) { c->parts.held_ub += n; return F2Q_OK; }
+    UmiDev &u = *s.dev;
+    if (u.slots && 2 * (s.held_ub + n) <= s.n_slots) { s.held_ub += n; return F2Q_OK; }
     unsigned long long ctr[F2Q_UMI_CTR_WORDS] = {0, 0, 0, 0};
     if (u.slots) {
-        if ((rc = parts_read_ctr(c, ctr))) return rc;
-        if (2 * (ctr[F2Q_UMI_HELD] + n) <= c->parts.n_slots) { c->parts.held_ub = ctr[F2Q_UMI_HELD] + n; return F2Q_OK; }
+        if ((rc = pairset_read_ctr(c, s, ctr))) return rc;
+        if (2 * (ctr[F2Q_UMI_HELD] + n) <= s.n_slots) { s.held_ub = ctr[F2Q_UMI_HELD] + n; return F2Q_OK; }
     }
     const uint64_t held = ctr[F2Q_UMI_HELD];
-    uint64_t slots = std::max<uint64_t>(c->parts.min_slots, 2);
+    uint64_t slots = std::max<uint64_t>(s.min_slots, 2);
     while (slots < 2 * (held + n) || slots < 4 * held) slots <<= 1;
-    if (slots > (1ull << 32)) return fail(c, F2Q_ENOMEM, "the recombinant set would exceed 2^32 slots");
+    if (slots > (1ull << 32)) return fail(c, F2Q_ENOMEM, std::string("the ") + s.name + " set would exceed 2^32 slots");
     UmiDev fresh = u; std::vector<void *> owner;
-    if ((rc = dev_alloc(c, (size_t)slots, &fresh.slots, owner, 0xFF)) || (rc = dev_alloc(c, (size_t)slots, &fresh.reads, owner, 0))) {
+    if ((rc = dev_alloc(c, (size_t)slots, &fresh.slots, owner, 0xFF)) ||
+        (s.keep_reads && (rc = dev_alloc(c, (size_t)slots, &fresh.reads, owner, 0)))) {
         free_all(c, owner);
-        return fail(c, F2Q_ENOMEM, "no device memory for a recombinant set of " + std::to_string(slots) + " slots: " + c->err);
+        return fail(c, F2Q_ENOMEM, std::string("no device memory for a ") + s.name + " set of " + std::to_string(slots) + " slots: " + c->err);
     }
     fresh.mask = (uint32_t)(slots - 1);
     if (u.slots && held) {
-        hipLaunchKernelGGL(k_umi_rehash<true>, dim3((unsigned)((c->parts.n_slots + 255) / 256)), dim3(256), 0, c->stream, u, fresh);
+        if (u.reads) hipLaunchKernelGGL(k_umi_rehash<true>, dim3((unsigned)((s.n_slots + 255) / 256)), dim3(256), 0, c->stream, u, fresh);
+        else hipLaunchKernelGGL(k_umi_rehash<false>, dim3((unsigned)((s.n_slots + 255) / 256)), dim3(256), 0, c->stream, u, fresh);
         HIPC(c, hipGetLastError());
-        c->parts.rehashes++;
-        if (c->trace) fprintf(stderr, "[f2q trace] recombinant set rehash %llu: %llu pairs, %llu -> %llu slots\n", (unsigned long long)c->parts.rehashes,
-                              (unsigned long long)held, (unsigned long long)c->parts.n_slots, (unsigned long long)slots);
+        s.rehashes++;
+        if (c->trace) fprintf(stderr, "[f2q trace] %s set rehash %llu: %llu pairs, %llu -> %llu slots\n", s.name, (unsigned long long)s.rehashes,
+                              (unsigned long long)held, (unsigned long long)s.n_slots, (unsigned long long)slots);
     }
-    free_all(c, c->parts.set_allocs);                            // (waits for the stream)
-    c->parts.set_allocs = owner;
-    u.slots = fresh.slots; u.reads = fresh.reads; u.mask = fresh.mask; c->parts.n_slots = slots;
-    c->parts.held_ub = held + n;
+    free_all(c, s.set_allocs);                                   // (waits for the stream)
+    s.set_allocs = owner;
+    u.slots = fresh.slots; u.reads = fresh.reads; u.mask = fresh.mask; s.n_slots = slots;
+    s.held_ub = held + n;
+    return F2Q_OK;
+}
+
+// ---- distinct UMIs per feature -------------------------------------------------------------------------------------
+// umis[] and the set's counters, with the first launch after f2q_set_umi or a new library
+static int umi_counters(f2q_ctx *c)
+{
+    if (c->umi.dev.umis) return F2Q_OK;
+    UmiDev u = c->umi.dev; std::vector<void *> owner;
+    if (dev_alloc(c, (size_t)std::max<uint64_t>(c->lib_h.n_features, 1), &u.umis, owner, 0) ||
+        dev_alloc(c, (size_t)F2Q_UMI_CTR_WORDS, &u.ctr, owner, 0)) {
+        free_all(c, owner);
+        return fail(c, F2Q_ENOMEM, "no device memory for the UMI counters: " + c->err);
+    }
+    c->umi.dev.umis = u.umis; c->umi.dev.ctr = u.ctr; c->umi.fix_allocs = owner;
     return F2Q_OK;
 }
 
@@ -1821,25 +1830,25 @@ static int umi_run_stages(f2q_ctx *c, const std::vector<UmiStage> &stages, float
 extern "C" int f2q_umi_collapse(f2q_ctx *c, int32_t dist, int64_t *molecules, int64_t extra[2])
 {
     if (!c) return F2Q_EINVAL;
-    if (!c->umi.on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (c->raw_mode != RAW_UMI) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
     if (dist != 0 && dist != 1) return fail(c, F2Q_EINVAL, "UMIs are collapsed at Hamming distance 1 (or 0: as they are)");
     HIPC(c, hipSetDevice(c->device));
     const double t0 = now_ms();
     const uint64_t nf = c->lib_h.n_features;
     std::vector<unsigned long long> h(nf + 1, 0ull);             // molecules, edges
     float ms[3] = {0, 0, 0};
-    const UmiGeom g = umi_geometry(c, dist ? c->umi.n_slots : 0);     // (dist 0 launches nothing)
+    const UmiGeom g = umi_geometry(c, dist ? c->umi.set.n_slots : 0);     // (dist 0 launches nothing)
     const UmiDev &u = c->umi.dev;
     DevScope scratch(c);
     if (u.umis && u.slots && dist == 0) {                        // (nothing counted yet: all zero)
         if (nf) HIPC(c, hipMemcpyAsync(h.data(), u.umis, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     } else if (u.umis && u.slots) {
-        if (c->umi.n_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
+        if (c->umi.set.n_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
         uint32_t *parent = nullptr; unsigned long long *mol = nullptr;
-        if (dev_alloc(c, (size_t)c->umi.n_slots, &parent, scratch.v) || dev_alloc(c, (size_t)nf + 1, &mol, scratch.v, 0))
-            return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi.n_slots) + " slots: " + c->err);
+        if (dev_alloc(c, (size_t)c->umi.set.n_slots, &parent, scratch.v) || dev_alloc(c, (size_t)nf + 1, &mol, scratch.v, 0))
+            return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi.set.n_slots) + " slots: " + c->err);
         const std::vector<UmiStage> stages = {
-            {"k_umi_uf_init", [&] { hipLaunchKernelGGL(k_umi_uf_init, dim3(g.g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi.n_slots); }},
+            {"k_umi_uf_init", [&] { hipLaunchKernelGGL(k_umi_uf_init, dim3(g.g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi.set.n_slots); }},
             {"k_umi_link", [&] {
                 if (g.by_lane) hipLaunchKernelGGL(k_umi_link_lane, dim3(g.glink), dim3(g.wg), 0, c->stream, u, parent, mol + nf);
                 else hipLaunchKernelGGL(k_umi_link<false>, dim3(g.glink), dim3(g.wg), 0, c->stream, u, parent, (uint32_t *)nullptr, mol + nf); }},
@@ -1848,7 +1857,7 @@ extern "C" int f2q_umi_collapse(f2q_ctx *c, int32_t dist, int64_t *molecules, in
         HIPC(c, hipMemcpyAsync(h.data(), mol, (nf + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     }
     unsigned long long ctr[F2Q_UMI_CTR_WORDS];
-    if (int rc = umi_read_ctr(c, ctr)) return rc;
+    if (int rc = pairset_read_ctr(c, c->umi.set, ctr)) return rc;
     unsigned long long total = 0;
     for (uint64_t i = 0; i < nf; i++) { total += h[i]; if (molecules) molecules[i] = (int64_t)h[i]; }
     if (extra) { extra[0] = (int64_t)ctr[F2Q_UMI_HELD]; extra[1] = (int64_t)h[nf]; }
@@ -1860,10 +1869,10 @@ extern "C" int f2q_umi_collapse(f2q_ctx *c, int32_t dist, int64_t *molecules, in
 // the wrap of a 32-bit count excluded on the host: no pair can have 2^32 reads while the context has counted fewer
 static int umi_reads_ready(f2q_ctx *c, const char *who, unsigned long long ctr[F2Q_UMI_CTR_WORDS])
 {
-    if (!c->umi.on) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
-    if (!c->umi.reads_on) return fail(c, F2Q_ESTATE, std::string(who) + " needs the reads per pair: call f2q_set_umi_reads before counting");
+    if (c->raw_mode != RAW_UMI) return fail(c, F2Q_ESTATE, "not a UMI context: call f2q_set_umi first");
+    if (!c->umi.set.keep_reads) return fail(c, F2Q_ESTATE, std::string(who) + " needs the reads per pair: call f2q_set_umi_reads before counting");
     HIPC(c, hipSetDevice(c->device));
-    if (int rc = umi_read_ctr(c, ctr)) return rc;
+    if (int rc = pairset_read_ctr(c, c->umi.set, ctr)) return rc;
     if (ctr[F2Q_UMI_READS] >= (1ull << 32))
         return fail(c, F2Q_EUNSUPPORTED, std::string(who) + ": 2^32 or more reads with a valid UMI -- a pair's 32-bit count may have wrapped");
     return F2Q_OK;
@@ -1881,17 +1890,17 @@ extern "C" int f2q_umi_collapse_directional(f2q_ctx *c, int64_t *molecules, int6
     const uint64_t nf = c->lib_h.n_features;
     std::vector<unsigned long long> h(nf + 3, 0ull);             // molecules, edges, flagged slots, reads
     float ms[4] = {0, 0, 0, 0};
-    const UmiGeom g = umi_geometry(c, c->umi.n_slots);
+    const UmiGeom g = umi_geometry(c, c->umi.set.n_slots);
     const UmiDev &u = c->umi.dev;
     DevScope scratch(c);
     if (u.umis && u.slots && u.reads) {                          // (nothing counted yet: all zero)
-        if (c->umi.n_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
+        if (c->umi.set.n_slots > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the UMI set has more than 2^31 slots: too large to collapse");
         uint32_t *parent = nullptr, *dom = nullptr; unsigned long long *mol = nullptr;
-        if (dev_alloc(c, (size_t)c->umi.n_slots, &parent, scratch.v) || dev_alloc(c, (size_t)c->umi.n_slots, &dom, scratch.v, 0) ||
+        if (dev_alloc(c, (size_t)c->umi.set.n_slots, &parent, scratch.v) || dev_alloc(c, (size_t)c->umi.set.n_slots, &dom, scratch.v, 0) ||
             dev_alloc(c, (size_t)nf + 3, &mol, scratch.v, 0))
-            return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi.n_slots) + " slots: " + c->err);
+            return fail(c, F2Q_ENOMEM, "no device memory to collapse a UMI set of " + std::to_string(c->umi.set.n_slots) + " slots: " + c->err);
         const std::vector<UmiStage> stages = {
-            {"k_umi_uf_init", [&] { hipLaunchKernelGGL(k_umi_uf_init, dim3(g.g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi.n_slots); }},
+            {"k_umi_uf_init", [&] { hipLaunchKernelGGL(k_umi_uf_init, dim3(g.g256), dim3(256), 0, c->stream, parent, (unsigned long long)c->umi.set.n_slots); }},
             {"k_umi_link_dir", [&] { hipLaunchKernelGGL(k_umi_link<true>, dim3(g.glink), dim3(g.wg), 0, c->stream, u, parent, dom, mol + nf); }},
             {"k_umi_dir_spread", [&] { hipLaunchKernelGGL(k_umi_dir_spread, dim3(g.g256), dim3(256), 0, c->stream, u, (const uint32_t *)parent, dom); }},
             {"k_umi_dir_roots", [&] { hipLaunchKernelGGL(k_umi_dir_roots, dim3(g.g256), dim3(256), 0, c->stream, u, (const uint32_t *)parent, (const uint32_t *)dom, mol, mol + nf + 1); }}};
@@ -1920,13 +1929,13 @@ extern "C" int f2q_umi_pairs(f2q_ctx *c, uint64_t cap, uint64_t *n, uint32_t *fe
     std::vector<unsigned long long> words;                       // 12 bytes per slot on the host: a failure is F2Q_ENOMEM, not an exception
     std::vector<uint32_t> cnt;
     std::vector<std::pair<unsigned long long, uint32_t>> held;
-    try { words.resize(c->umi.n_slots); cnt.resize(c->umi.n_slots); held.reserve((size_t)*n); }
-    catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy a UMI set of " + std::to_string(c->umi.n_slots) + " slots"); }
-    HIPC(c, hipMemcpyAsync(words.data(), c->umi.dev.slots, c->umi.n_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, hipMemcpyAsync(cnt.data(), c->umi.dev.reads, c->umi.n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    try { words.resize(c->umi.set.n_slots); cnt.resize(c->umi.set.n_slots); held.reserve((size_t)*n); }
+    catch (const std::bad_alloc &) { return fail(c, F2Q_ENOMEM, "no host memory to copy a UMI set of " + std::to_string(c->umi.set.n_slots) + " slots"); }
+    HIPC(c, hipMemcpyAsync(words.data(), c->umi.dev.slots, c->umi.set.n_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(cnt.data(), c->umi.dev.reads, c->umi.set.n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, hipStreamSynchronize(c->stream));
     uint64_t occupied = 0;
-    for (uint64_t i = 0; i < c->umi.n_slots; i++) if (words[i] != KEY_EMPTY && occupied++ < *n) held.emplace_back(words[i], cnt[i]);      // (never past the reserve)
+    for (uint64_t i = 0; i < c->umi.set.n_slots; i++) if (words[i] != KEY_EMPTY && occupied++ < *n) held.emplace_back(words[i], cnt[i]);      // (never past the reserve)
     if (occupied != *n) return fail(c, F2Q_EHIP, "the UMI set holds " + std::to_string(occupied) + " pairs, its counter says " + std::to_string(*n));
     std::sort(held.begin(), held.end());                         // the word is (feature << 32) | codes
     for (size_t i = 0; i < held.size(); i++) {
@@ -1935,6 +1944,72 @@ extern "C" int f2q_umi_pairs(f2q_ctx *c, uint64_t cap, uint64_t *n, uint32_t *fe
         if (reads) reads[i] = held[i].second;
     }
     return F2Q_OK;
+}
+
+// The raw records of a view, one launch: the byte-exact routine per record, in the kernel of the context's mode -- the same
+// road with the (feature, UMI) set, the barcode verdict and the matrix, the reverse strand, the window at n + 1 starts, the
+// indel trial of the unassigned reads, or the part verdicts and the recombinant set.
+static int launch_raw(f2q_ctx *c, const RawBlock &rbv, Accum &acc, uint32_t &launches)
+{
+    int rc;
+    if ((rc = acc_ready(c))) return rc;                          // the raw-record kernels add to the accumulators directly
+    RawBlock rb = rbv;
+    rb.first_index += c->reads_seen;
+    const uint64_t wg = (rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
+    // kern(run, lib, tail...) over the records, with `shmem` bytes of dynamic LDS
+    auto launch = [&](const char *name, size_t shmem, auto kern, const auto &...tail) -> int {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(F2Q_GEN_THREADS), shmem, c->stream, c->run_d, c->lib_d, tail...);
+        HIPC(c, hipGetLastError());
+        launches++;
+        EC_POINT(c, name);
+        return F2Q_OK;
+    };
+    switch (c->raw_mode) {
+        case RAW_NONE:
+            return launch("k_count_general", 0, rb.len1 ? k_count_general<true> : k_count_general<false>, c->ec, rb, acc);
+        case RAW_UMI: {
+            if ((rc = umi_counters(c)) || (rc = pairset_reserve(c, c->umi.set, rb.n))) return rc;
+            const UmiDev &u = c->umi.dev;
+            const bool keep = u.reads != nullptr;
+            if (c->umi.hdr_sep) {                                // the UMI comes from the header (f2q_set_umi_header): rb.hdr_umi
+                if (!rb.hdr_umi) return fail(c, F2Q_ESTATE, "a block without header UMIs on a header-UMI context");
+                if (!rb.len1) return launch("k_count_umi (header)", 0, keep ? k_count_umi<true, true> : k_count_umi<false, true>, c->ec, rb, acc, u);
+                return launch("k_count_umi_pair (header)", 0, keep ? k_count_umi_pair<true, F2Q_UMI_PAIR_STAGE_DEFAULT, true> : k_count_umi_pair<false, F2Q_UMI_PAIR_STAGE_DEFAULT, true>, c->ec, rb, acc, u);
+            }
+            if (!rb.len1) return launch("k_count_umi", 0, keep ? k_count_umi<true> : k_count_umi<false>, c->ec, rb, acc, u);
+            // merged pairs (f2q_set_umi_paired): a pair is one record
+            if (!u.len1 && !u.len2) return fail(c, F2Q_ESTATE, "a block of pairs on a single-read UMI context");
+            if (c->umi.pair_stage) return launch("k_count_umi_pair", 0, keep ? k_count_umi_pair<true, true> : k_count_umi_pair<false, true>, c->ec, rb, acc, u);
+            return launch("k_count_umi_pair", 0, keep ? k_count_umi_pair<true, false> : k_count_umi_pair<false, false>, c->ec, rb, acc, u);
+        }
+        case RAW_DEMUX: {
+            if ((rc = demux_alloc(c))) return rc;                // (only after an allocation that failed: a retry)
+            const DemuxDev &d = c->demux.dev;
+            const bool lds = c->demux.lds_table;
+            const size_t shmem = (lds ? ((size_t)d.mask + 1) * 8 : 0) + ((size_t)d.n + 1) * 5 * 4;
+            // the most any context can ask for, so that dyn_lds sets it once: the attribute belongs to the kernel, not to the context
+            const size_t most = (lds ? (size_t)F2Q_DEMUX_LDS_SLOTS * 8 : 0) + ((size_t)F2Q_DEMUX_MAXN + 1) * 5 * 4;
+            if ((rc = dyn_lds(c, lds ? (const void *)k_count_demux<true> : (const void *)k_count_demux<false>, most))) return rc;
+            return launch("k_count_demux", shmem, lds ? k_count_demux<true> : k_count_demux<false>, c->ec, rb, acc, d);
+        }
+        case RAW_STRAND: {
+            if ((rc = strand_alloc(c))) return rc;               // (only after an allocation that failed: a retry)
+            const bool both = c->strand.mode == F2Q_STRAND_BOTH;
+            return launch(both ? "k_count_strand<both>" : "k_count_strand<rev>", 0, both ? k_count_strand<true> : k_count_strand<false>, c->ec, rb, acc, c->strand.dev);
+        }
+        case RAW_STAGGER:
+            return launch("k_count_stagger", 0, k_count_stagger, rb, acc, c->stagger.dev);
+        case RAW_INDEL:
+            if (!c->indel.dev.del_counts && (rc = indel_install(c, true))) return rc;      // (only after an allocation that failed: a retry)
+            if (!c->indel.dev.del_counts) return fail(c, F2Q_ESTATE, "an indel context without its table: f2q_set_features failed");
+            return launch("k_count_indel", 0, k_count_indel, c->ec, rb, acc, c->indel.dev);
+        case RAW_PARTS:
+            if (!c->parts.dev.counts) return fail(c, F2Q_ESTATE, "a parts context without its tables: f2q_set_features failed");
+            if ((rc = pairset_reserve(c, c->parts.set, rb.n))) return rc;
+            return launch(rb.len1 ? "k_count_parts<paired>" : "k_count_parts", 0, rb.len1 ? k_count_parts<true> : k_count_parts<false>, c->ec, rb, acc, c->parts.dev);
+    }
+    return fail(c, F2Q_ESTATE, "no such raw-record mode");
 }
 
 // one set of launches over a view of a block (all of it in Counter mode, a step of it in Extract+Count mode)
@@ -1962,95 +2037,7 @@ static int launch_view(f2q_ctx *c, const PackedBlock &pb, const RawBlock &rbv, A
         default:                    rc = launch_fixed_v1(c, pb, acc, launches); break;
     }
     if (rc || !rbv.n) return rc;
-    if ((rc = acc_ready(c))) return rc;                          // the raw-record kernels add to the accumulators directly
-    RawBlock rb = rbv;
-    rb.first_index += c->reads_seen;
-    const uint64_t wg = (rb.n + F2Q_GEN_THREADS - 1) / F2Q_GEN_THREADS;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(wg, (uint64_t)c->n_cu * 64u);
-    if (c->umi.on) {                                             // the same road with the (feature, UMI) set (f2q_set_umi)
-        if ((rc = umi_reserve(c, rb.n))) return rc;
-        if (c->umi.hdr_sep) {                                    // the UMI comes from the header (f2q_set_umi_header): rb.hdr_umi
-            if (!rb.hdr_umi) return fail(c, F2Q_ESTATE, "a block without header UMIs on a header-UMI context");
-            const bool keep = c->umi.dev.reads != nullptr;
-#define F2Q_LAUNCH_UMI_HDR(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev)
-            if (!rb.len1) { if (keep) F2Q_LAUNCH_UMI_HDR(k_count_umi<true, true>); else F2Q_LAUNCH_UMI_HDR(k_count_umi<false, true>); }
-            else if (keep) F2Q_LAUNCH_UMI_HDR(k_count_umi_pair<true, F2Q_UMI_PAIR_STAGE_DEFAULT, true>);
-            else F2Q_LAUNCH_UMI_HDR(k_count_umi_pair<false, F2Q_UMI_PAIR_STAGE_DEFAULT, true>);
-#undef F2Q_LAUNCH_UMI_HDR
-        }
-        else if (rb.len1) {                                      // merged pairs (f2q_set_umi_paired): a pair is one record
-            if (!c->umi.dev.len1 && !c->umi.dev.len2) return fail(c, F2Q_ESTATE, "a block of pairs on a single-read UMI context");
-            const bool keep = c->umi.dev.reads != nullptr;
-#define F2Q_LAUNCH_UMI_PAIR(R, S) hipLaunchKernelGGL((k_count_umi_pair<R, S>), dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev)
-            if (c->umi.pair_stage) { if (keep) F2Q_LAUNCH_UMI_PAIR(true, true); else F2Q_LAUNCH_UMI_PAIR(false, true); }
-            else { if (keep) F2Q_LAUNCH_UMI_PAIR(true, false); else F2Q_LAUNCH_UMI_PAIR(false, false); }
-#undef F2Q_LAUNCH_UMI_PAIR
-        }
-        else if (c->umi.dev.reads) hipLaunchKernelGGL(k_count_umi<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev);
-        else hipLaunchKernelGGL(k_count_umi<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->umi.dev);
-        HIPC(c, hipGetLastError());
-        launches++;
-        EC_POINT(c, c->umi.hdr_sep ? (rb.len1 ? "k_count_umi_pair (header)" : "k_count_umi (header)") : rb.len1 ? "k_count_umi_pair" : "k_count_umi");
-        return F2Q_OK;
-    }
-    if (c->demux.on) {                                           // the same road with the barcode verdict and the matrix (f2q_set_sample_barcodes)
-        if ((rc = demux_alloc(c))) return rc;                    // (only after an allocation that failed: a retry)
-        const DemuxDev &d = c->demux.dev;
-        const size_t shmem = (c->demux.lds_table ? ((size_t)d.mask + 1) * 8 : 0) + ((size_t)d.n + 1) * 5 * 4;
-        if (!c->demux.shmem_set) {                               // once per context, the most any context can ask for: the attribute belongs to the kernel, not to the context
-            const void *kern = c->demux.lds_table ? (const void *)k_count_demux<true> : (const void *)k_count_demux<false>;
-            const size_t most = (c->demux.lds_table ? (size_t)F2Q_DEMUX_LDS_SLOTS * 8 : 0) + ((size_t)F2Q_DEMUX_MAXN + 1) * 5 * 4;
-            HIPC(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-            c->demux.shmem_set = true;
-        }
-        if (c->demux.lds_table) hipLaunchKernelGGL(k_count_demux<true>, dim3(grid), dim3(F2Q_GEN_THREADS), shmem, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, d);
-        else hipLaunchKernelGGL(k_count_demux<false>, dim3(grid), dim3(F2Q_GEN_THREADS), shmem, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, d);
-        HIPC(c, hipGetLastError());
-        launches++;
-        EC_POINT(c, "k_count_demux");
-        return F2Q_OK;
-    }
-    if (c->strand.mode) {                                        // the same road on the reverse strand, or on both (f2q_set_strand)
-        if ((rc = strand_alloc(c))) return rc;                   // (only after an allocation that failed: a retry)
-        if (c->strand.mode == F2Q_STRAND_BOTH) hipLaunchKernelGGL(k_count_strand<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->strand.dev);
-        else hipLaunchKernelGGL(k_count_strand<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->strand.dev);
-        HIPC(c, hipGetLastError());
-        launches++;
-        EC_POINT(c, c->strand.mode == F2Q_STRAND_BOTH ? "k_count_strand<both>" : "k_count_strand<rev>");
-        return F2Q_OK;
-    }
-    if (c->stagger.n) {                                          // the same road with the window tried at n + 1 starts (f2q_set_stagger)
-        hipLaunchKernelGGL(k_count_stagger, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, rb, acc, c->stagger.dev);
-        HIPC(c, hipGetLastError());
-        launches++;
-        EC_POINT(c, "k_count_stagger");
-        return F2Q_OK;
-    }
-    if (c->indel.on) {                                           // the same road with the indel trial of the unassigned reads (f2q_set_indel)
-        if (!c->indel.dev.del_counts && (rc = indel_install(c, true))) return rc;      // (only after an allocation that failed: a retry)
-        if (!c->indel.dev.del_counts) return fail(c, F2Q_ESTATE, "an indel context without its table: f2q_set_features failed");
-        hipLaunchKernelGGL(k_count_indel, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->indel.dev);
-        HIPC(c, hipGetLastError());
-        launches++;
-        EC_POINT(c, "k_count_indel");
-        return F2Q_OK;
-    }
-    if (c->parts.on) {                                           // the same road with the part verdicts, the tables and the recombinant set (f2q_set_parts)
-        if (!c->parts.dev.counts) return fail(c, F2Q_ESTATE, "a parts context without its tables: f2q_set_features failed");
-        if ((rc = parts_reserve(c, rb.n))) return rc;
-        if (rb.len1) hipLaunchKernelGGL(k_count_parts<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->parts.dev);
-        else hipLaunchKernelGGL(k_count_parts<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc, c->parts.dev);
-        HIPC(c, hipGetLastError());
-        launches++;
-        EC_POINT(c, rb.len1 ? "k_count_parts<paired>" : "k_count_parts");
-        return F2Q_OK;
-    }
-    if (rb.len1) hipLaunchKernelGGL(k_count_general<true>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
-    else hipLaunchKernelGGL(k_count_general<false>, dim3(grid), dim3(F2Q_GEN_THREADS), 0, c->stream, c->run_d, c->lib_d, c->ec, rb, acc);
-    HIPC(c, hipGetLastError());
-    launches++;
-    EC_POINT(c, "k_count_general");
-    return F2Q_OK;
+    return launch_raw(c, rbv, acc, launches);
 }
 
 // ---- Extract+Count, anchored tiles, hot keys in LDS (EcHot, k_extract_anchor_hot) ---------------------------------
@@ -2184,14 +2171,7 @@ static int launch_block(f2q_ctx *c, const f2q_block *b, f2q_timing *t, hipEvent_
 {
     if (!k0) { k0 = c->ev_k0; k1 = c->ev_k1; }          // (a queued step brings its own pair)
     if (c->prm.mode == 0 && !c->have_lib) return fail(c, F2Q_ESTATE, "f2q_set_features must be called before counting in Counter mode");
-    if (c->umi.on && b->pb.n_tiles) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_umi: a UMI context counts raw records only");
-    if (c->stagger.n && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_stagger: a stagger context counts single raw records only");
-    if (c->indel.on && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_indel: an indel context counts single raw records only");
-    if (c->strand.mode && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_strand: a context with a strand mode counts single raw records only");
-    if (c->demux.on && (b->pb.n_tiles || b->rb.len1)) return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_sample_barcodes: a demultiplexing context counts single raw records only");
-    if (c->parts.on && (b->pb.n_tiles || (b->rb.n && (b->rb.len1 != nullptr) != (c->n_mate1 != 0))))
-        return fail(c, F2Q_ESTATE, "the block was packed before f2q_set_parts: a parts context counts raw records only");
-    if (c->umi.hdr_sep && b->rb.n && !b->rb.hdr_umi) return fail(c, F2Q_ESTATE, "the block was made before f2q_set_umi_header (or without headers): its records carry no header UMI");
+    if (c->raw_mode != RAW_NONE) if (int rc = raw_mode_block(c, b)) return rc;
     c->counted = true;
     Accum acc{c->acc_d, c->acc_d + (c->acc_n - 5), nullptr, nullptr, nullptr, nullptr, c->carry_d};
 #ifdef F2Q_STAMP
@@ -2714,12 +2694,7 @@ extern "C" int f2q_set_mate2(f2q_ctx *c, const int32_t *start2, int32_t n_start2
 {
     if (!c) return F2Q_EINVAL;
     if (c->have_lib || c->n_mate1) return fail(c, F2Q_ESTATE, "f2q_set_mate2 comes once, after f2q_create and before f2q_set_features");
-    if (c->umi.on) return fail(c, F2Q_ESTATE, "a UMI context (f2q_set_umi) counts single reads only: f2q_set_mate2 comes first, then f2q_set_umi_paired");
-    if (c->demux.on) return fail(c, F2Q_ESTATE, "a demultiplexing context (f2q_set_sample_barcodes) counts single reads only");
-    if (c->strand.mode) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts single reads only");
-    if (c->stagger.n) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts single reads only");
-    if (c->indel.on) return fail(c, F2Q_ESTATE, "an indel context (f2q_set_indel) counts single reads only");
-    if (c->parts.on) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) keeps its windows: f2q_set_mate2 comes first, then f2q_set_parts");
+    if (int rc = raw_mode_no_mate2(c)) return rc;
     if (!c->run_h.fixed) return fail(c, F2Q_EINVAL, "paired-end runs take fixed windows only (--st): anchored mates are not implemented");
     if (!start2 || n_start2 < 1 || c->prm.n_start + n_start2 > F2Q_MAX_ITER) return fail(c, F2Q_EINVAL, "mate 2 needs 1 .. 16 - n_start windows");
     for (int i = 0; i < n_start2; i++) if (start2[i] < 0) return fail(c, F2Q_EINVAL, "a mate-2 window starts before the mate");
@@ -3395,12 +3370,7 @@ static int count_file_impl(f2q_ctx *c, const char *path, uint32_t rank, uint32_t
 {
     if (!c || !path || world == 0 || rank >= world) return F2Q_EINVAL;
     if (int rc = single_only(c)) return rc;
-    if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
-    if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
-    if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
-    if (c->stagger.n && world > 1) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts whole files: the offset histograms of several ranks are not merged");
-    if (c->indel.on && world > 1) return fail(c, F2Q_ESTATE, "an indel context (f2q_set_indel) counts whole files: the indel counts of several ranks are not merged");
-    if (c->parts.on && world > 1) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) counts whole files: the tables and sets of several ranks are not merged");
+    if (int rc = raw_mode_one_rank(c, world)) return rc;
     HIPC(c, hipSetDevice(c->device));
     size_t CH = file_chunk_bytes((size_t)256 << 20);
     TextSource src;
@@ -3684,12 +3654,7 @@ extern "C" int f2q_count_pieces(f2q_ctx *c, const char *path, uint32_t rank, uin
 {
     if (!c || !path || !census || world == 0 || rank >= world || !piece_bytes_ok(piece_bytes)) return F2Q_EINVAL;
     if (int rc = single_only(c)) return rc;
-    if (c->umi.on && world > 1) return fail(c, F2Q_ESTATE, "a UMI context counts whole files: the sets of several ranks are not merged");
-    if (c->demux.on && world > 1) return fail(c, F2Q_ESTATE, "a demultiplexing context counts whole files: the matrices of several ranks are not merged");
-    if (c->strand.mode && world > 1) return fail(c, F2Q_ESTATE, "a context with a strand mode (f2q_set_strand: rev / both) counts whole files: the reverse-strand counts of several ranks are not merged");
-    if (c->stagger.n && world > 1) return fail(c, F2Q_ESTATE, "a stagger context (f2q_set_stagger) counts whole files: the offset histograms of several ranks are not merged");
-    if (c->indel.on && world > 1) return fail(c, F2Q_ESTATE, "an indel context (f2q_set_indel) counts whole files: the indel counts of several ranks are not merged");
-    if (c->parts.on && world > 1) return fail(c, F2Q_ESTATE, "a parts context (f2q_set_parts) counts whole files: the tables and sets of several ranks are not merged");
+    if (int rc = raw_mode_one_rank(c, world)) return rc;
     HIPC(c, hipSetDevice(c->device));
     TextSource src;
     { std::string err; if (src.open(path, err) != 0) return fail(c, F2Q_EIO, err); }

@@ -3,7 +3,7 @@
 // path, so every read or pair becomes a raw record, as f2q_set_parts leaves it -- and then, record by record, what a lane
 // of the kernel does: parts_read (general_read for the joined verdict, part_verdict twice, parts_class, the pair table, the
 // recombinant set through umi_claim_at / umi_read_add) of 2fast2q_amd/csrc/f2q_device.h, over tables built by
-// parts_validate / parts_build of f2q_host.h and a set sized by parts_reserve's rule (growth is umi_rehash_one<true> over
+// parts_validate / parts_build of f2q_host.h and a set sized by pairset_reserve's rule (growth is umi_rehash_one<true> over
 // every slot).  The product never uses this file.
 // -DF2Q_PARTS_EMU_MAIN: a stand-alone program over a built-in sample (for -fsanitize=address,undefined builds).
 #include <stdio.h>
@@ -65,7 +65,7 @@ static int ptemu_install(PtEmu *x, const char *seqs, const uint32_t *offs, uint3
     return F2Q_OK;
 }
 
-// room for n more pairs at a load of at most one half (parts_reserve)
+// room for n more pairs at a load of at most one half (pairset_reserve)
 static void ptemu_reserve(PtEmu *x, uint64_t n)
 {
     const uint64_t held = x->ctr[F2Q_UMI_HELD];

@@ -1,6 +1,6 @@
 // tests/emu/f2q_umi_emu.cpp -- TEST INFRASTRUCTURE.  The per-lane logic of k_count_umi (general_read with a UmiHook,
 // umi_codes / umi_insert / umi_claim of 2fast2q_amd/csrc/f2q_device.h) compiled with g++ and run record by record over
-// the existing emulation (f2q_emu.cpp, included whole), with the host's sizing rule (umi_reserve of f2q_lib.hip: at most
+// the existing emulation (f2q_emu.cpp, included whole), with the host's sizing rule (pairset_reserve of f2q_lib.hip: at most
 // half full after a block in which every record brings a new pair; growth is umi_rehash_one over every slot, as in
 // k_umi_rehash; with reads kept, reads[] is allocated zeroed with the set and filled by the rehash), so the CPU suite can
 // check it against the oracle.  The product never uses this file.

@@ -2,7 +2,7 @@
 // (f2q_pair_emu.cpp, included whole: frame_fastq twice + pack_pairs) with the plan of a paired UMI context -- no fast
 // path, so every pair becomes a merged raw record, as f2q_set_umi_paired leaves it -- and then, record by record, what a
 // lane of the kernel does: general_read<.., PAIRED> with a UmiPairHook (umi_codes_paired / umi_insert / umi_claim of
-// 2fast2q_amd/csrc/f2q_device.h) over a set sized by umi_reserve's rule (at most half full after a block in which every
+// 2fast2q_amd/csrc/f2q_device.h) over a set sized by pairset_reserve's rule (at most half full after a block in which every
 // pair is new; growth is umi_rehash_one over every slot).  The product never uses this file.
 // -DF2Q_UMI_PAIR_EMU_MAIN: a stand-alone program over a built-in sample (for -fsanitize=address,undefined builds).
 #include <stdio.h>
