@@ -22,6 +22,7 @@ EXPORTS = (
     "f2q_text_upload", "f2q_count_text", "f2q_text_free", "f2q_text_from_bgzf", "f2q_text_read",
     "f2q_set_mate2", "f2q_count_block_paired", "f2q_block_from_fastq_paired", "f2q_count_file_paired",
     "f2q_set_assign_library", "f2q_ec_assign", "f2q_ec_fetch_assigned",
+    "f2q_ec_collapse", "f2q_ec_fetch_collapsed",
     "f2q_set_umi", "f2q_read_umis", "f2q_umi_collapse",
     "f2q_set_umi_reads", "f2q_umi_collapse_directional", "f2q_umi_pairs",
     "f2q_set_umi_paired", "f2q_set_umi_header",
@@ -182,6 +183,8 @@ def load(path=None):
     L.f2q_set_assign_library.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32]
     L.f2q_ec_assign.argtypes = [vp, i64p, i64p, C.POINTER(Timing)]
     L.f2q_ec_fetch_assigned.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.f2q_ec_collapse.argtypes = [vp, C.c_int32, C.c_int32, i64p, C.POINTER(Timing)]
+    L.f2q_ec_fetch_collapsed.argtypes = [vp, u64p, i64p]
     L.f2q_set_umi.argtypes = [vp, C.c_int32, C.c_int32]
     L.f2q_set_umi_paired.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.f2q_set_umi_header.argtypes = [vp, C.c_int32, C.c_int32]
@@ -811,5 +814,40 @@ class Counter:
         raw = keys.raw
         rows = [(raw[int(offs[i]):int(offs[i + 1])].decode("latin-1"), int(counts[i]), int(first[i]), int(feat[i]), int(dist[i]))
                 for i in range(n)]
+        rows.sort(key=lambda r: r[2])
+        return rows
+
+    ECC_EXTRA = ("eligible_keys", "absorbed_keys", "absorbed_reads", "longest_chain")
+
+    def ec_collapse(self, dist=1, ratio=5, want_timing=False):
+        """fold every plain extracted key of at most 29 bases into its neighbour one substitution away with the most
+        reads, when that one has at least `ratio` times its reads (f2q_ec_collapse; dist 0: every key stays its own
+        centroid): the four counters as a dict (and the timing)"""
+        extra = np.zeros(4, dtype=np.int64)
+        t = Timing()
+        self._check(self._L.f2q_ec_collapse(self._h, int(dist), int(ratio), extra.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(t)))
+        out = dict(zip(self.ECC_EXTRA, (int(x) for x in extra)))
+        return (out, t.as_dict()) if want_timing else out
+
+    def ec_collapsed(self):
+        """[(key, reads, first_read, centroid_key, cluster_reads)] of the last ec_collapse in first-occurrence order;
+        cluster_reads is 0 for a key that is no centroid"""
+        nk, nb = C.c_uint64(), C.c_uint64()
+        self._check(self._L.f2q_ec_size(self._h, C.byref(nk), C.byref(nb)))
+        n = nk.value
+        keys = C.create_string_buffer(max(nb.value, 1))
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        first = np.zeros(max(n, 1), dtype=np.uint64)
+        cent = np.zeros(max(n, 1), dtype=np.uint64)
+        cluster = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self._L.f2q_ec_fetch_collapsed(self._h, cent.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                   cluster.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._check(self._L.f2q_ec_fetch(self._h, keys, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         counts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         first.ctypes.data_as(C.POINTER(C.c_uint64))))
+        raw = keys.raw
+        text = [raw[int(offs[i]):int(offs[i + 1])].decode("latin-1") for i in range(n)]
+        rows = [(text[i], int(counts[i]), int(first[i]), text[int(cent[i])], int(cluster[i])) for i in range(n)]
         rows.sort(key=lambda r: r[2])
         return rows

@@ -1032,6 +1032,102 @@ F2Q_HD void ec_count_key(const EcDev &ec, const KV &kv, unsigned long long read_
 }
 
 // ---------------------------------------------------------------------------------------------
+// Extract+Count keys one base apart collapsed (f2q_ec_collapse; the rule: ec_collapse of include/f2q.h)
+// ---------------------------------------------------------------------------------------------
+// A pass over the single-word table after counting: the table is written by earlier launches only (plain loads).  The
+// eligible keys are the plain ones of 1 .. 29 bases (length field 1 .. 29: no 'N' flag, not the empty key).  A key's
+// parent is its neighbour (same length, one base substituted) with the most reads among those with reads >= ratio * its
+// own; parent[], root[] are per slot, cluster[] is per slot with four counters behind it.
+#define F2Q_ECC_NONE 0xFFFFFFFFu
+#define F2Q_ECC_ELIGIBLE 0           // words of the counters behind cluster[]: eligible keys ...
+#define F2Q_ECC_ABSORBED 1           // ... keys with a parent ...
+#define F2Q_ECC_ABSORBED_READS 2     // ... their reads
+#define F2Q_ECC_CHAIN 3              // the longest parent chain (a maximum)
+#define F2Q_ECC_CTR_WORDS 4
+#define F2Q_ECC_MAXCHAIN 64u         // reads at least double along a chain (ratio >= 2), so 64-bit counts end it before this
+// the slot that holds word k, else F2Q_ECC_NONE: ec64_insert_word's hash and probe sequence, read-only
+F2Q_HD uint32_t ec64_find(const EcDev &ec, unsigned long long k)
+{
+    uint32_t s = hash32(k ^ (k >> 29), 32) & ec.k64_mask;
+    for (uint32_t guard = 0; guard <= ec.k64_mask; guard++) {
+        const unsigned long long v = gp(ec.k64_slots)[s];
+        if (v == k) return s;
+        if (v == KEY_EMPTY) return F2Q_ECC_NONE;
+        s = (s + 1) & ec.k64_mask;
+    }
+    return F2Q_ECC_NONE;
+}
+// the bases of an eligible key, 0: the slot is empty or its key is not eligible
+F2Q_HD uint32_t ecc_length(unsigned long long word)
+{
+    const uint32_t lf = (uint32_t)(word >> 58);
+    return word != KEY_EMPTY && lf >= 1u && lf <= (uint32_t)F2Q_EC64_MAXLEN ? lf : 0u;
+}
+// neighbour n (0 .. 3L-1) of key word k: base n / 3 replaced by the (n % 3)-th of the three other bases in the order
+// A < C < G < T, so n ascends by position, then by substituted base; the length field is never touched
+F2Q_HD unsigned long long ecc_neighbour(unsigned long long k, uint32_t n)
+{
+    const uint32_t j = n / 3u, r = n - 3u * j;
+    const uint32_t b = (uint32_t)(k >> (2u * j)) & 3u, nb = r < b ? r : r + 1u;
+    return k ^ ((unsigned long long)(b ^ nb) << (2u * j));
+}
+// a parent candidate: reads == 0 is "none" (a parent has at least ratio >= 2 reads)
+struct EccCand { unsigned long long reads; uint32_t slot, n; };
+F2Q_HD bool ecc_better(const EccCand &a, const EccCand &b)
+{
+    return a.reads > b.reads || (a.reads == b.reads && a.reads != 0ull && a.n < b.n);
+}
+// neighbour n of key k (c reads): when the table holds it with at least ratio * c reads (64 bits) it competes with `best`
+F2Q_HD void ecc_probe(const EcDev &ec, unsigned long long k, unsigned long long c, uint32_t ratio, uint32_t n, EccCand &best)
+{
+    const uint32_t s = ec64_find(ec, ecc_neighbour(k, n));
+    if (s == F2Q_ECC_NONE) return;
+    const unsigned long long cs = gp(ec.k64_count)[s] + 1ull;    // (the count word holds n - 1)
+    if (cs < (unsigned long long)ratio * c) return;
+    const EccCand x{cs, s, n};
+    if (ecc_better(x, best)) best = x;
+}
+// One lane of k_ec_parent_lane: slot s, its 3L look-ups one after the other.  parent[s] = s for an empty slot, a key that
+// is not eligible and a centroid
+F2Q_HD void ecc_parent_lane(const EcDev &ec, uint32_t *parent, uint32_t ratio, uint32_t s)
+{
+    const unsigned long long k = gp(ec.k64_slots)[s];
+    const uint32_t per = 3u * ecc_length(k);
+    EccCand best{0ull, s, 0u};
+    if (per) {
+        const unsigned long long c = gp(ec.k64_count)[s] + 1ull;
+        for (uint32_t n = 0; n < per; n++) ecc_probe(ec, k, c, ratio, n, best);
+    }
+    gpw(parent)[s] = best.slot;
+}
+// One lane of k_ec_roots, after the parents are final: slot s walks to the end of its chain, stores it and adds its reads
+// to the cluster of that slot.  tot: thread-local eligible keys, absorbed keys, their reads, the longest chain
+F2Q_HD void ecc_root_lane(const EcDev &ec, const uint32_t *parent, uint32_t *root, unsigned long long *cluster, uint32_t s,
+                          unsigned long long tot[F2Q_ECC_CTR_WORDS])
+{
+    const unsigned long long k = gp(ec.k64_slots)[s];
+    if (k == KEY_EMPTY) { gpw(root)[s] = s; return; }
+    const unsigned long long c = gp(ec.k64_count)[s] + 1ull;
+    uint32_t r = s, depth = 0;
+    for (uint32_t p = gp(parent)[r]; p != r && depth < F2Q_ECC_MAXCHAIN; p = gp(parent)[r]) { r = p; depth++; }
+    gpw(root)[s] = r;
+    acc_add(&cluster[r], c);
+    if (ecc_length(k)) tot[F2Q_ECC_ELIGIBLE]++;
+    if (depth) {
+        tot[F2Q_ECC_ABSORBED]++; tot[F2Q_ECC_ABSORBED_READS] += c;
+        if (depth > tot[F2Q_ECC_CHAIN]) tot[F2Q_ECC_CHAIN] = depth;
+    }
+}
+F2Q_HD void ecc_max(unsigned long long *p, unsigned long long v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)__hip_atomic_fetch_max(gpw(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    if (v > *p) *p = v;
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------
 // distinct UMIs per feature (--umi S,L: Counter mode, the byte-exact road only)
 // ---------------------------------------------------------------------------------------------
 // The UMI of a read is upper(seq[S:S+L]), 1 <= L <= 16: valid only when the read holds all L bases, each is A/C/G/T and

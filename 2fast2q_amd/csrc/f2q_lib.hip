@@ -33,6 +33,7 @@ using namespace f2q;
 #include "f2q_pair_kernels.h"
 #include "f2q_inflate_kernels.h"
 #include "f2q_assign_kernels.h"
+#include "f2q_ec_collapse_kernels.h"
 #include "f2q_umi_kernels.h"
 #include "f2q_demux_kernels.h"
 #include "f2q_strand_kernels.h"
@@ -156,6 +157,12 @@ struct f2q_ctx {
     AssignDev asg{};
     uint64_t asg_nb = 0, asg_nw = 0;     // entries / slots the per-key arrays cover
     uint64_t ec_gen = 1, asg_gen = 0;    // ec_gen: bumped by every count call, reset and table growth
+    // extracted keys one base apart collapsed (f2q_ec_collapse): root[] and cluster[] of the last call over the single-word
+    // slots (null: every key is its own centroid), valid while ecc_gen == ec_gen
+    std::vector<void *> ecc_allocs;
+    uint32_t *ecc_root = nullptr;
+    unsigned long long *ecc_cluster = nullptr;
+    uint64_t ecc_nb = 0, ecc_nw = 0, ecc_gen = 0;    // entries / slots the per-key arrays cover
     // The raw-record modes (RAW_MODES): at most one is in place.  Each sends every read down the raw-record road
     // (raw_road_enter) to a kernel of its own; its parameters and device memory live in its struct below
     RawMode raw_mode = RAW_NONE;
@@ -810,7 +817,7 @@ extern "C" void f2q_destroy(f2q_ctx *c)
                           (unsigned long long)c->n_malloc, c->tr_malloc, (unsigned long long)c->n_hipfree, c->tr_hipfree, (unsigned long long)c->n_reuse, c->tr_reserve, (unsigned long long)c->n_rehash);
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
     free_all(c, c->lib_allocs); free_all(c, c->ec_allocs); free_all(c, c->ec_allocs64); free_all(c, c->ec_allocs_ctr); free_all(c, c->hot_allocs);
-    free_all(c, c->asg_lib_allocs); free_all(c, c->asg_allocs);
+    free_all(c, c->asg_lib_allocs); free_all(c, c->asg_allocs); free_all(c, c->ecc_allocs);
     mode_drop(c);
     if (c->asg_acc_d) (void)hipFree(c->asg_acc_d);
     if (c->defer_d) (void)hipFree(c->defer_d);
@@ -4099,5 +4106,115 @@ extern "C" int f2q_ec_fetch_assigned(f2q_ctx *c, int32_t *feature, int32_t *dist
     };
     for (size_t e = 0; e < fb.size(); e++) put(fb[e], db[e]);
     for (size_t s = 0; s < fw.size(); s++) if (dw[s] != F2Q_ASG_EMPTY) put(fw[s], dw[s]);
+    return F2Q_OK;
+}
+
+// ---- Extract+Count: extracted keys one base apart collapsed ----------------------------------------------
+// A pass over the single-word table after counting (include/f2q.h: ec_collapse).  parent[], root[] and cluster[] (with the
+// four counters behind it) are scratch of 16 bytes per slot from the device-memory cache; root[] and cluster[] stay until
+// the next call for f2q_ec_fetch_collapsed.  The tables are only read, so the call changes nothing another call reads.
+// The parent launch is the lane-per-slot k_ec_parent_lane (F2Q_ECC_LINK=lane, and the default: on the 50 M-read workload it
+// measured 3 % faster than the wave-cooperative layout, profiles/r19_ec_collapse_rates.txt); F2Q_ECC_LINK=wave: k_ec_parent
+// (A/B runs, cross-checks)
+extern "C" int f2q_ec_collapse(f2q_ctx *c, int32_t dist, int32_t ratio, int64_t extra[4], f2q_timing *t)
+{
+    if (!c) return F2Q_EINVAL;
+    if (t) memset(t, 0, sizeof *t);
+    if (extra) memset(extra, 0, 4 * sizeof(int64_t));
+    if (c->prm.mode != 1) return fail(c, F2Q_ESTATE, "not in Extract+Count mode");
+    if (dist != 0 && dist != 1) return fail(c, F2Q_EINVAL, "extracted keys are collapsed at one mismatch (or 0: as they are)");
+    if (ratio < 2 || ratio > 255) return fail(c, F2Q_EINVAL, "the read ratio of a parent must be 2 .. 255");
+    HIPC(c, hipSetDevice(c->device));
+    const double t0 = now_ms();
+    // everything that still counts into the tables comes first, as in f2q_ec_assign
+    if (c->aux_busy) { HIPC(c, hipStreamSynchronize(c->aux_stream)); c->aux_busy = false; }
+    unsigned long long ctr[F2Q_CTR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int rc;
+    if (c->ec.ctr && (rc = ec_counters(c, ctr))) return rc;
+    const uint64_t nb = c->ec.slots ? ctr[0] : 0, nw = c->ec.k64_slots && ctr[3] && dist ? (uint64_t)c->ec.k64_mask + 1 : 0;
+    c->ecc_gen = 0;
+    free_all(c, c->ecc_allocs);
+    c->ecc_root = nullptr; c->ecc_cluster = nullptr;
+    if (nw > (1ull << 31)) return fail(c, F2Q_ENOMEM, "the single-word table has more than 2^31 slots: too large to collapse");
+    unsigned long long h[F2Q_ECC_CTR_WORDS] = {0, 0, 0, 0};
+    float ms = 0, ms_parent = 0;
+    struct Event { hipEvent_t e = nullptr; ~Event() { if (e) (void)hipEventDestroy(e); } } mid;      // F2Q_TRACE=1: between the two kernels
+    const char *e = getenv("F2Q_ECC_LINK");
+    const bool by_lane = !(e && !strcmp(e, "wave"));
+    uint32_t launches = 0;
+    if (nw) {
+        uint32_t *parent = nullptr;
+        if (dev_alloc(c, (size_t)nw, &parent, c->ecc_allocs) || dev_alloc(c, (size_t)nw, &c->ecc_root, c->ecc_allocs) ||
+            dev_alloc(c, (size_t)nw + F2Q_ECC_CTR_WORDS, &c->ecc_cluster, c->ecc_allocs)) {
+            free_all(c, c->ecc_allocs);
+            c->ecc_root = nullptr; c->ecc_cluster = nullptr;
+            return fail(c, F2Q_ENOMEM, "no device memory to collapse a table of " + std::to_string(nw) + " slots: " + c->err);
+        }
+        HIPC(c, hipMemsetAsync(c->ecc_cluster, 0, (nw + F2Q_ECC_CTR_WORDS) * sizeof(unsigned long long), c->stream));
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((nw + F2Q_ECC_THREADS - 1) / F2Q_ECC_THREADS, (uint64_t)c->n_cu * 8u);
+        HIPC(c, hipEventRecord(c->ev_k0, c->stream));
+        if (by_lane) hipLaunchKernelGGL(k_ec_parent_lane, dim3(grid), dim3(F2Q_ECC_THREADS), 0, c->stream, c->ec, parent, (uint32_t)ratio);
+        else hipLaunchKernelGGL(k_ec_parent, dim3(grid), dim3(F2Q_ECC_THREADS), 0, c->stream, c->ec, parent, (uint32_t)ratio);
+        HIPC(c, hipGetLastError());
+        EC_POINT(c, "k_ec_parent");
+        if (c->trace) { HIPC(c, hipEventCreate(&mid.e)); HIPC(c, hipEventRecord(mid.e, c->stream)); }
+        hipLaunchKernelGGL(k_ec_roots, dim3(grid), dim3(F2Q_ECC_THREADS), 0, c->stream, c->ec, (const uint32_t *)parent, c->ecc_root, c->ecc_cluster);
+        HIPC(c, hipGetLastError());
+        EC_POINT(c, "k_ec_roots");
+        HIPC(c, hipEventRecord(c->ev_k1, c->stream));
+        launches = 2;
+        HIPC(c, hipMemcpyAsync(h, c->ecc_cluster + nw, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (nw) HIPC(c, hipEventElapsedTime(&ms, c->ev_k0, c->ev_k1));
+    if (mid.e) HIPC(c, hipEventElapsedTime(&ms_parent, c->ev_k0, mid.e));
+    if (extra) for (int k = 0; k < F2Q_ECC_CTR_WORDS; k++) extra[k] = (int64_t)h[k];
+    if (t) { t->kernel_ms = ms; t->total_ms = now_ms() - t0; t->launches = launches; }
+    c->ecc_nb = nb; c->ecc_nw = nw; c->ecc_gen = c->ec_gen;
+    if (c->trace) fprintf(stderr, "[f2q trace] Extract+Count collapse (mismatches %d, ratio %d): %llu keys, %llu eligible, %llu absorbed with %llu reads, longest chain %llu, "
+                          "%.3f ms (kernels %.3f: k_ec_parent %.3f, k_ec_roots %.3f; %s, %llu slots)\n", dist, ratio, (unsigned long long)(ctr[0] + ctr[3]), h[0], h[1], h[2], h[3],
+                          now_ms() - t0, ms, ms_parent, ms - ms_parent,
+                          by_lane ? "lane" : "wave", (unsigned long long)nw);
+    return F2Q_OK;
+}
+
+extern "C" int f2q_ec_fetch_collapsed(f2q_ctx *c, uint64_t *centroid, int64_t *cluster_reads)
+{
+    if (!c) return F2Q_EINVAL;
+    if (c->prm.mode != 1) return fail(c, F2Q_ESTATE, "not in Extract+Count mode");
+    if (c->ecc_gen != c->ec_gen)
+        return fail(c, F2Q_ESTATE, "the Extract+Count tables have changed since the last f2q_ec_collapse (or it was never called)");
+    HIPC(c, hipSetDevice(c->device));
+    // f2q_ec_fetch's order: the byte-string entries (each its own centroid), then the occupied single-word slots
+    const size_t nb = (size_t)c->ecc_nb, ns = c->ec.k64_slots ? (size_t)c->ec.k64_mask + 1 : 0;
+    std::vector<unsigned long long> cnt(nb);
+    if (nb) HIPC(c, hipMemcpyAsync(cnt.data(), c->ec.ent_count, nb * 8, hipMemcpyDeviceToHost, c->stream));
+    std::vector<unsigned long long> ks(ns), kc(ns), cl(c->ecc_nw);
+    std::vector<uint32_t> root(c->ecc_nw);
+    if (ns) {
+        HIPC(c, hipMemcpyAsync(ks.data(), c->ec.k64_slots, ns * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(kc.data(), c->ec.k64_count, ns * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (c->ecc_nw) {
+        if (c->ecc_nw != ns) return fail(c, F2Q_ESTATE, "the single-word table is not the one f2q_ec_collapse walked");
+        HIPC(c, hipMemcpyAsync(root.data(), c->ecc_root, ns * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(cl.data(), c->ecc_cluster, ns * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < nb; i++) {
+        if (centroid) centroid[i] = i;
+        if (cluster_reads) cluster_reads[i] = (int64_t)cnt[i];
+    }
+    std::vector<uint64_t> index(ns);                             // slot -> position among the occupied slots
+    size_t o = nb;
+    for (size_t s = 0; s < ns; s++) if (ks[s] != KEY_EMPTY) index[s] = o++;
+    for (size_t s = 0; s < ns; s++) {
+        if (ks[s] == KEY_EMPTY) continue;
+        const bool walked = c->ecc_nw != 0;
+        const size_t r = walked ? root[s] : s;
+        if (r >= ns || ks[r] == KEY_EMPTY) return fail(c, F2Q_ESTATE, "slot " + std::to_string(s) + " of the single-word table has no centroid");
+        if (centroid) centroid[index[s]] = index[r];
+        if (cluster_reads) cluster_reads[index[s]] = (int64_t)(walked ? cl[s] : kc[s] + 1ull);      // (the count word holds n - 1)
+    }
     return F2Q_OK;
 }

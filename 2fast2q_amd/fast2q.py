@@ -308,6 +308,8 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
         raise RuntimeError("--as: assignments are not merged across several ranks; run one process")
     if param.get('umi') and sharding.world().size > 1:
         raise RuntimeError("--umi: the UMI sets are not merged across several ranks; run one process")
+    if param.get('ec_collapse') and sharding.world().size > 1:
+        raise RuntimeError("--ecm 1: the merged tables of several ranks are not collapsed; run one process")
     if param.get('umi_paired') and sharding.world().size > 1:
         raise RuntimeError("--umi1 / --umi2: the UMI sets are not merged across several ranks; run one process")
     if param.get('umi_header') and sharding.world().size > 1:
@@ -349,6 +351,11 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             # every key's feature (f2q_ec_assign)
             acounts, stats = ctx.ec_assign()
             param.setdefault('assigned', {})[raw] = ([int(n) for n in acounts], ctx.ec_assigned())
+        if param.get('ec_collapse') and not counter_mode:
+            # the sample's plain keys one base apart folded on the device (f2q_ec_collapse): the counters, every key's centroid
+            dist, ratio = param['ec_collapse']
+            extra = ctx.ec_collapse(dist, ratio)
+            param.setdefault('collapsed', {})[raw] = (extra, ctx.ec_collapsed())
         if umi_length(param):                       # distinct UMIs per feature and the two sample-level counters (f2q_read_umis)
             umis, umi_reads, umi_failed = ctx.read_umis()
             # the sample's record: per kind of UMI_TABLES that was computed, a number per feature and the sample-level counters
@@ -448,6 +455,16 @@ def aligner(i, raw, features, param, reads_stats):
             csv_writer(os.path.join(param["directory"], sample.name + "_assigned.csv"),
                        [["#key", "reads", "feature_name", "mismatches"]] +
                        [[key, n, names[f] if f >= 0 else "", d] for key, n, _first, f, d in arows])
+    if raw in param.get('collapsed', {}):            # --ecm 1: every key's centroid; the sample's column of <name>_collapsed.csv
+        extra, crows = param['collapsed'].pop(raw)
+        centroids = [(key, cluster) for key, _n, _first, cent, cluster in crows if cent == key]
+        param.setdefault("collapse_samples", {})[sample.name] = (
+            SampleResult(sample.name, value, unit, _sample_rows(centroids), dict(local)),
+            [len(crows), extra["eligible_keys"], extra["absorbed_keys"], len(centroids), extra["absorbed_reads"], extra["longest_chain"]])
+        if sharding.world().rank == 0:
+            os.makedirs(param["directory"], exist_ok=True)
+            csv_writer(os.path.join(param["directory"], sample.name + "_clusters.csv"),
+                       [["#key", "reads", "centroid", "cluster_reads"]] + [[key, n, cent, cluster] for key, n, _first, cent, cluster in crows])
     if raw in param.get('umi_counted', {}):          # --umi: the same rows once per kind, holding UMIs / molecules instead of reads
         rec = param['umi_counted'].pop(raw)
         pair_table = rec.pop("pair_table", None)
@@ -583,6 +600,9 @@ def initializer(cmd):
     if param.get('parts'):
         print(" Each of the two feature parts is also matched on its own; recombinant reads are counted per pair of parts")
         print(f" {PARTS_HEADER[1:]}")
+    if param.get('ec_collapse'):
+        print(" Extracted sequences of one sample that differ in one base are collapsed into the one with the most reads")
+        print(f" {ec_collapse_header(param)[1:]}")
     if param.get('umi_mismatch'):
         print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
     if param.get('umi_rule') == 'directional':
@@ -722,7 +742,11 @@ def input_parser(argv=None):
     ap.add_argument("--indel", nargs='?', const=True, help="Reads that the one fixed window (--st s --l L, L 2-31) assigns to no feature are tried as a one-base deletion and as a one-base insertion of every feature of L bases; they are reported per feature and per position (<name>_indel.csv, <name>_indel_positions.csv) and change no count. Counter mode, single reads, one --st value, one process")
     ap.add_argument("--parts", nargs='?', const=True, help="Pair libraries (features A:B over exactly two windows: --st a,b, or --pe --st a --st2 b): each part is also matched on its own with --m mismatches per part; reads whose two parts the library does not pair are counted as recombinants (<name>_parts.csv, <name>_recombinants.csv). Counter mode, one process")
     ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
+    ap.add_argument("--ecm", help="With --mo EC: mismatches among the extracted sequences, 0 (default) or 1. 1: per sample, every plain sequence of at most 29 bases is folded into the sequence one substitution away with the most reads, when that one has at least --ecr times its reads (<sample>_clusters.csv, <name>_collapsed.csv). One fixed window of at most 29 bases or one --us/--ds pair, single reads, one process")
+    ap.add_argument("--ecr", help="With --ecm 1: the reads a sequence needs, as a multiple of another's, to absorb it: 2-255 (default = 5)")
     args = ap.parse_args(argv)
+    if args.ecm is not None and args.ecm.strip() == "0" and args.ecr is None:
+        args.ecm = None                                         # --ecm 0 is a run without the flag
     if args.v is not None:
         print(f"\nVersion: {version}\n")
         sys.exit()
@@ -934,6 +958,12 @@ def input_parser(argv=None):
             colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
             sys.exit(2)
         p['assign'] = True
+    if args.ecm is not None or args.ecr is not None:
+        refusal = ec_collapse_refusal(args, p)
+        if refusal:
+            colourful_errors("FATAL", refusal)
+            sys.exit(2)
+        p['ec_collapse'] = (1, int(args.ecr) if args.ecr is not None else 5)
     for value, key in paths:                                   # :1178-1191
         if value is None:
             p[key] = os.getcwd()
@@ -948,6 +978,29 @@ def input_parser(argv=None):
         else:
             p[key] = value
     return p
+
+
+def ec_collapse_refusal(args, p):
+    """why --ecm / --ecr cannot be taken as given, else None (input_parser: before any output directory exists)"""
+    ecm = None if args.ecm is None else args.ecm.strip()
+    if ecm not in (None, "0", "1"):
+        return f"--ecm takes 0 or 1 (mismatches among the extracted sequences): --ecm {args.ecm} is not understood."
+    if ecm != "1":                                              # (--ecm 0 alone never gets here)
+        return f"--ecr {args.ecr} only has a meaning with --ecm 1: without it the extracted sequences are not collapsed."
+    if args.ecr is not None and not (re.fullmatch(r"[0-9]{1,4}", args.ecr.strip()) and 2 <= int(args.ecr) <= 255):
+        return f"--ecr takes a whole number from 2 to 255: --ecr {args.ecr} is not one."
+    if p['Running Mode'] != "EC":
+        return "--ecm 1 only has a meaning with --mo EC: Counter mode extracts no sequences to collapse."
+    if args.pe is not None:
+        return "--ecm 1 cannot be combined with --pe: the joined keys of a pair are not collapsed."
+    anchored = args.us is not None or args.ds is not None
+    if anchored and max(len(str(x).split(",")) for x in (args.us, args.ds) if x is not None) > 1:
+        return "--ecm 1 needs one --us/--ds pair: with several pairs every extracted sequence is a ':'-joined key and none could be collapsed."
+    if not anchored and len(str(p['start']).split(",")) > 1:
+        return f"--ecm 1 needs one window: with --st {p['start']} every extracted sequence is a ':'-joined key and none could be collapsed."
+    if not (args.us is not None and args.ds is not None) and p['length'] > 29:
+        return f"--ecm 1 collapses sequences of at most 29 bases: with --l {p['length']} none could be collapsed."
+    return None
 
 
 def file_sizer_split(param):
@@ -993,6 +1046,9 @@ def file_sizer_split(param):
         sys.exit(2)
     if param.get('umi') and sharding.world().size > 1:
         colourful_errors("FATAL", "--umi: the UMI sets are not merged across several ranks; run one process.")
+        sys.exit(2)
+    if param.get('ec_collapse') and sharding.world().size > 1:
+        colourful_errors("FATAL", "--ecm 1: the merged tables of several ranks live on the host and are not collapsed; run one process.")
         sys.exit(2)
     param["sequencing_files"] = {"len_files": len(files), "preprocess_files": files[:1], "files": files}
     return param
@@ -1054,6 +1110,15 @@ def _samples_from_directory(directory):
     return found
 
 
+def ec_collapse_header(param):
+    return "#Extracted sequences collapsed, mismatches, ratio: %d,%d" % param['ec_collapse']
+
+
+EC_COLLAPSE_STATS_HEAD = ["#Sample name (collapsed sequences)", "Number of distinct sequences", "Number of sequences that can be collapsed",
+                          "Number of sequences absorbed by another", "Number of centroids", "Number of reads of the absorbed sequences",
+                          "Longest chain of absorbed sequences"]
+
+
 def run_headers(param):
     """the '#key: value' lines that open <name>_stats.csv (:1323-1337)"""
     lines = [f"#2FAST2Q version: {param['version']}"]
@@ -1094,6 +1159,8 @@ def run_headers(param):
         lines.append(INDEL_HEADER)
     if param.get('parts'):
         lines.append(PARTS_HEADER)
+    if param.get('ec_collapse'):
+        lines.append(ec_collapse_header(param))
     return lines
 
 
@@ -1132,6 +1199,10 @@ def compiling(param):
         _, ahead, atable = compile_table(param["assign_samples"])
         csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_features.csv"),
                    [ahead] + [[feature] + counts for feature, counts in atable.items()])
+    if param.get("collapse_samples"):                # --ecm 1: <name>.csv's layout over the samples' centroids and their cluster reads
+        _, chead, ctable = compile_table({name: rec[0] for name, rec in param["collapse_samples"].items()})
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_collapsed.csv"),
+                   [chead] + [[feature] + counts for feature, counts in ctable.items()])
     for kind, suffix, _, _, _ in UMI_TABLES:         # --umi / --mu 1 / --mur directional: <name>.csv's layout and row order per kind
         per_sample = {name: rec[kind] for name, rec in param.get("umi_samples", {}).items() if kind in rec}
         if per_sample:
@@ -1259,6 +1330,9 @@ def run_stats(headers, param, compiled, head, ordered):
         global_stat += [PARTS_STATS_HEAD] + [
             [s.name, c["pair_perfect"], c["pair_imperfect"], c["recombinant"], len(parts[s.name][1]), c["part1_only"], c["part2_only"], c["neither"]]
             for s in ordered if s.name in parts for c in [parts[s.name][2]]]
+    coll = param.get("collapse_samples", {})
+    if coll:                                                     # --ecm 1: the collapse of each file
+        global_stat += [EC_COLLAPSE_STATS_HEAD] + [[s.name] + coll[s.name][1] for s in ordered if s.name in coll]
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib

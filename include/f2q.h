@@ -298,6 +298,59 @@ int f2q_ec_assign(f2q_ctx *ctx, int64_t *counts, int64_t stats[5], f2q_timing *t
  * changed since that f2q_ec_assign (a counting call, f2q_reset_counts) or it was never called. */
 int f2q_ec_fetch_assigned(f2q_ctx *ctx, int32_t *feature, int32_t *dist);
 
+/* ---- Extract+Count without a library: extracted keys one base apart collapsed -----------------
+ * Random-barcode pools, lineage barcodes, Tn-seq tags: most distinct keys of such a run are sequencing errors of a few
+ * true ones.  The reference has no counterpart and no outside tool is reproduced; the rule below is the specification
+ * (it is in the spirit of message passing between Hamming neighbours, with ONE best parent per key so that the outcome
+ * is a function of the key -> reads table alone: not of read order, table size or growth history).
+ *
+ *     def eligible(key):                                   # plain keys of the single-word table
+ *         return 1 <= len(key) <= 29 and set(key) <= set("ACGT")
+ *
+ *     def ec_collapse(table, ratio):                       # table: {key: reads}  ->  {key: (centroid, cluster_reads)}
+ *         parent = {}
+ *         for b, nb in table.items():
+ *             if not eligible(b):
+ *                 continue                                 # never a child, never a parent
+ *             best = None
+ *             for j in range(len(b)):                      # the earliest substituted position wins a tie ...
+ *                 for x in "ACGT":                         # ... then the alphabetically smallest substituted base
+ *                     if x == b[j]:
+ *                         continue
+ *                     a = b[:j] + x + b[j + 1:]            # same length, one substitution; `a` is eligible as `b` is
+ *                     if a in table and table[a] >= ratio * nb and (best is None or table[a] > table[best]):
+ *                         best = a
+ *             if best is not None:
+ *                 parent[b] = best                         # ratio >= 2: a parent has strictly more reads, a forest
+ *         def centroid(k):
+ *             while k in parent:
+ *                 k = parent[k]
+ *             return k
+ *         cluster = dict.fromkeys(table, 0)
+ *         for k, n in table.items():
+ *             cluster[centroid(k)] += n
+ *         return {k: (centroid(k), cluster[k]) for k in table}         # cluster_reads of a non-centroid is 0
+ *
+ * Keys with an 'N', keys longer than 29 bases, ':'-joined keys of several parts, the empty key and everything else the
+ * byte-string table holds are their own centroids with their own reads.  The comparison is made in 64 bits.
+ *
+ * f2q_ec_collapse: dist 1 collapses the keys the tables hold NOW; dist 0 makes every key its own centroid (all four
+ * counters zero, nothing launched); any other dist, or a ratio outside 2 .. 255, is F2Q_EINVAL.  extra = eligible keys,
+ * absorbed keys (keys with a parent), the reads of the absorbed keys, the longest parent chain.  The call is ordered
+ * after everything that still counts into the tables, as f2q_ec_assign is, and synchronises the stream; t->kernel_ms is
+ * the HIP-event time of its two kernels.  The result is computed afresh by every call, the call may come any number of
+ * times, also between counting calls, and changes nothing another call reads.  F2Q_ESTATE on a Counter context,
+ * F2Q_ENOMEM when the scratch (16 bytes per slot of the single-word table) cannot be had: the tables stay intact.
+ *
+ * f2q_ec_fetch_collapsed: per key, in exactly the order f2q_ec_fetch returns the keys: centroid[i] = the index, in that
+ * order, of key i's centroid (i itself for a centroid), cluster_reads[i] as in the rule; arrays of n_keys (f2q_ec_size)
+ * entries, either may be NULL.  F2Q_ESTATE when the tables have changed since that f2q_ec_collapse (a counting call,
+ * f2q_reset_counts, a growth) or it was never called.
+ * Not implemented: two mismatches, insertions and deletions between keys, keys with 'N' or longer than 29 bases,
+ * multi-part and paired keys, collapsing across samples or ranks, a child's reads split among several parents. */
+int f2q_ec_collapse(f2q_ctx *ctx, int32_t dist, int32_t ratio, int64_t extra[4], f2q_timing *t);
+int f2q_ec_fetch_collapsed(f2q_ctx *ctx, uint64_t *centroid, int64_t *cluster_reads);
+
 /* ---- distinct UMIs per feature ---------------------------------------------------------------
  * Libraries with an inline UMI next to the feature: how many MOLECULES does a feature's read count stand for?  The
  * reference has no counterpart; the verdict of every read stays the reference's (fast2q.py:362-380), so counts, the
