@@ -23,6 +23,7 @@ struct Emu {
     std::vector<unsigned long long> acc;      // counts + 5 stats
     EcDev ec; std::vector<unsigned long long> slots, ent_off, ent_count, ent_first, ctr, k64s, k64c, k64f; std::vector<uint32_t> ent_len, arena;
     uint64_t reads_seen = 0, fast = 0, general = 0, v2_reads = 0, anchor_reads = 0;
+    uint64_t pairs_slow = 0;                  // reads pairs_lane hands to the byte-exact routine (k_count_anchor_pairs: anchor_slow)
     int use_v2 = 1, use_lt = 1, use_pw = 1;
     uint64_t lt_reads = 0, pt_reads = 0;
     std::string err;
@@ -134,6 +135,7 @@ size_t emu_count_block(void *h, const uint8_t *buf, size_t n)
                 uint8_t kb[F2Q_PAIRS_KEYMAX];
                 const int res = pairs_lane<NW, KB>(e->run, e->lib, e->ec, kb, LO, HI, FLG, r, FU, FD, FW, gi, idx, nullptr, !lower);
                 if (res < 0) {
+                    e->pairs_slow++;
                     uint8_t sq[F2Q_ANCHOR_MAXLEN], ql[F2Q_ANCHOR_MAXLEN];
                     for (int i = 0; i < r; i++) {
                         sq[i] = (uint8_t)"ACGT"[((LO[i >> 5] >> (i & 31)) & 1u) | (((HI[i >> 5] >> (i & 31)) & 1u) << 1)];
@@ -526,6 +528,29 @@ uint64_t emu_pt_reads(void *h) { return ((Emu *)h)->pt_reads; }
 int emu_pt_parts(void *h) { return ((Emu *)h)->ix.pt.ok ? (int)((Emu *)h)->ix.pt.n_parts : 0; }
 uint64_t emu_v2_reads(void *h) { return ((Emu *)h)->v2_reads; }
 uint64_t emu_anchor_reads(void *h) { return ((Emu *)h)->anchor_reads; }
+uint64_t emu_pairs_slow(void *h) { return ((Emu *)h)->pairs_slow; }
+// the byte-string index as build_gk left it (read-only): gk_tab, and per group the GkGroup as 8 + 2 * F2Q_GK_MAXP + 1 words
+// (len, n, ids_off, exact_off, bits, n_pieces, F2Q_GK_MAXP, F2Q_GK_MAXW, piece_off[], cut[]).  Each returns the words
+// there are and writes at most cap of them.
+uint64_t emu_gk_tab(void *h, uint32_t *out, uint64_t cap)
+{
+    Emu *e = (Emu *)h;
+    for (uint64_t i = 0; i < e->ix.gk_tab.size() && i < cap; i++) out[i] = e->ix.gk_tab[i];
+    return e->ix.gk_tab.size();
+}
+uint64_t emu_gk_groups(void *h, uint32_t *out, uint64_t cap)
+{
+    Emu *e = (Emu *)h;
+    const uint64_t per = 8 + 2 * F2Q_GK_MAXP + 1, n = e->lib.gk.n_groups;
+    for (uint64_t gi = 0; gi < n && (gi + 1) * per <= cap; gi++) {
+        const GkGroup &g = e->ix.gk_groups[gi];
+        uint32_t *o = out + gi * per;
+        o[0] = g.len; o[1] = g.n; o[2] = g.ids_off; o[3] = g.exact_off; o[4] = g.bits; o[5] = g.n_pieces; o[6] = F2Q_GK_MAXP; o[7] = F2Q_GK_MAXW;
+        for (int p = 0; p < F2Q_GK_MAXP; p++) o[8 + p] = g.piece_off[p];
+        for (int p = 0; p <= F2Q_GK_MAXP; p++) o[8 + F2Q_GK_MAXP + p] = g.cut[p];
+    }
+    return n * per;
+}
 // entries: first the byte-string table, then the occupied slots of the single-word table
 static std::vector<size_t> k64_live(Emu *e) { std::vector<size_t> v; for (size_t i = 0; i < e->k64s.size(); i++) if (e->k64s[i] != ~0ull) v.push_back(i); return v; }
 uint64_t emu_ec_n(void *h) { Emu *e = (Emu *)h; return e->ctr[0] + k64_live(e).size(); }

@@ -56,6 +56,11 @@ def lib():
         L.emu_pt_parts.argtypes = [vp]
         L.emu_anchor_reads.restype = C.c_uint64
         L.emu_anchor_reads.argtypes = [vp]
+        L.emu_pairs_slow.restype = C.c_uint64
+        L.emu_pairs_slow.argtypes = [vp]
+        for fn in (L.emu_gk_tab, L.emu_gk_groups):
+            fn.restype = C.c_uint64
+            fn.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64]
         L.emu_ec_n.restype = C.c_uint64
         L.emu_ec_n.argtypes = [vp]
         L.emu_ec_overflow.restype = C.c_uint64
@@ -135,6 +140,28 @@ class Emu:
 
     def anchor_reads(self):
         return lib().emu_anchor_reads(self._h)
+
+    def pairs_slow(self):
+        """reads of a several-pair run that pairs_lane handed to the byte-exact routine"""
+        return lib().emu_pairs_slow(self._h)
+
+    def gk(self):
+        """the byte-string index build_gk made of the library: (gk_tab as a list, the groups as dicts; `maxp` and `maxw`
+        are F2Q_GK_MAXP and F2Q_GK_MAXW)"""
+        out = []
+        for fn in (lib().emu_gk_tab, lib().emu_gk_groups):
+            n = fn(self._h, None, 0)
+            buf = (C.c_uint32 * max(n, 1))()
+            assert fn(self._h, buf, n) == n
+            out.append(list(buf)[:n])
+        tab, words = out
+        groups = []
+        for i in range(0, len(words), 8 + 2 * 8 + 1):
+            w = words[i:i + 25]
+            assert w[6] == 8
+            groups.append(dict(len=w[0], n=w[1], ids_off=w[2], exact_off=w[3], bits=w[4], n_pieces=w[5], maxp=w[6], maxw=w[7],
+                               piece_off=w[8:8 + w[5]], cut=w[16:16 + w[5] + 1]))
+        return tab, groups
 
     def read(self):
         counts = (C.c_int64 * max(self.n, 1))()

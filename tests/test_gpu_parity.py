@@ -687,7 +687,7 @@ def test_multi_window_lds_kernel_vs_oracle(P, monkeypatch, miss, starts, length,
     assert res[0][1] == short and res[1][1] == short and res[2][1] == 40000
 
 
-@pytest.mark.parametrize("miss", [0, 1, 3])
+@pytest.mark.parametrize("miss", [0, 1, 3, 7])
 @pytest.mark.parametrize("glen", [12, 40])
 def test_general_key_index_kernel_vs_oracle(P, miss, glen):
     """k_count_general over the byte-string index (GkDesc): a library with odd symbols, three lengths and near-duplicates,
