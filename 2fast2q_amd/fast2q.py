@@ -29,7 +29,8 @@ import re
 import sys
 import threading
 import time
-from dataclasses import dataclass
+from collections import namedtuple
+from dataclasses import dataclass, field
 from pathlib import Path
 
 from . import binding, sharding
@@ -140,39 +141,14 @@ def sample_barcodes_loader(path):
 
 
 def _counter_kwargs(param):
-    if param.get('paired'):                         # a paired context: the windows of mate 2 and its direction (f2q_set_mate2)
-        plain = {k: v for k, v in param.items() if k != 'paired'}
-        kwargs = dict(_counter_kwargs(plain), start2=param['start2'], rc2=bool(param.get('rc2')))
-        if param.get('umi_paired'):                 # --umi1 / --umi2: a paired UMI context (f2q_set_umi_paired), part of the key too
-            kwargs['umi_paired'] = tuple(param['umi_paired'])
-            if param.get('umi_rule') == 'directional':
-                kwargs['umi_reads'] = True
-        return kwargs                               # (--umih: the plain keys carry it; the UMI of a pair is in mate 1's header)
+    """the keyword arguments of the run's context: the core ones, then what every option of the run adds"""
     kwargs = dict(mode=param['Running Mode'], miss=param['miss'], phred=param['phred'], length=param['length'],
                   start=param['start'], upstream=param['upstream'], downstream=param['downstream'],
                   miss_search_up=param['miss_search_up'], miss_search_down=param['miss_search_down'],
                   qual_up=param['qual_up'], qual_down=param['qual_down'],
                   device=int(param.get('device', os.environ.get("F2Q_DEVICE", os.environ.get("LOCAL_RANK", 0)))))
-    if param.get('umi'):                            # a UMI context (f2q_set_umi); part of the key contexts are kept under
-        kwargs['umi'] = tuple(param['umi'])         # (--mu is not: collapsing changes no context)
-        if param.get('umi_rule') == 'directional':  # --mur directional: the context keeps the reads of every pair (f2q_set_umi_reads)
-            kwargs['umi_reads'] = True
-    if param.get('umi_header'):                     # --umih: the UMI is in the read header (f2q_set_umi_header)
-        kwargs['umi_header'] = tuple(param['umi_header'])
-        if param.get('umi_rule') == 'directional':
-            kwargs['umi_reads'] = True
-    if param.get('sample_barcodes'):                # --sb: a demultiplexing context (f2q_set_sample_barcodes); part of the key too
-        sb = param['sample_barcodes']
-        kwargs['sample_barcodes'] = (sb['start'], tuple(sb['barcodes']))
-        kwargs['barcode_mismatch'] = sb['miss']
-    if param.get('strand'):                         # --strand rev / both (f2q_set_strand); part of the key too
-        kwargs['strand'] = param['strand']
-    if param.get('parts'):                          # --parts: each part of a pair library matched alone (f2q_set_parts); part of the key too
-        kwargs['parts'] = True
-    if param.get('stagger'):                        # --stagger N: the window tried at N + 1 starts (f2q_set_stagger); part of the key too
-        kwargs['stagger'] = param['stagger']
-    if param.get('indel'):                          # --indel: one-base insertions and deletions reported (f2q_set_indel); part of the key too
-        kwargs['indel'] = True
+    for opt in _options_of(param):
+        kwargs.update(opt.kwargs(param))
     return kwargs
 
 
@@ -294,42 +270,31 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
     contract.  A paired-end run (param['paired']) counts `raw` together with its mate file param['mates'][raw].  A cut-off or damaged .gz gives the counts of every complete record before the damage plus the
     reference's warning (its parser keeps what it counted when readline raises, :405-407).  `features` is updated in
     place: Counter mode adds to Features.counts, Extract+Count mode adds the de-novo keys in first-occurrence order."""
+    return _count_sample(i, raw, features, param, reads_stats, preprocess)[:3]
+
+
+def _count_sample(i, raw, features, param, reads_stats, preprocess=False):
+    """reads_counter, and next to its three values what every option of the run read from the context while it held the
+    sample: {option name: Option.read()'s record}.  aligner() calls this one."""
     if (param['upstream'] is not None) and (param['downstream'] is not None):
         if len(str(param['upstream']).split(",")) != len(str(param['downstream']).split(",")):
             colourful_errors("FATAL", "Up and Downstream sequences must be submitted in concurrent pairs, separated by ,.")
             sys.exit()
     local_read_stats = dict.fromkeys(binding.STAT_NAMES, 0)
     if preprocess:                                  # memo warm-up (:1593-1617) has nothing to warm here
-        return features, reads_stats, local_read_stats
+        return features, reads_stats, local_read_stats, {}
+    options = _options_of(param)
+    world = sharding.world()
+    for opt in reversed(options):                   # (as file_sizer_split, for a caller that gets past it)
+        if world.size > 1 and opt.one_rank(param):
+            raise RuntimeError(opt.one_rank(param))
     counter_mode = param['Running Mode'] == 'C'
     seqs = list(features) if counter_mode else None
-    assign = list(param['assign_features']) if param.get('assign') and not counter_mode else None
-    if assign is not None and sharding.world().size > 1:
-        raise RuntimeError("--as: assignments are not merged across several ranks; run one process")
-    if param.get('umi') and sharding.world().size > 1:
-        raise RuntimeError("--umi: the UMI sets are not merged across several ranks; run one process")
-    if param.get('ec_collapse') and sharding.world().size > 1:
-        raise RuntimeError("--ecm 1: the merged tables of several ranks are not collapsed; run one process")
-    if param.get('umi_paired') and sharding.world().size > 1:
-        raise RuntimeError("--umi1 / --umi2: the UMI sets are not merged across several ranks; run one process")
-    if param.get('umi_header') and sharding.world().size > 1:
-        raise RuntimeError("--umih: the UMI sets are not merged across several ranks; run one process")
-    if param.get('sample_barcodes') and sharding.world().size > 1:
-        raise RuntimeError("--sb: the demultiplexed counts are not merged across several ranks; run one process")
-    if param.get('strand') and sharding.world().size > 1:
-        raise RuntimeError("--strand: the reverse-strand counts are not merged across several ranks; run one process")
-    if param.get('parts') and sharding.world().size > 1:
-        raise RuntimeError("--parts: the part tables and recombinant sets are not merged across several ranks; run one process")
-    if param.get('stagger') and sharding.world().size > 1:
-        raise RuntimeError("--stagger: the offset histograms are not merged across several ranks; run one process")
-    if param.get('indel') and sharding.world().size > 1:
-        raise RuntimeError("--indel: the indel counts are not merged across several ranks; run one process")
-    ctx =_context_for(seqs, _counter_kwargs(param)) if assign is None else _context_for(seqs, _counter_kwargs(param), assign)
+    kwargs = _counter_kwargs(param)
+    assign = kwargs.pop('assign_library', None)     # (not an argument of the context: given to it once it is made)
+    ctx = _context_for(seqs, kwargs, assign)
     try:
-        world = sharding.world()
         if param.get('paired'):
-            if world.size > 1:
-                raise RuntimeError("--pe: paired files are not shared out over several ranks; run one process")
             try:
                 _, truncated = ctx.count_file_paired(raw, param['mates'][raw])
             except binding.F2QError as exc:
@@ -346,38 +311,12 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
             _, truncated = ctx.count_file(raw)
             counts, stats = ctx.read_counts()
             ec_rows = None if counter_mode else ctx.ec_results()
-        if assign is not None:
-            # one match per distinct key on the device: the Counter-mode count vector and counters of the same reads, and
-            # every key's feature (f2q_ec_assign)
-            acounts, stats = ctx.ec_assign()
-            param.setdefault('assigned', {})[raw] = ([int(n) for n in acounts], ctx.ec_assigned())
-        if param.get('ec_collapse') and not counter_mode:
-            # the sample's plain keys one base apart folded on the device (f2q_ec_collapse): the counters, every key's centroid
-            dist, ratio = param['ec_collapse']
-            extra = ctx.ec_collapse(dist, ratio)
-            param.setdefault('collapsed', {})[raw] = (extra, ctx.ec_collapsed())
-        if umi_length(param):                       # distinct UMIs per feature and the two sample-level counters (f2q_read_umis)
-            umis, umi_reads, umi_failed = ctx.read_umis()
-            # the sample's record: per kind of UMI_TABLES that was computed, a number per feature and the sample-level counters
-            rec = param.setdefault('umi_counted', {})[raw] = {"umis": ([int(n) for n in umis], dict(umi_reads=umi_reads, umi_failed=umi_failed))}
-            if param.get('umi_mismatch'):           # --mu 1: UMIs of a feature one base apart joined (f2q_umi_collapse)
-                molecules, pairs, edges = ctx.collapse_umis(param['umi_mismatch'])
-                rec["molecules"] = ([int(n) for n in molecules], dict(umi_pairs=pairs, umi_edges=edges, umi_molecules=int(sum(molecules))))
-            if param.get('umi_rule') == 'directional':      # --mur directional: the directional rule on the same set, and its pairs
-                molecules, pairs, edges, dominated, reads = ctx.collapse_umis_directional()
-                rec["directional"] = ([int(n) for n in molecules], dict(umi_pairs=pairs, umi_edges=edges, umi_dominated=dominated,
-                                                                        umi_molecules=int(sum(molecules)), umi_pair_reads=reads))
-                rec["pair_table"] = ctx.umi_pairs() if not param.get("delete", True) else None
-        if param.get('sample_barcodes'):            # --sb: the count matrix, the counters per sample barcode, the verdicts (f2q_read_demux)
-            param.setdefault('demux_counted', {})[raw] = ctx.read_demux()
-        if param.get('strand'):                     # --strand rev / both: reads assigned on the reverse strand, the strand counters (f2q_read_strands)
-            param.setdefault('strand_counted', {})[raw] = ctx.read_strands()
-        if param.get('stagger'):                    # --stagger N: reads assigned without / with mismatches at each offset (f2q_read_stagger)
-            param.setdefault('stagger_counted', {})[raw] = ctx.read_stagger()
-        if param.get('indel'):                      # --indel: deletion and insertion reads per feature and per position, the four totals (f2q_read_indels)
-            param.setdefault('indel_counted', {})[raw] = ctx.read_indels()
-        if param.get('parts'):                      # --parts: counts by the part rule, the marginals, the six classes (f2q_read_parts) and the recombinant pairs
-            param.setdefault('parts_counted', {})[raw] = (ctx.read_parts(), ctx.parts_recombinants())
+        extras = {}
+        for opt in options:
+            record = opt.read(ctx, param)
+            if record is not None:
+                extras[opt.name] = record
+                stats = record.get('stats', stats)  # (--as: the counters Counter mode gives for the same reads)
     except BaseException:
         _drop_context(ctx)                          # whatever state the failure left: the next sample starts afresh
         raise
@@ -394,7 +333,7 @@ def reads_counter(i, raw, features, param, reads_stats, preprocess=False):
                 features[key] = Features(key, n)
     for k, v in zip(binding.STAT_NAMES, stats):
         local_read_stats[k] = int(v)
-    return features, reads_stats, local_read_stats
+    return features, reads_stats, local_read_stats, extras
 
 
 @dataclass
@@ -406,6 +345,7 @@ class SampleResult:
     time_unit: str       # seconds / minutes / hours
     rows: list           # [feature name, reads] in the sample's row order (numeric or alphabetical, :790-793)
     stats: dict          # the five counters of reads_counter (:310-316)
+    extras: dict = field(default_factory=dict)   # what the run's options add: {option name: Option.sample()'s record}
 
     def sentence(self):
         """first line of <sample>_reads.csv, as upstream words it (:785)"""
@@ -436,91 +376,37 @@ def _elapsed_text(seconds):
 
 
 def aligner(i, raw, features, param, reads_stats):
-    """One sample (:752-801): count it, order its rows, and keep the result for compiling() in param["samples"].
-    <sample>_reads.csv is only written when the temporaries are kept (--k): nothing reads it back."""
+    """One sample (:752-801): count it, order its rows, and keep the result for compiling() in param["samples"] -- what the
+    run's options add to it travels in its extras.  <sample>_reads.csv is only written when the temporaries are kept
+    (--k): nothing reads it back."""
     started = time.perf_counter()
-    packed = reads_counter(i, raw, features, param, reads_stats)
+    packed = _count_sample(i, raw, features, param, reads_stats)
     if packed is None:
         return reads_stats
-    features, reads_stats, local = packed
+    features, reads_stats, local, records = packed
     rows = _sample_rows([f.name, f.counts] for f in features.values())
     value, unit = _elapsed_text(time.perf_counter() - started)
     sample = SampleResult(_sample_name(raw), value, unit, rows, dict(local))
-    if raw in param.get('assigned', {}):             # --as: the table Counter mode would have given, and every key's feature
-        acounts, arows = param['assigned'].pop(raw)
-        names = [f.name for f in param['assign_features'].values()]
-        param.setdefault("assign_samples", {})[sample.name] = SampleResult(sample.name, value, unit, _sample_rows(zip(names, acounts)), dict(local))
-        if sharding.world().rank == 0:
-            os.makedirs(param["directory"], exist_ok=True)
-            csv_writer(os.path.join(param["directory"], sample.name + "_assigned.csv"),
-                       [["#key", "reads", "feature_name", "mismatches"]] +
-                       [[key, n, names[f] if f >= 0 else "", d] for key, n, _first, f, d in arows])
-    if raw in param.get('collapsed', {}):            # --ecm 1: every key's centroid; the sample's column of <name>_collapsed.csv
-        extra, crows = param['collapsed'].pop(raw)
-        centroids = [(key, cluster) for key, _n, _first, cent, cluster in crows if cent == key]
-        param.setdefault("collapse_samples", {})[sample.name] = (
-            SampleResult(sample.name, value, unit, _sample_rows(centroids), dict(local)),
-            [len(crows), extra["eligible_keys"], extra["absorbed_keys"], len(centroids), extra["absorbed_reads"], extra["longest_chain"]])
-        if sharding.world().rank == 0:
-            os.makedirs(param["directory"], exist_ok=True)
-            csv_writer(os.path.join(param["directory"], sample.name + "_clusters.csv"),
-                       [["#key", "reads", "centroid", "cluster_reads"]] + [[key, n, cent, cluster] for key, n, _first, cent, cluster in crows])
-    if raw in param.get('umi_counted', {}):          # --umi: the same rows once per kind, holding UMIs / molecules instead of reads
-        rec = param['umi_counted'].pop(raw)
-        pair_table = rec.pop("pair_table", None)
-        names = [f.name for f in features.values()]
-        param.setdefault("umi_samples", {})[sample.name] = {
-            kind: SampleResult(sample.name, value, unit, _sample_rows(zip(names, column)), dict(local, **stats)) for kind, (column, stats) in rec.items()}
-        if not param.get("delete", True) and sharding.world().rank == 0:
-            os.makedirs(param["directory"], exist_ok=True)
-            kinds = [t for t in UMI_TABLES if t[0] in rec]
-            both = _sample_rows((f.name, (f.counts,) + tuple(ns)) for f, ns in zip(features.values(), zip(*(rec[t[0]][0] for t in kinds))))  # (the order of `rows`)
-            csv_writer(os.path.join(param["directory"], sample.name + "_umi_reads.csv"),
-                       [["#Feature", "Reads"] + [t[2] for t in kinds]] + [[name, *ns] for name, ns in both])
-            if pair_table is not None:               # every (feature, UMI) pair with its reads, in f2q_umi_pairs' order
-                length = umi_length(param)          # (--umi1 + --umi2: the concatenation as sequenced)
-                csv_writer(os.path.join(param["directory"], sample.name + "_umi_pairs.csv"),
-                           [["#Feature", "UMI", "Reads"]] + [[names[f], umi_text(int(c), length), int(n)] for f, c, n in zip(*pair_table)])
-    if raw in param.get('demux_counted', {}):        # --sb: the same rows once per sample barcode, then the unassigned reads
-        matrix, sstats, verdicts = param['demux_counted'].pop(raw)
-        names = [f.name for f in features.values()]
-        columns = [SampleResult(f"{sample.name}:{bname}", value, unit, _sample_rows(zip(names, (int(n) for n in matrix[b]))),
-                                dict(zip(binding.STAT_NAMES, (int(n) for n in sstats[b]))))
-                   for b, bname in enumerate(param['sample_barcodes']['names'] + ["unassigned"])]
-        param.setdefault("demux_samples", {})[sample.name] = (columns, [int(n) for n in verdicts])
-    if raw in param.get('strand_counted', {}):       # --strand rev / both: the sample's column split by the strand a read was counted on
-        rev_counts, extra = param['strand_counted'].pop(raw)
-        split = [(f.name, int(f.counts) - int(n), int(n)) for f, n in zip(features.values(), rev_counts)]
-        columns = [SampleResult(f"{sample.name}:fwd", value, unit, _sample_rows((name, fwd) for name, fwd, _ in split), {}),
-                   SampleResult(f"{sample.name}:rev", value, unit, _sample_rows((name, rev) for name, _, rev in split), {})]
-        param.setdefault("strand_samples", {})[sample.name] = (columns, [int(n) for n in extra])
-    if raw in param.get('stagger_counted', {}):      # --stagger N: the sample's two columns of <name>_stagger.csv
-        perfect, imperfect = param['stagger_counted'].pop(raw)
-        param.setdefault("stagger_samples", {})[sample.name] = ([int(n) for n in perfect], [int(n) for n in imperfect])
-    if raw in param.get('indel_counted', {}):        # --indel: the sample's two columns of <name>_indel.csv and of <name>_indel_positions.csv, its totals
-        dels, inss, del_pos, ins_pos, totals = param['indel_counted'].pop(raw)
-        names = [f.name for f in features.values()]
-        columns = [SampleResult(f"{sample.name}:del", value, unit, _sample_rows(zip(names, (int(n) for n in dels))), {}),
-                   SampleResult(f"{sample.name}:ins", value, unit, _sample_rows(zip(names, (int(n) for n in inss))), {})]
-        param.setdefault("indel_samples", {})[sample.name] = (columns, [int(n) for n in del_pos], [int(n) for n in ins_pos], [int(n) for n in totals])
-    if raw in param.get('parts_counted', {}):        # --parts: the same rows holding parts_counts; the recombinant pairs by their texts; the classes
-        (parts_counts, part1, part2, classes), (i1, i2, reads) = param['parts_counted'].pop(raw)
-        names = [f.name for f in features.values()]
-        firsts, seconds = part_libraries(list(features))
-        recombinants = {(firsts[a], seconds[b]): int(n) for a, b, n in zip(i1, i2, reads)}
-        param.setdefault("parts_samples", {})[sample.name] = (
-            SampleResult(sample.name, value, unit, _sample_rows(zip(names, (int(n) for n in parts_counts))), dict(local)),
-            recombinants, dict(zip(binding.PARTS_CLASSES, (int(n) for n in classes))))
-        if not param.get("delete", True) and sharding.world().rank == 0:
-            os.makedirs(param["directory"], exist_ok=True)
-            csv_writer(os.path.join(param["directory"], sample.name + "_parts_marginals.csv"),
-                       [["#position", "part", "reads"]] + [[1, part, int(n)] for part, n in zip(firsts, part1)] + [[2, part, int(n)] for part, n in zip(seconds, part2)])
+    sample.extras.update((opt.name, opt.sample(records[opt.name], sample, features, param)) for opt in OPTIONS if opt.name in records)
     if not param['Progress bar']:
         colourful_errors("INFO", f"Sample {sample.name} was processed in {value} {unit}")
     param.setdefault("samples", {})[sample.name] = sample     # a later file of the same name replaces the earlier one,
     if not param.get("delete", True) and sharding.world().rank == 0:   # as its _reads.csv would upstream
         csv_writer(os.path.join(param["directory"], sample.name + "_reads.csv"), sample.reads_csv_rows())
     return reads_stats
+
+
+def _sample_file(param, sample, suffix, rows):
+    """<sample><suffix> of one option, written by rank 0"""
+    if sharding.world().rank == 0:
+        os.makedirs(param["directory"], exist_ok=True)
+        csv_writer(os.path.join(param["directory"], sample.name + suffix), rows)
+
+
+def _column(sample, pairs, stats=None, tag=""):
+    """a column of one of the options' tables: [name, number] pairs in the sample's row order, under the sample's name
+    (+ tag) and running time, with the counters that go with them (the sample's own unless given)"""
+    return SampleResult(sample.name + tag, sample.time_value, sample.time_unit, _sample_rows(pairs), dict(sample.stats if stats is None else stats))
 
 
 def _sample_rows(pairs):
@@ -573,40 +459,9 @@ def initializer(cmd):
         print(f" Finding features with the folowing length: {param['length']}bp")
     if (param['upstream'] is None) and (param['downstream'] is None):
         print(f" Read alignment start position: {param['start']}")
-    if param.get('assign'):
-        print(f" Extracted sequences are assigned to the features of {param['feature']} ({param['miss']} mismatches allowed)")
-    if param.get('paired'):
-        print(f" Paired-end: mate 2 start position: {param['start2']}" + (" (mate 2 reverse-complemented)" if param['rc2'] else ""))
-    if param.get('umi'):
-        print(f" Distinct UMIs are counted per feature: UMI start position in the read: {param['umi'][0]}, length: {param['umi'][1]}bp")
-    for mate, part in enumerate(param.get('umi_paired') or (), 1):
-        if part:
-            print(f" Distinct UMIs are counted per feature: UMI part in mate {mate}, start position: {part[0]}, length: {part[1]}bp")
-    if param.get('umi_header'):
-        print(f" Distinct UMIs are counted per feature: UMI in the read header, behind the last '{param['umi_header'][0]}' of the read id, length: {param['umi_header'][1]}bp")
-    if param.get('sample_barcodes'):
-        sb = param['sample_barcodes']
-        print(f" Reads are demultiplexed by {len(sb['barcodes'])} inline sample barcodes of {sb['path']}")
-        print(f" {sample_barcodes_header(param)[1:]}")
-    if param.get('strand'):
-        print(f" Reads are counted on {'the reverse strand' if param['strand'] == 'rev' else 'the forward strand, else on the reverse strand'}")
-        print(f" {strand_header(param)[1:]}")
-    if param.get('stagger'):
-        print(f" The feature window is tried at the starts {param['start']} .. {int(param['start']) + param['stagger']}: the earliest exact one counts, else the earliest within --m")
-        print(f" {stagger_header(param)[1:]}")
-    if param.get('indel'):
-        print(" Reads that are assigned no feature are tried as one-base deletions and insertions of every feature; they are reported, not counted")
-        print(f" {INDEL_HEADER[1:]}")
-    if param.get('parts'):
-        print(" Each of the two feature parts is also matched on its own; recombinant reads are counted per pair of parts")
-        print(f" {PARTS_HEADER[1:]}")
-    if param.get('ec_collapse'):
-        print(" Extracted sequences of one sample that differ in one base are collapsed into the one with the most reads")
-        print(f" {ec_collapse_header(param)[1:]}")
-    if param.get('umi_mismatch'):
-        print(f" UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})")
-    if param.get('umi_rule') == 'directional':
-        print(" Molecules are also counted by the directional rule: a UMI absorbs a neighbour with at most (its reads + 1) / 2 reads (--mur directional)")
+    for opt in _options_of(param):
+        for line in opt.banner(param):
+            print(f" {line}")
     print(f" All data will be saved into {param['directory']}")
     print("\n ---- ")
     param["cpu"] = param["cpu"] if isinstance(param["cpu"], int) and param["cpu"] > 0 else (os.cpu_count() or 1)
@@ -656,27 +511,25 @@ def umi_length(param):
     return sum(part[1] for part in param.get('umi_paired') or () if part)
 
 
+# the line each of these options adds to the parameter print-out and to the head of <name>_stats.csv
+INDEL_HEADER, PARTS_HEADER = "#Indel reads reported: 1", "#Parts matched independently: 2"
+
+
 def sample_barcodes_header(param):
-    """the line a --sb run adds to the parameter print-out and to the head of <name>_stats.csv"""
     sb = param['sample_barcodes']
     return f"#Sample barcodes, start, length, mismatches: {sb['start']},{len(sb['barcodes'][0])},{sb['miss']}"
 
 
 def stagger_header(param):
-    """the line a --stagger N run (N > 0) adds to the parameter print-out and to the head of <name>_stats.csv"""
     return f"#Stagger: {param['stagger']}"
 
 
-INDEL_HEADER = "#Indel reads reported: 1"      # the line an --indel run adds to the parameter print-out and to the head of <name>_stats.csv
-
-
 def strand_header(param):
-    """the line a --strand rev / both run adds to the parameter print-out and to the head of <name>_stats.csv"""
     return f"#Strand: {param['strand']}"
 
 
-# the line a --parts run adds to the parameter print-out and to the head of <name>_stats.csv
-PARTS_HEADER = "#Parts matched independently: 2"
+def ec_collapse_header(param):
+    return "#Extracted sequences collapsed, mismatches, ratio: %d,%d" % param['ec_collapse']
 
 
 def parse_umih(text):
@@ -697,6 +550,527 @@ def parse_umi(text):
     if not m or int(m.group(1)) > 0x3FFFFFFF or not 1 <= int(m.group(2)) <= 16:
         return None
     return int(m.group(1)), int(m.group(2))
+
+
+# ---- the command-line options beyond the reference's ---------------------------------------------------------------------
+@dataclass
+class Option:
+    """What one command-line option adds to a run: one row of OPTIONS.  input_parser, _counter_kwargs, file_sizer_split, main,
+    _count_sample, aligner, initializer, run_headers, compiling and run_stats are loops over the rows around their option-free
+    core; none of them names an option.  Every field but the first three has the default of an option that adds nothing
+    there.  `found` is [(sample, the option's record of it)] over the samples that carry one, in <name>.csv's column order;
+    tables and stats are asked only when there are any."""
+    name: str                    # its key of param (set by parse; the option is on when it holds something) and of SampleResult.extras
+    flags: tuple                 # (flag, add_argument's keywords) of each of its flags
+    parse: callable              # (args, p), asked when the command line holds one of its flags: sets its keys of p; the sentence that refuses it, else None
+    on: callable = None          # (param): where `name` alone does not tell
+    library: callable = lambda features, param: None       # main(), once the library is read: checks it or loads beside it; a refusal, else None
+    kwargs: callable = lambda param: {}                     # what it adds to the context's keyword arguments (and so to the key contexts are kept under)
+    one_rank: callable = lambda param: None                 # what several ranks do not merge, as one sentence
+    banner: callable = lambda param: []                     # its lines of the parameter print-out
+    header: callable = lambda param: []                     # its '#key: value' lines at the head of <name>_stats.csv
+    read: callable = lambda ctx, param: None                # what it fetches from the context that has counted a sample, as a dict
+    sample: callable = None      # (got, sample, features, param): read()'s dict shaped for the tables, kept as sample.extras[name]; writes its per-sample files
+    tables: callable = lambda param, found: []              # [(suffix, rows)]: every <name><suffix>.csv it adds
+    stats: callable = lambda param, found: []               # the rows of its blocks of <name>_stats.csv
+
+    def found(self, ordered):
+        return [(s, s.extras[self.name]) for s in ordered if self.name in s.extras]
+
+
+def _options_of(param):
+    return [opt for opt in OPTIONS if (opt.on(param) if opt.on else param.get(opt.name))]
+
+
+def _counter_mode_only(flag, p):
+    """the refusal of an option that reads the library while it counts, in an Extract+Count run"""
+    return None if p['Running Mode'] == "C" else f"{flag} only has a meaning in Counter mode: it cannot be combined with --mo EC."
+
+
+def _cannot_combine(flag, args, p, others, why):
+    """the refusal of `flag` next to any of `others`, named as the command line gives them.  --strand counts when it is a
+    strand mode (fwd is a run without it), --stagger when its row took it (0 is a run without it)."""
+    given = []
+    for other in others:
+        if other == "--strand":
+            given += [f"--strand {args.strand}"] if args.strand in ("rev", "both") else []
+        elif other == "--stagger":
+            given += [f"--stagger {p['stagger']}"] if p.get('stagger') else []
+        elif getattr(args, other.lstrip("-")) is not None:
+            given.append(other)
+    return f"{flag} cannot be combined with {' / '.join(given)}: {why}." if given else None
+
+
+def _one_window_start(flag, p):
+    if not re.fullmatch(r"[0-9]+", str(p['start']).strip()):
+        return f"{flag} needs exactly one window start at or after the first base: --st {p['start']} does not name one."
+
+
+def _not_merged(flag, what):
+    return f"{flag}: {what} not merged across several ranks; run one process"
+
+
+def _names(features):
+    return [f.name for f in features.values()]
+
+
+def _ints(numbers):
+    return [int(n) for n in numbers]
+
+
+def _table(suffix, columns):
+    """(suffix, rows) of <name><suffix>.csv: <name>.csv's layout over these columns"""
+    head, table = _table_of(columns)
+    return suffix, [head] + [[feature] + counts for feature, counts in table.items()]
+
+
+def _parse_paired(args, p):
+    if args.pe is None:
+        return f"{'--st2' if args.st2 is not None else '--rc2'} only has a meaning with --pe."
+    if args.t is not None:
+        return "--pe cannot be combined with -t: the test mode runs on one packaged single-end sample."
+    if args.us is not None or args.ds is not None:
+        return "--pe takes fixed positions only (--st / --st2): it cannot be combined with --us / --ds."
+    if args.st2 is None:
+        return "--pe needs --st2: the start position(s) of the feature part(s) within mate 2."
+    p['paired'], p['start2'], p['rc2'] = True, args.st2, args.rc2 is not None
+
+
+PAIRED = Option(
+    'paired', parse=_parse_paired,
+    flags=(("--pe", dict(nargs='?', const=True, help="Paired-end: the files of --s are paired by name (_R1/_R2, else _1/_2); --st names the feature parts in mate 1, --st2 those in mate 2")),
+           ("--st2", dict(help="With --pe: the start position(s) of the feature part(s) within mate 2")),
+           ("--rc2", dict(nargs='?', const=True, help="With --pe: mate 2 is reverse-complemented before its parts are taken"))),
+    kwargs=lambda param: dict(start2=param['start2'], rc2=bool(param.get('rc2'))),      # the windows of mate 2 and its direction (f2q_set_mate2)
+    one_rank=lambda param: "--pe: paired files are not shared out over several ranks; run one process",
+    banner=lambda param: [f"Paired-end: mate 2 start position: {param['start2']}" + (" (mate 2 reverse-complemented)" if param['rc2'] else "")],
+    header=lambda param: [f"#Paired-end, feature start position in mate 2: {param['start2']}", f"#Mate 2 reverse-complemented: {'yes' if param['rc2'] else 'no'}"])
+
+
+# ---- --umi, --umi1 / --umi2 or --umih name the run's one source of UMIs (param['umi'], ['umi_paired'], ['umi_header']); --mu 1 and
+# --mur directional add a kind of UMI_TABLES each.  A sample's record: {kind: its column of that kind}
+def _parse_umi_family(args, p):
+    if args.umi is not None:
+        if _counter_mode_only("--umi", p):
+            return _counter_mode_only("--umi", p)
+        if args.pe is not None:
+            return "--umi takes single reads: it cannot be combined with --pe. The UMI of a pair is named per mate with --umi1 S,L and / or --umi2 S,L."
+        p['umi'] = parse_umi(args.umi)
+        if p['umi'] is None:
+            return f"--umi {args.umi}: expected S,L with a start S >= 0 and a length 1 <= L <= 16."
+    if args.umi1 is not None or args.umi2 is not None:
+        given = " / ".join(f for f, v in (("--umi1", args.umi1), ("--umi2", args.umi2)) if v is not None)
+        if args.pe is None:
+            return f"{given} only has a meaning with --pe: the UMI part of one mate of a pair (single reads: --umi)."
+        if args.umi is not None:
+            return f"{given} cannot be combined with --umi: --umi names the UMI of single reads."
+        if _counter_mode_only(given, p):
+            return _counter_mode_only(given, p)
+        parts = []
+        for flag, value in (("--umi1", args.umi1), ("--umi2", args.umi2)):
+            parts.append(None if value is None else parse_umi(value))
+            if value is not None and parts[-1] is None:
+                return f"{flag} {value}: expected S,L with a start S >= 0 and a length 1 <= L <= 16."
+        if sum(part[1] for part in parts if part) > 16:
+            return f"--umi1 {args.umi1} --umi2 {args.umi2}: the two parts together hold 16 bases at most."
+        p['umi_paired'] = tuple(parts)
+    if args.umih is not None:
+        refusal = _cannot_combine("--umih", args, p, UMI_FLAGS[:3], "a run has one source of UMIs, the read header or the read") or _counter_mode_only("--umih", p)
+        if refusal:
+            return refusal
+        parsed = parse_umih(args.umih)
+        if isinstance(parsed, str):
+            return f"--umih {args.umih}: {parsed}."
+        p['umi_header'] = parsed
+    any_umi = any(getattr(args, flag.lstrip("-")) is not None for flag in UMI_FLAGS)
+    if args.mu is not None:
+        if not any_umi:
+            return "--mu only has a meaning with --umi: the mismatches allowed between two UMIs of one feature."
+        if args.mu not in ("0", "1"):
+            return f"--mu {args.mu}: expected 0 or 1 (UMIs are collapsed at Hamming distance 1 at most)."
+        if args.mu == "1":                                      # (0 is a run without the flag)
+            p['umi_mismatch'] = 1
+    if args.mur is not None:
+        if args.mur not in ("cluster", "directional"):
+            return f"--mur {args.mur}: expected cluster or directional."
+        if not any_umi or args.mu != "1":
+            return "--mur only has a meaning with --umi and --mu 1: the rule UMIs one base apart are collapsed by."
+        if args.mur == "directional":
+            p['umi_rule'] = 'directional'
+
+
+def _umi_kwargs(param):
+    # f2q_set_umi, f2q_set_umi_paired, f2q_set_umi_header (--mu: collapsing changes no context); --mur directional: it keeps the reads of every pair (f2q_set_umi_reads)
+    kwargs = {key: tuple(param[key]) for key in ('umi', 'umi_paired', 'umi_header') if param.get(key)}
+    return dict(kwargs, umi_reads=True) if param.get('umi_rule') == 'directional' else kwargs
+
+
+def _umi_lines(param):
+    """[(line of the parameter print-out, line at the head of <name>_stats.csv)]"""
+    said, lines = "Distinct UMIs are counted per feature: UMI", []
+    if param.get('umi'):
+        lines.append((f"{said} start position in the read: {param['umi'][0]}, length: {param['umi'][1]}bp", f"#UMI start position in the read, length: {param['umi'][0]},{param['umi'][1]}"))
+    lines += [(f"{said} part in mate {mate}, start position: {part[0]}, length: {part[1]}bp", f"#UMI in mate {mate}, start, length: {part[0]},{part[1]}")
+              for mate, part in enumerate(param.get('umi_paired') or (), 1) if part]
+    if param.get('umi_header'):
+        lines.append((f"{said} in the read header, behind the last '{param['umi_header'][0]}' of the read id, length: {param['umi_header'][1]}bp",
+                      f"#UMI in read header, separator, length: {param['umi_header'][0]},{param['umi_header'][1]}"))
+    if param.get('umi_mismatch'):
+        lines.append((f"UMIs of one feature that differ in one base are collapsed (--mu {param['umi_mismatch']})", f"#UMI mismatches collapsed: {param['umi_mismatch']}"))
+    if param.get('umi_rule') == 'directional':
+        lines.append(("Molecules are also counted by the directional rule: a UMI absorbs a neighbour with at most (its reads + 1) / 2 reads (--mur directional)",
+                      "#UMI collapse rule: directional"))
+    return lines
+
+
+def _umi_read(ctx, param):
+    """per kind of UMI_TABLES that was computed: (a number per feature, the sample-level counters); --mur directional with
+    --k: the (feature, UMI, reads) table too"""
+    umis, umi_reads, umi_failed = ctx.read_umis()           # distinct UMIs per feature and the two sample-level counters (f2q_read_umis)
+    got = {"umis": (_ints(umis), dict(umi_reads=umi_reads, umi_failed=umi_failed))}
+    if param.get('umi_mismatch'):                           # --mu 1: UMIs of a feature one base apart joined (f2q_umi_collapse)
+        molecules, pairs, edges = ctx.collapse_umis(param['umi_mismatch'])
+        got["molecules"] = (_ints(molecules), dict(umi_pairs=pairs, umi_edges=edges, umi_molecules=int(sum(molecules))))
+    if param.get('umi_rule') == 'directional':              # --mur directional: the directional rule on the same set, and its pairs
+        molecules, pairs, edges, dominated, reads = ctx.collapse_umis_directional()
+        got["directional"] = (_ints(molecules), dict(umi_pairs=pairs, umi_edges=edges, umi_dominated=dominated, umi_molecules=int(sum(molecules)), umi_pair_reads=reads))
+        got["pair_table"] = ctx.umi_pairs() if not param.get("delete", True) else None
+    return got
+
+
+def _umi_sample(got, sample, features, param):
+    """the sample's rows once per kind, holding UMIs / molecules instead of reads"""
+    got = dict(got)
+    pair_table = got.pop("pair_table", None)
+    if not param.get("delete", True):                       # the temporaries of --k
+        kinds = [t for t in UMI_TABLES if t[0] in got]
+        both = _sample_rows((f.name, (f.counts,) + tuple(ns)) for f, ns in zip(features.values(), zip(*(got[t[0]][0] for t in kinds))))  # (the order of sample.rows)
+        _sample_file(param, sample, "_umi_reads.csv", [["#Feature", "Reads"] + [t[2] for t in kinds]] + [[name, *ns] for name, ns in both])
+    if pair_table is not None:                              # every (feature, UMI) pair with its reads, in f2q_umi_pairs' order
+        length = umi_length(param)                          # (--umi1 + --umi2: the concatenation as sequenced)
+        _sample_file(param, sample, "_umi_pairs.csv", [["#Feature", "UMI", "Reads"]] + [[_names(features)[f], umi_text(int(c), length), int(n)] for f, c, n in zip(*pair_table)])
+    return {kind: _column(sample, zip(_names(features), column), dict(sample.stats, **stats)) for kind, (column, stats) in got.items()}
+
+
+def _umi_stats(param, found):
+    """per kind: its head, then one line of counters per sample"""
+    rows = []
+    for kind, _, _, stats_head, counters in UMI_TABLES:
+        lines = [[s.name] + [rec[kind].stats[c] for c in counters] for s, rec in found if kind in rec]
+        rows += [stats_head] + lines if lines else []
+    return rows
+
+
+UMI = Option(
+    'umi', parse=_parse_umi_family, on=lambda param: umi_length(param) > 0,
+    flags=(("--umi", dict(help="S,L: every read carries a UMI of L bases (1-16) at position S; Counter mode also reports the distinct UMIs per feature (<name>_umi.csv)")),
+           ("--umi1", dict(help="With --pe, S,L: the UMI (or its first part) is L bases at position S of mate 1")),
+           ("--umi2", dict(help="With --pe, S,L: the UMI (or its second part) is L bases at position S of mate 2 as sequenced (whatever --rc2 says); --umi1 and --umi2 together hold 16 bases at most")),
+           ("--umih", dict(help="SEP,L: the UMI of every read is in its header, the L bases (1-16) behind the last SEP of the read id, e.g. _,8 after umi_tools extract / fastp --umi, :,8 for an Illumina index-read UMI; with --pe: mate 1's header. Takes the place of --umi / --umi1 / --umi2")),
+           ("--mu", dict(help="With --umi (or --umih, --umi1 / --umi2): mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")),
+           ("--mur", dict(help="With --umi and --mu 1: the rule UMIs are collapsed by, cluster (default) or directional. directional: a UMI absorbs a neighbouring UMI only when it has at least twice its reads minus one (<name>_umi_directional.csv)"))),
+    kwargs=_umi_kwargs, read=_umi_read, sample=_umi_sample, stats=_umi_stats,
+    one_rank=lambda param: _not_merged("--umi" if param.get('umi') else "--umih" if param.get('umi_header') else "--umi1 / --umi2", "the UMI sets are"),
+    banner=lambda param: [said for said, _ in _umi_lines(param)],
+    header=lambda param: [line for _, line in _umi_lines(param)],
+    tables=lambda param, found: [_table(suffix, [rec[kind] for _, rec in found if kind in rec])             # <name>.csv's layout and row order per kind
+                                 for kind, suffix, _, _, _ in UMI_TABLES if any(kind in rec for _, rec in found)])
+
+
+# ---- --sb.  A sample's record: a column per barcode, then the unassigned reads; the five verdict counters
+DemuxSample = namedtuple("DemuxSample", "columns verdicts")
+
+
+def _parse_sample_barcodes(args, p):
+    if args.sb is None:
+        return f"{'--sbs' if args.sbs is not None else '--sbm'} only has a meaning with --sb: the .csv file with the sample barcodes."
+    refusal = _counter_mode_only("--sb", p) or _cannot_combine("--sb", args, p, ("--pe",) + UMI_FLAGS, "sample barcodes are taken from single reads without UMIs")
+    if refusal:
+        return refusal
+    if args.sbs is not None and not (args.sbs.isascii() and args.sbs.isdigit() and int(args.sbs) <= 0x3FFFFFFF):
+        return f"--sbs {args.sbs}: expected the start position of the sample barcode within the read, a number >= 0."
+    if args.sbm is not None and args.sbm not in ("0", "1"):
+        return f"--sbm {args.sbm}: expected 0 or 1 (sample barcodes are matched at Hamming distance 1 at most)."
+    loaded = sample_barcodes_loader(args.sb)
+    if isinstance(loaded, str):
+        return f"--sb {args.sb}: {loaded}."
+    p['sample_barcodes'] = dict(path=args.sb, names=loaded[0], barcodes=loaded[1], start=int(args.sbs or 0), miss=int(args.sbm or 0))
+
+
+def _demux_sample(got, sample, features, param):
+    columns = [_column(sample, zip(_names(features), _ints(got["matrix"][b])), dict(zip(binding.STAT_NAMES, _ints(got["sample_stats"][b]))), f":{bname}")
+               for b, bname in enumerate(param['sample_barcodes']['names'] + ["unassigned"])]
+    return DemuxSample(columns, _ints(got["verdicts"]))
+
+
+def _demux_stats(param, found):
+    """the verdicts per file, then the counters per (file, barcode)"""
+    return ([DEMUX_VERDICT_STATS_HEAD] + [[s.name] + rec.verdicts for s, rec in found] + [DEMUX_SAMPLE_STATS_HEAD] +
+            [[c.name, c.stats["reads"], c.stats["perfect_counter"] + c.stats["imperfect_counter"], c.stats["perfect_counter"],
+              c.stats["imperfect_counter"], c.stats["non_aligned_counter"], c.stats["quality_failed"]] for _, rec in found for c in rec.columns])
+
+
+SAMPLE_BARCODES = Option(
+    'sample_barcodes', parse=_parse_sample_barcodes, sample=_demux_sample, stats=_demux_stats,
+    flags=(("--sb", dict(help="The full path to a .csv file with rows name,barcode: the reads of every file are demultiplexed by an inline sample barcode (1-16 bases, at most 1024 barcodes of one length) while they are counted (<name>_demux.csv). Counter mode, single reads, one process")),
+           ("--sbs", dict(help="With --sb: the start position of the sample barcode within the read (default = 0)")),
+           ("--sbm", dict(help="With --sb: mismatches allowed in the sample barcode, 0 or 1 (default = 0)"))),
+    kwargs=lambda param: dict(sample_barcodes=(param['sample_barcodes']['start'], tuple(param['sample_barcodes']['barcodes'])),     # a demultiplexing context
+                              barcode_mismatch=param['sample_barcodes']['miss']),                                                  # (f2q_set_sample_barcodes)
+    one_rank=lambda param: _not_merged("--sb", "the demultiplexed counts are"),
+    banner=lambda param: [f"Reads are demultiplexed by {len(param['sample_barcodes']['barcodes'])} inline sample barcodes of {param['sample_barcodes']['path']}",
+                          sample_barcodes_header(param)[1:]],
+    header=lambda param: [sample_barcodes_header(param)],
+    read=lambda ctx, param: dict(zip(("matrix", "sample_stats", "verdicts"), ctx.read_demux())),     # the count matrix, the counters per barcode, the verdicts (f2q_read_demux)
+    tables=lambda param, found: [_table("_demux", [column for _, rec in found for column in rec.columns])])
+
+
+# ---- --strand rev / both.  A sample's record: its column split by the strand a read was counted on; the four strand counters
+StrandSample = namedtuple("StrandSample", "columns counters")
+
+
+def _parse_strand(args, p):
+    if args.strand not in ("fwd", "rev", "both"):
+        return f"--strand {args.strand}: expected fwd, rev or both."
+    if args.strand != "fwd":                                     # (fwd is a run without the flag)
+        flag = f"--strand {args.strand}"
+        refusal = _counter_mode_only(flag, p) or _cannot_combine(flag, args, p, ("--pe",) + UMI_FLAGS + ("--sb",),
+                                                                 "the reverse strand is read from single reads without UMIs or sample barcodes")
+        if refusal:
+            return refusal
+        p['strand'] = args.strand
+
+
+def _strand_sample(got, sample, features, param):
+    split = [(f.name, int(f.counts) - int(n), int(n)) for f, n in zip(features.values(), got["rev_counts"])]
+    return StrandSample([_column(sample, ((name, fwd) for name, fwd, _ in split), {}, ":fwd"), _column(sample, ((name, rev) for name, _, rev in split), {}, ":rev")],
+                        _ints(got["counters"]))
+
+
+STRAND = Option(
+    'strand', parse=_parse_strand, sample=_strand_sample,
+    flags=(("--strand", dict(help="fwd (default), rev or both: the orientation the reads are counted in. rev: every read is reverse-complemented first; both: a read that is assigned no feature as sequenced is tried reverse-complemented (<name>_strand.csv). Counter mode, single reads, one process")),),
+    kwargs=lambda param: dict(strand=param['strand']),                                              # (f2q_set_strand)
+    one_rank=lambda param: _not_merged("--strand", "the reverse-strand counts are"),
+    banner=lambda param: [f"Reads are counted on {'the reverse strand' if param['strand'] == 'rev' else 'the forward strand, else on the reverse strand'}", strand_header(param)[1:]],
+    header=lambda param: [strand_header(param)],
+    read=lambda ctx, param: dict(zip(("rev_counts", "counters"), ctx.read_strands())),              # reads assigned on the reverse strand per feature, the strand counters (f2q_read_strands)
+    tables=lambda param, found: [_table("_strand", [column for _, rec in found for column in rec.columns])],
+    stats=lambda param, found: [STRAND_STATS_HEAD] + [[s.name] + rec.counters for s, rec in found])
+
+
+# ---- --stagger N.  A sample's record: its reads assigned without / with mismatches at each offset
+StaggerSample = namedtuple("StaggerSample", "perfect imperfect")
+
+
+def _parse_stagger(args, p):
+    if not re.fullmatch(r"[0-9]{1,3}", str(args.stagger)) or int(args.stagger) > 32:
+        return f"--stagger {args.stagger}: expected a number of extra starts, 0 to 32."
+    if int(args.stagger):                                        # (0 is a run without the flag)
+        flag = f"--stagger {args.stagger}"
+        refusal = (_counter_mode_only(flag, p) or
+                   _cannot_combine(flag, args, p, ("--pe", "--us", "--ds") + UMI_FLAGS + ("--sb", "--parts", "--strand"),
+                                   "one fixed window of single reads is tried at several starts, without anchors, UMIs, sample barcodes, a strand mode or parts") or
+                   _one_window_start(flag, p))
+        if refusal:
+            return refusal
+        p['stagger'] = int(args.stagger)
+
+
+def _stagger_stats(param, found):
+    """where the reads of each file were assigned"""
+    rows = [STAGGER_STATS_HEAD]
+    for s, rec in found:
+        both = [a + b for a, b in zip(rec.perfect, rec.imperfect)]
+        rows.append([s.name, both[0], sum(both[1:]), both.index(max(both))])
+    return rows
+
+
+STAGGER = Option(
+    'stagger', parse=_parse_stagger, stats=_stagger_stats,
+    flags=(("--stagger", dict(help="N (0-32): the one fixed window (--st s --l L) is tried at the starts s .. s+N; a read counts at the earliest start that reads a feature exactly, else at the earliest one within --m (<name>_stagger.csv). 0 (default): off. Counter mode, single reads, one --st value, one process")),),
+    kwargs=lambda param: dict(stagger=param['stagger']),                                            # the window tried at N + 1 starts (f2q_set_stagger)
+    one_rank=lambda param: _not_merged("--stagger", "the offset histograms are"),
+    banner=lambda param: [f"The feature window is tried at the starts {param['start']} .. {int(param['start']) + param['stagger']}: the earliest exact one counts, else the earliest within --m",
+                          stagger_header(param)[1:]],
+    header=lambda param: [stagger_header(param)],
+    read=lambda ctx, param: dict(zip(("perfect", "imperfect"), ctx.read_stagger())),                # (f2q_read_stagger)
+    sample=lambda got, sample, features, param: StaggerSample(_ints(got["perfect"]), _ints(got["imperfect"])),
+    tables=lambda param, found: [("_stagger", [["#Offset", "Start"] + [f"{s.name}:{kind}" for s, _ in found for kind in ("perfect", "imperfect")]] +     # a row per offset
+                                  [[d, int(param['start']) + d] + [n for _, rec in found for n in (rec.perfect[d], rec.imperfect[d])] for d in range(param['stagger'] + 1)])])
+
+
+# ---- --indel.  A sample's record: its deletion and its insertion column, the reads of either per position, the four totals
+IndelSample = namedtuple("IndelSample", "columns del_pos ins_pos totals")
+
+
+def _parse_indel(args, p):
+    if args.indel is not True:
+        return f"--indel takes no value: --indel {args.indel} is not understood."
+    refusal = (_counter_mode_only("--indel", p) or
+               _cannot_combine("--indel", args, p, ("--pe", "--us", "--ds") + UMI_FLAGS + ("--sb", "--parts", "--strand", "--stagger"),
+                               "the unassigned reads of one fixed window of single reads are examined, without anchors, UMIs, sample barcodes, a strand mode, parts or a stagger") or
+               _one_window_start("--indel", p))
+    if refusal:
+        return refusal
+    if not 2 <= p['length'] <= 31:
+        return f"--indel needs a window of 2 to 31 bases: --l {p['length']} is outside that range."
+    p['indel'] = True
+
+
+INDEL = Option(
+    'indel', parse=_parse_indel,
+    flags=(("--indel", dict(nargs='?', const=True, help="Reads that the one fixed window (--st s --l L, L 2-31) assigns to no feature are tried as a one-base deletion and as a one-base insertion of every feature of L bases; they are reported per feature and per position (<name>_indel.csv, <name>_indel_positions.csv) and change no count. Counter mode, single reads, one --st value, one process")),),
+    kwargs=lambda param: dict(indel=True),                                                          # one-base insertions and deletions reported (f2q_set_indel)
+    one_rank=lambda param: _not_merged("--indel", "the indel counts are"),
+    banner=lambda param: ["Reads that are assigned no feature are tried as one-base deletions and insertions of every feature; they are reported, not counted", INDEL_HEADER[1:]],
+    header=lambda param: [INDEL_HEADER],
+    read=lambda ctx, param: dict(zip(("dels", "inss", "del_pos", "ins_pos", "totals"), ctx.read_indels())),     # per feature and per position, the four totals (f2q_read_indels)
+    sample=lambda got, sample, features, param: IndelSample([_column(sample, zip(_names(features), _ints(got["dels"])), {}, ":del"),
+                                                             _column(sample, zip(_names(features), _ints(got["inss"])), {}, ":ins")],
+                                                            _ints(got["del_pos"]), _ints(got["ins_pos"]), _ints(got["totals"])),
+    tables=lambda param, found: [_table("_indel", [column for _, rec in found for column in rec.columns]),
+                                 ("_indel_positions", [["#Position"] + [f"{s.name}:{kind}" for s, _ in found for kind in ("del", "ins")]] +              # a row per position
+                                  [[at] + [n for _, rec in found for n in (rec.del_pos[at], rec.ins_pos[at])] for at in range(param['length'])])],
+    stats=lambda param, found: [INDEL_STATS_HEAD] + [[s.name] + rec.totals for s, rec in found])
+
+
+# ---- --parts.  A sample's record: its rows by the part rule, {(part 1, part 2): reads} of its recombinant pairs, its six read classes by name
+PartsSample = namedtuple("PartsSample", "table recombinants classes")
+
+
+def _parse_parts(args, p):
+    refusal = _counter_mode_only("--parts", p) or _cannot_combine("--parts", args, p, ("--us", "--ds") + UMI_FLAGS + ("--sb", "--strand"),
+                                                                  "the parts are matched at fixed positions, without UMIs, sample barcodes or a strand mode")
+    if refusal:
+        return refusal
+    windows = [len(str(p['start']).split(","))] + ([len(str(args.st2).split(","))] if args.pe is not None else [])
+    if windows not in ([2], [1, 1]):
+        return (f"--parts needs exactly two windows: --st a,b for single reads, or one window per mate with --pe (--st a --st2 b); "
+                f"--st {p['start']}" + (f" --st2 {args.st2}" if args.pe is not None else "") + f" names {' + '.join(str(n) for n in windows)}.")
+    p['parts'] = True
+
+
+def _parts_library(features, param):
+    wrong = check_parts_library(features)
+    return f"--parts takes a library of pairs, --g {param['feature']}: {wrong}." if wrong else None
+
+
+def _parts_sample(got, sample, features, param):
+    firsts, seconds = part_libraries(list(features))
+    if not param.get("delete", True):
+        _sample_file(param, sample, "_parts_marginals.csv", [["#position", "part", "reads"]] + [[1, part, int(n)] for part, n in zip(firsts, got["part1"])] +
+                     [[2, part, int(n)] for part, n in zip(seconds, got["part2"])])
+    return PartsSample(_column(sample, zip(_names(features), _ints(got["parts_counts"]))), {(firsts[a], seconds[b]): int(n) for a, b, n in zip(*got["recombinants"])},
+                       dict(zip(binding.PARTS_CLASSES, _ints(got["classes"]))))
+
+
+def _parts_tables(param, found):
+    """<name>.csv's layout and row order holding parts_counts; the recombinant pairs of any sample, those with the most reads first"""
+    columns = [rec.recombinants for _, rec in found]
+    pairs = sorted({pair for column in columns for pair in column}, key=lambda pair: (-sum(column.get(pair, 0) for column in columns), pair))
+    return [_table("_parts", [rec.table for _, rec in found]),
+            ("_recombinants", [["#Part1", "Part2"] + [s.name for s, _ in found]] + [[a, b] + [column.get((a, b), 0) for column in columns] for a, b in pairs])]
+
+
+PARTS = Option(
+    'parts', parse=_parse_parts, library=_parts_library, sample=_parts_sample, tables=_parts_tables,
+    flags=(("--parts", dict(nargs='?', const=True, help="Pair libraries (features A:B over exactly two windows: --st a,b, or --pe --st a --st2 b): each part is also matched on its own with --m mismatches per part; reads whose two parts the library does not pair are counted as recombinants (<name>_parts.csv, <name>_recombinants.csv). Counter mode, one process")),),
+    kwargs=lambda param: dict(parts=True),                                                          # each part of a pair library matched alone (f2q_set_parts)
+    one_rank=lambda param: _not_merged("--parts", "the part tables and recombinant sets are"),
+    banner=lambda param: ["Each of the two feature parts is also matched on its own; recombinant reads are counted per pair of parts", PARTS_HEADER[1:]],
+    header=lambda param: [PARTS_HEADER],
+    read=lambda ctx, param: dict(zip(("parts_counts", "part1", "part2", "classes"), ctx.read_parts()), recombinants=ctx.parts_recombinants()),      # (f2q_read_parts, f2q_parts_recombinants)
+    stats=lambda param, found: [PARTS_STATS_HEAD] + [                                               # the six read classes per file, the distinct recombinant pairs next to their reads
+        [s.name, c["pair_perfect"], c["pair_imperfect"], c["recombinant"], len(rec.recombinants), c["part1_only"], c["part2_only"], c["neither"]] for s, rec in found for c in [rec.classes]])
+
+
+# ---- --as.  A sample's record: the column Counter mode would have given for it
+def _parse_assign(args, p):
+    if args.g is None or args.t is not None:
+        return "--as needs --g: the .csv file with the features the extracted sequences are assigned to."
+    if p['Running Mode'] != "EC":
+        return "--as only has a meaning with --mo EC: Counter mode assigns every read already."
+    p['assign'] = True
+
+
+def _assign_read(ctx, param):
+    """one match per distinct key on the device: the Counter-mode count vector and counters of the same reads (they take the
+    place of the sample's own), and every key's feature (f2q_ec_assign)"""
+    counts, stats = ctx.ec_assign()
+    return dict(counts=_ints(counts), stats=stats, rows=ctx.ec_assigned())
+
+
+def _assign_sample(got, sample, features, param):
+    names = _names(param['assign_features'])
+    _sample_file(param, sample, "_assigned.csv", [["#key", "reads", "feature_name", "mismatches"]] + [[key, n, names[f] if f >= 0 else "", d] for key, n, _first, f, d in got["rows"]])
+    return _column(sample, zip(names, got["counts"]))
+
+
+ASSIGN = Option(
+    'assign', parse=_parse_assign, read=_assign_read, sample=_assign_sample,
+    flags=(("--as", dict(dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")),),
+    library=lambda features, param: param.update(assign_features=features_loader(param["feature"])),
+    kwargs=lambda param: dict(assign_library=list(param['assign_features'])),                       # the library the context matches its keys against, given to it once it is made
+    one_rank=lambda param: _not_merged("--as", "assignments are"),
+    banner=lambda param: [f"Extracted sequences are assigned to the features of {param['feature']} ({param['miss']} mismatches allowed)"],
+    tables=lambda param, found: [_table("_features", [rec for _, rec in found])])                   # the table Counter mode would have written for the same samples
+
+
+# ---- --ecm 1 / --ecr.  A sample's record: its centroids with their cluster reads, the six numbers of EC_COLLAPSE_STATS_HEAD
+CollapseSample = namedtuple("CollapseSample", "table counters")
+
+
+def _parse_ec_collapse(args, p):
+    ecm = None if args.ecm is None else args.ecm.strip()
+    if ecm == "0" and args.ecr is None:
+        args.ecm = None                                         # --ecm 0 is a run without the flag: the recorded command line leaves it out
+        return None
+    if ecm not in (None, "0", "1"):
+        return f"--ecm takes 0 or 1 (mismatches among the extracted sequences): --ecm {args.ecm} is not understood."
+    if ecm != "1":
+        return f"--ecr {args.ecr} only has a meaning with --ecm 1: without it the extracted sequences are not collapsed."
+    if args.ecr is not None and not (re.fullmatch(r"[0-9]{1,4}", args.ecr.strip()) and 2 <= int(args.ecr) <= 255):
+        return f"--ecr takes a whole number from 2 to 255: --ecr {args.ecr} is not one."
+    if p['Running Mode'] != "EC":
+        return "--ecm 1 only has a meaning with --mo EC: Counter mode extracts no sequences to collapse."
+    if args.pe is not None:
+        return "--ecm 1 cannot be combined with --pe: the joined keys of a pair are not collapsed."
+    anchored = args.us is not None or args.ds is not None
+    if anchored and max(len(str(x).split(",")) for x in (args.us, args.ds) if x is not None) > 1:
+        return "--ecm 1 needs one --us/--ds pair: with several pairs every extracted sequence is a ':'-joined key and none could be collapsed."
+    if not anchored and len(str(p['start']).split(",")) > 1:
+        return f"--ecm 1 needs one window: with --st {p['start']} every extracted sequence is a ':'-joined key and none could be collapsed."
+    if not (args.us is not None and args.ds is not None) and p['length'] > 29:
+        return f"--ecm 1 collapses sequences of at most 29 bases: with --l {p['length']} none could be collapsed."
+    p['ec_collapse'] = (1, int(args.ecr) if args.ecr is not None else 5)
+
+
+def _collapse_sample(got, sample, features, param):
+    counters, rows = got["counters"], got["rows"]
+    _sample_file(param, sample, "_clusters.csv", [["#key", "reads", "centroid", "cluster_reads"]] + [[key, n, cent, cluster] for key, n, _first, cent, cluster in rows])
+    centroids = [(key, cluster) for key, _n, _first, cent, cluster in rows if cent == key]
+    return CollapseSample(_column(sample, centroids), [len(rows), counters["eligible_keys"], counters["absorbed_keys"], len(centroids), counters["absorbed_reads"], counters["longest_chain"]])
+
+
+EC_COLLAPSE = Option(
+    'ec_collapse', parse=_parse_ec_collapse, sample=_collapse_sample,
+    flags=(("--ecm", dict(help="With --mo EC: mismatches among the extracted sequences, 0 (default) or 1. 1: per sample, every plain sequence of at most 29 bases is folded into the sequence one substitution away with the most reads, when that one has at least --ecr times its reads (<sample>_clusters.csv, <name>_collapsed.csv). One fixed window of at most 29 bases or one --us/--ds pair, single reads, one process")),
+           ("--ecr", dict(help="With --ecm 1: the reads a sequence needs, as a multiple of another's, to absorb it: 2-255 (default = 5)"))),
+    one_rank=lambda param: "--ecm 1: the merged tables of several ranks live on the host and are not collapsed; run one process",
+    banner=lambda param: ["Extracted sequences of one sample that differ in one base are collapsed into the one with the most reads", ec_collapse_header(param)[1:]],
+    header=lambda param: [ec_collapse_header(param)],
+    read=lambda ctx, param: dict(counters=ctx.ec_collapse(*param['ec_collapse']), rows=ctx.ec_collapsed()),    # the sample's plain keys one base apart folded on the device (f2q_ec_collapse)
+    tables=lambda param, found: [_table("_collapsed", [rec.table for _, rec in found])],            # <name>.csv's layout over the samples' centroids and their cluster reads
+    stats=lambda param, found: [EC_COLLAPSE_STATS_HEAD] + [[s.name] + rec.counters for s, rec in found])
+
+
+UMI_FLAGS = ("--umi", "--umi1", "--umi2", "--umih")
+# in the order of the '#key: value' lines and of the blocks of <name>_stats.csv
+OPTIONS = (PAIRED, UMI, SAMPLE_BARCODES, STRAND, STAGGER, INDEL, PARTS, ASSIGN, EC_COLLAPSE)
+# the order the command line is examined in, which decides what a command line that is wrong twice is told: the order the
+# options came to the program in (--parts before --stagger and --indel)
+PARSE_ORDER = (PAIRED, UMI, SAMPLE_BARCODES, STRAND, PARTS, STAGGER, INDEL, ASSIGN, EC_COLLAPSE)
 
 
 def input_parser(argv=None):
@@ -725,49 +1099,17 @@ def input_parser(argv=None):
     ap.add_argument("--fs", nargs='?', const=False, help="File Split mode (accepted for compatibility; ignored)")
     ap.add_argument("--k", nargs='?', const=False, help="If enabled, keeps all temporary files (default is disabled)")
     ap.add_argument("--gpu", help="HIP device ordinal (default: LOCAL_RANK or 0)")
-    ap.add_argument("--pe", nargs='?', const=True, help="Paired-end: the files of --s are paired by name (_R1/_R2, else _1/_2); --st names the feature parts in mate 1, --st2 those in mate 2")
-    ap.add_argument("--st2", help="With --pe: the start position(s) of the feature part(s) within mate 2")
-    ap.add_argument("--rc2", nargs='?', const=True, help="With --pe: mate 2 is reverse-complemented before its parts are taken")
-    ap.add_argument("--umi", help="S,L: every read carries a UMI of L bases (1-16) at position S; Counter mode also reports the distinct UMIs per feature (<name>_umi.csv)")
-    ap.add_argument("--umi1", help="With --pe, S,L: the UMI (or its first part) is L bases at position S of mate 1")
-    ap.add_argument("--umi2", help="With --pe, S,L: the UMI (or its second part) is L bases at position S of mate 2 as sequenced (whatever --rc2 says); --umi1 and --umi2 together hold 16 bases at most")
-    ap.add_argument("--umih", help="SEP,L: the UMI of every read is in its header, the L bases (1-16) behind the last SEP of the read id, e.g. _,8 after umi_tools extract / fastp --umi, :,8 for an Illumina index-read UMI; with --pe: mate 1's header. Takes the place of --umi / --umi1 / --umi2")
-    ap.add_argument("--mu", help="With --umi (or --umih, --umi1 / --umi2): mismatches in the UMI, 0 or 1 (default 0). 1: UMIs of one feature that differ in one base count as one molecule (<name>_umi_collapsed.csv)")
-    ap.add_argument("--mur", help="With --umi and --mu 1: the rule UMIs are collapsed by, cluster (default) or directional. directional: a UMI absorbs a neighbouring UMI only when it has at least twice its reads minus one (<name>_umi_directional.csv)")
-    ap.add_argument("--sb", help="The full path to a .csv file with rows name,barcode: the reads of every file are demultiplexed by an inline sample barcode (1-16 bases, at most 1024 barcodes of one length) while they are counted (<name>_demux.csv). Counter mode, single reads, one process")
-    ap.add_argument("--sbs", help="With --sb: the start position of the sample barcode within the read (default = 0)")
-    ap.add_argument("--sbm", help="With --sb: mismatches allowed in the sample barcode, 0 or 1 (default = 0)")
-    ap.add_argument("--strand", help="fwd (default), rev or both: the orientation the reads are counted in. rev: every read is reverse-complemented first; both: a read that is assigned no feature as sequenced is tried reverse-complemented (<name>_strand.csv). Counter mode, single reads, one process")
-    ap.add_argument("--stagger", help="N (0-32): the one fixed window (--st s --l L) is tried at the starts s .. s+N; a read counts at the earliest start that reads a feature exactly, else at the earliest one within --m (<name>_stagger.csv). 0 (default): off. Counter mode, single reads, one --st value, one process")
-    ap.add_argument("--indel", nargs='?', const=True, help="Reads that the one fixed window (--st s --l L, L 2-31) assigns to no feature are tried as a one-base deletion and as a one-base insertion of every feature of L bases; they are reported per feature and per position (<name>_indel.csv, <name>_indel_positions.csv) and change no count. Counter mode, single reads, one --st value, one process")
-    ap.add_argument("--parts", nargs='?', const=True, help="Pair libraries (features A:B over exactly two windows: --st a,b, or --pe --st a --st2 b): each part is also matched on its own with --m mismatches per part; reads whose two parts the library does not pair are counted as recombinants (<name>_parts.csv, <name>_recombinants.csv). Counter mode, one process")
-    ap.add_argument("--as", dest="assign", nargs='?', const=True, help="With --mo EC and --g: every extracted sequence is also assigned to its feature (--m mismatches), giving the Counter mode table of the same run")
-    ap.add_argument("--ecm", help="With --mo EC: mismatches among the extracted sequences, 0 (default) or 1. 1: per sample, every plain sequence of at most 29 bases is folded into the sequence one substitution away with the most reads, when that one has at least --ecr times its reads (<sample>_clusters.csv, <name>_collapsed.csv). One fixed window of at most 29 bases or one --us/--ds pair, single reads, one process")
-    ap.add_argument("--ecr", help="With --ecm 1: the reads a sequence needs, as a multiple of another's, to absorb it: 2-255 (default = 5)")
+    for opt in OPTIONS:
+        for flag, keywords in opt.flags:
+            ap.add_argument(flag, **keywords)
     args = ap.parse_args(argv)
-    if args.ecm is not None and args.ecm.strip() == "0" and args.ecr is None:
-        args.ecm = None                                         # --ecm 0 is a run without the flag
     if args.v is not None:
         print(f"\nVersion: {version}\n")
         sys.exit()
     if args.c is None:
         return None
-    if args.pe is not None and args.t is not None:
-        colourful_errors("FATAL", "--pe cannot be combined with -t: the test mode runs on one packaged single-end sample.")
-        sys.exit(2)
-    if args.assign is not None and (args.g is None or args.t is not None):
-        colourful_errors("FATAL", "--as needs --g: the .csv file with the features the extracted sequences are assigned to.")
-        sys.exit(2)
     p = {"cmd": True, "big_file_split": args.fs is not None}
-    p['used_cmd'] = " ".join(f"--{k}" if isinstance(v, bool) and v else f"--{k} {v}"
-                             for k, v in ((("as" if k == "assign" else k), v) for k, v in vars(args).items()) if v is not None)
     p['Running Mode'] = "EC" if (args.mo is not None and "EC" in args.mo.upper()) else "C"
-    if args.t is None:
-        p["test_mode"] = False
-        paths = [[args.s, 'seq_files'], [args.g, 'feature'], [args.o, 'out']]
-    else:
-        p["test_mode"] = True
-        paths = [[ensure_example_fastq(), 'seq_files'], [_package_data('D39V_guides.csv'), 'feature'], [os.getcwd(), 'out']]
     p['out_file_name'] = args.fn if args.fn is not None else "compiled"
     p['length'] = int(args.l) if args.l is not None else 20
     p['Progress bar'] = args.pb is None
@@ -783,187 +1125,19 @@ def input_parser(argv=None):
     p['cpu'] = int(args.cp) if args.cp is not None else False
     if args.gpu is not None:
         p['device'] = int(args.gpu)
-    if args.pe is not None:
-        if args.us is not None or args.ds is not None:
-            colourful_errors("FATAL", "--pe takes fixed positions only (--st / --st2): it cannot be combined with --us / --ds.")
-            sys.exit(2)
-        if args.st2 is None:
-            colourful_errors("FATAL", "--pe needs --st2: the start position(s) of the feature part(s) within mate 2.")
-            sys.exit(2)
-        p['paired'], p['start2'], p['rc2'] = True, args.st2, args.rc2 is not None
-    elif args.st2 is not None or args.rc2 is not None:
-        colourful_errors("FATAL", f"{'--st2' if args.st2 is not None else '--rc2'} only has a meaning with --pe.")
-        sys.exit(2)
-    if args.umi is not None:
-        if p['Running Mode'] != "C":
-            colourful_errors("FATAL", "--umi only has a meaning in Counter mode: it cannot be combined with --mo EC.")
-            sys.exit(2)
-        if args.pe is not None:
-            colourful_errors("FATAL", "--umi takes single reads: it cannot be combined with --pe. The UMI of a pair is named per mate with --umi1 S,L and / or --umi2 S,L.")
-            sys.exit(2)
-        p['umi'] = parse_umi(args.umi)
-        if p['umi'] is None:
-            colourful_errors("FATAL", f"--umi {args.umi}: expected S,L with a start S >= 0 and a length 1 <= L <= 16.")
-            sys.exit(2)
-    if args.umi1 is not None or args.umi2 is not None:
-        given = " / ".join(f for f, v in (("--umi1", args.umi1), ("--umi2", args.umi2)) if v is not None)
-        if args.pe is None:
-            colourful_errors("FATAL", f"{given} only has a meaning with --pe: the UMI part of one mate of a pair (single reads: --umi).")
-            sys.exit(2)
-        if args.umi is not None:
-            colourful_errors("FATAL", f"{given} cannot be combined with --umi: --umi names the UMI of single reads.")
-            sys.exit(2)
-        if p['Running Mode'] != "C":
-            colourful_errors("FATAL", f"{given} only has a meaning in Counter mode: it cannot be combined with --mo EC.")
-            sys.exit(2)
-        parts = []
-        for flag, value in (("--umi1", args.umi1), ("--umi2", args.umi2)):
-            parts.append(None if value is None else parse_umi(value))
-            if value is not None and parts[-1] is None:
-                colourful_errors("FATAL", f"{flag} {value}: expected S,L with a start S >= 0 and a length 1 <= L <= 16.")
-                sys.exit(2)
-        if sum(part[1] for part in parts if part) > 16:
-            colourful_errors("FATAL", f"--umi1 {args.umi1} --umi2 {args.umi2}: the two parts together hold 16 bases at most.")
-            sys.exit(2)
-        p['umi_paired'] = tuple(parts)
-    if args.umih is not None:
-        others = [f for f, v in (("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2)) if v is not None]
-        if others:
-            colourful_errors("FATAL", f"--umih cannot be combined with {' / '.join(others)}: a run has one source of UMIs, the read header or the read.")
-            sys.exit(2)
-        if p['Running Mode'] != "C":
-            colourful_errors("FATAL", "--umih only has a meaning in Counter mode: it cannot be combined with --mo EC.")
-            sys.exit(2)
-        parsed = parse_umih(args.umih)
-        if isinstance(parsed, str):
-            colourful_errors("FATAL", f"--umih {args.umih}: {parsed}.")
-            sys.exit(2)
-        p['umi_header'] = parsed
-    any_umi = args.umi is not None or args.umi1 is not None or args.umi2 is not None or args.umih is not None
-    if args.mu is not None:
-        if not any_umi:
-            colourful_errors("FATAL", "--mu only has a meaning with --umi: the mismatches allowed between two UMIs of one feature.")
-            sys.exit(2)
-        if args.mu not in ("0", "1"):
-            colourful_errors("FATAL", f"--mu {args.mu}: expected 0 or 1 (UMIs are collapsed at Hamming distance 1 at most).")
-            sys.exit(2)
-        if args.mu == "1":
-            p['umi_mismatch'] = 1
-    if args.mur is not None:
-        if args.mur not in ("cluster", "directional"):
-            colourful_errors("FATAL", f"--mur {args.mur}: expected cluster or directional.")
-            sys.exit(2)
-        if not any_umi or args.mu != "1":
-            colourful_errors("FATAL", "--mur only has a meaning with --umi and --mu 1: the rule UMIs one base apart are collapsed by.")
-            sys.exit(2)
-        if args.mur == "directional":
-            p['umi_rule'] = 'directional'
-    if args.sb is None and (args.sbs is not None or args.sbm is not None):
-        colourful_errors("FATAL", f"{'--sbs' if args.sbs is not None else '--sbm'} only has a meaning with --sb: the .csv file with the sample barcodes.")
-        sys.exit(2)
-    if args.sb is not None:
-        if p['Running Mode'] != "C":
-            colourful_errors("FATAL", "--sb only has a meaning in Counter mode: it cannot be combined with --mo EC.")
-            sys.exit(2)
-        others = [f for f, v in (("--pe", args.pe), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2), ("--umih", args.umih)) if v is not None]
-        if others:
-            colourful_errors("FATAL", f"--sb cannot be combined with {' / '.join(others)}: sample barcodes are taken from single reads without UMIs.")
-            sys.exit(2)
-        if args.sbs is not None and not (args.sbs.isascii() and args.sbs.isdigit() and int(args.sbs) <= 0x3FFFFFFF):
-            colourful_errors("FATAL", f"--sbs {args.sbs}: expected the start position of the sample barcode within the read, a number >= 0.")
-            sys.exit(2)
-        if args.sbm is not None and args.sbm not in ("0", "1"):
-            colourful_errors("FATAL", f"--sbm {args.sbm}: expected 0 or 1 (sample barcodes are matched at Hamming distance 1 at most).")
-            sys.exit(2)
-        loaded = sample_barcodes_loader(args.sb)
-        if isinstance(loaded, str):
-            colourful_errors("FATAL", f"--sb {args.sb}: {loaded}.")
-            sys.exit(2)
-        p['sample_barcodes'] = dict(path=args.sb, names=loaded[0], barcodes=loaded[1], start=int(args.sbs or 0), miss=int(args.sbm or 0))
-    if args.strand is not None:
-        if args.strand not in ("fwd", "rev", "both"):
-            colourful_errors("FATAL", f"--strand {args.strand}: expected fwd, rev or both.")
-            sys.exit(2)
-        if args.strand != "fwd":                                 # (fwd is a run without the flag)
-            if p['Running Mode'] != "C":
-                colourful_errors("FATAL", f"--strand {args.strand} only has a meaning in Counter mode: it cannot be combined with --mo EC.")
-                sys.exit(2)
-            others = [f for f, v in (("--pe", args.pe), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2), ("--umih", args.umih), ("--sb", args.sb)) if v is not None]
-            if others:
-                colourful_errors("FATAL", f"--strand {args.strand} cannot be combined with {' / '.join(others)}: the reverse strand is read from single reads without UMIs or sample barcodes.")
-                sys.exit(2)
-            p['strand'] = args.strand
-    if args.parts is not None:
-        if p['Running Mode'] != "C":
-            colourful_errors("FATAL", "--parts only has a meaning in Counter mode: it cannot be combined with --mo EC.")
-            sys.exit(2)
-        others = [f for f, v in (("--us", args.us), ("--ds", args.ds), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2), ("--umih", args.umih), ("--sb", args.sb)) if v is not None]
-        if args.strand in ("rev", "both"):
-            others.append(f"--strand {args.strand}")
-        if others:
-            colourful_errors("FATAL", f"--parts cannot be combined with {' / '.join(others)}: the parts are matched at fixed positions, without UMIs, sample barcodes or a strand mode.")
-            sys.exit(2)
-        windows = [len(str(p['start']).split(","))] + ([len(str(args.st2).split(","))] if args.pe is not None else [])
-        if windows not in ([2], [1, 1]):
-            colourful_errors("FATAL", f"--parts needs exactly two windows: --st a,b for single reads, or one window per mate with --pe (--st a --st2 b); "
-                                      f"--st {p['start']}" + (f" --st2 {args.st2}" if args.pe is not None else "") + f" names {' + '.join(str(n) for n in windows)}.")
-            sys.exit(2)
-        p['parts'] = True
-    if args.stagger is not None:
-        if not re.fullmatch(r"[0-9]{1,3}", str(args.stagger)) or int(args.stagger) > 32:
-            colourful_errors("FATAL", f"--stagger {args.stagger}: expected a number of extra starts, 0 to 32.")
-            sys.exit(2)
-        if int(args.stagger):                                    # (0 is a run without the flag)
-            if p['Running Mode'] != "C":
-                colourful_errors("FATAL", f"--stagger {args.stagger} only has a meaning in Counter mode: it cannot be combined with --mo EC.")
-                sys.exit(2)
-            others = [f for f, v in (("--pe", args.pe), ("--us", args.us), ("--ds", args.ds), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2),
-                                     ("--umih", args.umih), ("--sb", args.sb), ("--parts", args.parts)) if v is not None]
-            if args.strand in ("rev", "both"):
-                others.append(f"--strand {args.strand}")
-            if others:
-                colourful_errors("FATAL", f"--stagger {args.stagger} cannot be combined with {' / '.join(others)}: one fixed window of single reads is tried at "
-                                          "several starts, without anchors, UMIs, sample barcodes, a strand mode or parts.")
-                sys.exit(2)
-            if not re.fullmatch(r"[0-9]+", str(p['start']).strip()):
-                colourful_errors("FATAL", f"--stagger {args.stagger} needs exactly one window start at or after the first base: --st {p['start']} does not name one.")
-                sys.exit(2)
-            p['stagger'] = int(args.stagger)
-    if args.indel is not None:
-        if args.indel is not True:
-            colourful_errors("FATAL", f"--indel takes no value: --indel {args.indel} is not understood.")
-            sys.exit(2)
-        if p['Running Mode'] != "C":
-            colourful_errors("FATAL", "--indel only has a meaning in Counter mode: it cannot be combined with --mo EC.")
-            sys.exit(2)
-        others = [f for f, v in (("--pe", args.pe), ("--us", args.us), ("--ds", args.ds), ("--umi", args.umi), ("--umi1", args.umi1), ("--umi2", args.umi2),
-                                 ("--umih", args.umih), ("--sb", args.sb), ("--parts", args.parts)) if v is not None]
-        if args.strand in ("rev", "both"):
-            others.append(f"--strand {args.strand}")
-        if p.get('stagger'):
-            others.append(f"--stagger {p['stagger']}")
-        if others:
-            colourful_errors("FATAL", f"--indel cannot be combined with {' / '.join(others)}: the unassigned reads of one fixed window of single reads are "
-                                      "examined, without anchors, UMIs, sample barcodes, a strand mode, parts or a stagger.")
-            sys.exit(2)
-        if not re.fullmatch(r"[0-9]+", str(p['start']).strip()):
-            colourful_errors("FATAL", f"--indel needs exactly one window start at or after the first base: --st {p['start']} does not name one.")
-            sys.exit(2)
-        if not 2 <= p['length'] <= 31:
-            colourful_errors("FATAL", f"--indel needs a window of 2 to 31 bases: --l {p['length']} is outside that range.")
-            sys.exit(2)
-        p['indel'] = True
-    if args.assign is not None:
-        if p['Running Mode'] != "EC":
-            colourful_errors("FATAL", "--as only has a meaning with --mo EC: Counter mode assigns every read already.")
-            sys.exit(2)
-        p['assign'] = True
-    if args.ecm is not None or args.ecr is not None:
-        refusal = ec_collapse_refusal(args, p)
+    for opt in PARSE_ORDER:                                    # before any output directory exists
+        given = any(getattr(args, keywords.get("dest", flag.lstrip("-"))) is not None for flag, keywords in opt.flags)
+        refusal = opt.parse(args, p) if given else None
         if refusal:
             colourful_errors("FATAL", refusal)
             sys.exit(2)
-        p['ec_collapse'] = (1, int(args.ecr) if args.ecr is not None else 5)
+    p['used_cmd'] = " ".join(f"--{k}" if isinstance(v, bool) and v else f"--{k} {v}"
+                             for k, v in ((("as" if k == "assign" else k), v) for k, v in vars(args).items()) if v is not None)
+    p["test_mode"] = args.t is not None
+    if args.t is None:
+        paths = [[args.s, 'seq_files'], [args.g, 'feature'], [args.o, 'out']]
+    else:                                                       # (after the refusals: the packaged sample is made on the GPU)
+        paths = [[ensure_example_fastq(), 'seq_files'], [_package_data('D39V_guides.csv'), 'feature'], [os.getcwd(), 'out']]
     for value, key in paths:                                   # :1178-1191
         if value is None:
             p[key] = os.getcwd()
@@ -980,60 +1154,17 @@ def input_parser(argv=None):
     return p
 
 
-def ec_collapse_refusal(args, p):
-    """why --ecm / --ecr cannot be taken as given, else None (input_parser: before any output directory exists)"""
-    ecm = None if args.ecm is None else args.ecm.strip()
-    if ecm not in (None, "0", "1"):
-        return f"--ecm takes 0 or 1 (mismatches among the extracted sequences): --ecm {args.ecm} is not understood."
-    if ecm != "1":                                              # (--ecm 0 alone never gets here)
-        return f"--ecr {args.ecr} only has a meaning with --ecm 1: without it the extracted sequences are not collapsed."
-    if args.ecr is not None and not (re.fullmatch(r"[0-9]{1,4}", args.ecr.strip()) and 2 <= int(args.ecr) <= 255):
-        return f"--ecr takes a whole number from 2 to 255: --ecr {args.ecr} is not one."
-    if p['Running Mode'] != "EC":
-        return "--ecm 1 only has a meaning with --mo EC: Counter mode extracts no sequences to collapse."
-    if args.pe is not None:
-        return "--ecm 1 cannot be combined with --pe: the joined keys of a pair are not collapsed."
-    anchored = args.us is not None or args.ds is not None
-    if anchored and max(len(str(x).split(",")) for x in (args.us, args.ds) if x is not None) > 1:
-        return "--ecm 1 needs one --us/--ds pair: with several pairs every extracted sequence is a ':'-joined key and none could be collapsed."
-    if not anchored and len(str(p['start']).split(",")) > 1:
-        return f"--ecm 1 needs one window: with --st {p['start']} every extracted sequence is a ':'-joined key and none could be collapsed."
-    if not (args.us is not None and args.ds is not None) and p['length'] > 29:
-        return f"--ecm 1 collapses sequences of at most 29 bases: with --l {p['length']} none could be collapsed."
-    return None
-
-
 def file_sizer_split(param):
     """sample discovery (:1657-1689): *.gz and *.fastq of the --s directory, smallest first"""
     if param["test_mode"]:
         param["sequencing_files"] = {"len_files": 1, "preprocess_files": [param["seq_files"]], "files": [param["seq_files"]]}
         return param
     files = [p[0] for p in path_parser(param["seq_files"], ["*.gz", "*.fastq"])]
-    if param.get('umi_paired') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--umi1 / --umi2: the UMI sets are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('umi_header') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--umih: the UMI sets are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('sample_barcodes') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--sb: the demultiplexed counts are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('strand') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--strand: the reverse-strand counts are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('stagger') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--stagger: the offset histograms are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('indel') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--indel: the indel counts are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('parts') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--parts: the part tables and recombinant sets are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('paired'):                                      # one sample per pair, named after its R1 file
-        if sharding.world().size > 1:
-            colourful_errors("FATAL", "--pe: paired files are not shared out over several ranks; run one process.")
+    for opt in reversed(_options_of(param)):                     # (the last row that refuses speaks: --umih or --parts, not the --pe it came with)
+        if sharding.world().size > 1 and opt.one_rank(param):
+            colourful_errors("FATAL", opt.one_rank(param) + ".")
             sys.exit(2)
+    if param.get('paired'):                                      # one sample per pair, named after its R1 file
         try:
             pairs = pair_files(files)
         except ValueError as exc:
@@ -1041,15 +1172,6 @@ def file_sizer_split(param):
             sys.exit(2)
         param['mates'] = dict(pairs)
         files = [r1 for r1, _ in pairs]
-    if param.get('assign') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--as: assignments are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('umi') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--umi: the UMI sets are not merged across several ranks; run one process.")
-        sys.exit(2)
-    if param.get('ec_collapse') and sharding.world().size > 1:
-        colourful_errors("FATAL", "--ecm 1: the merged tables of several ranks live on the host and are not collapsed; run one process.")
-        sys.exit(2)
     param["sequencing_files"] = {"len_files": len(files), "preprocess_files": files[:1], "files": files}
     return param
 
@@ -1110,15 +1232,6 @@ def _samples_from_directory(directory):
     return found
 
 
-def ec_collapse_header(param):
-    return "#Extracted sequences collapsed, mismatches, ratio: %d,%d" % param['ec_collapse']
-
-
-EC_COLLAPSE_STATS_HEAD = ["#Sample name (collapsed sequences)", "Number of distinct sequences", "Number of sequences that can be collapsed",
-                          "Number of sequences absorbed by another", "Number of centroids", "Number of reads of the absorbed sequences",
-                          "Longest chain of absorbed sequences"]
-
-
 def run_headers(param):
     """the '#key: value' lines that open <name>_stats.csv (:1323-1337)"""
     lines = [f"#2FAST2Q version: {param['version']}"]
@@ -1135,32 +1248,8 @@ def run_headers(param):
               f"#Mismatches in the downstream search sequence: {param['miss_search_down']}",
               f"#Minimal Phred-score in the upstream search sequence: {param['qual_up']}",
               f"#Minimal Phred-score in the downstream search sequence: {param['qual_down']}"]
-    if param.get('paired'):
-        lines += [f"#Paired-end, feature start position in mate 2: {param['start2']}",
-                  f"#Mate 2 reverse-complemented: {'yes' if param['rc2'] else 'no'}"]
-    if param.get('umi'):
-        lines.append(f"#UMI start position in the read, length: {param['umi'][0]},{param['umi'][1]}")
-    for mate, part in enumerate(param.get('umi_paired') or (), 1):
-        if part:
-            lines.append(f"#UMI in mate {mate}, start, length: {part[0]},{part[1]}")
-    if param.get('umi_header'):
-        lines.append(f"#UMI in read header, separator, length: {param['umi_header'][0]},{param['umi_header'][1]}")
-    if param.get('umi_mismatch'):
-        lines.append(f"#UMI mismatches collapsed: {param['umi_mismatch']}")
-    if param.get('umi_rule') == 'directional':
-        lines.append("#UMI collapse rule: directional")
-    if param.get('sample_barcodes'):
-        lines.append(sample_barcodes_header(param))
-    if param.get('strand'):
-        lines.append(strand_header(param))
-    if param.get('stagger'):
-        lines.append(stagger_header(param))
-    if param.get('indel'):
-        lines.append(INDEL_HEADER)
-    if param.get('parts'):
-        lines.append(PARTS_HEADER)
-    if param.get('ec_collapse'):
-        lines.append(ec_collapse_header(param))
+    for opt in _options_of(param):
+        lines += opt.header(param)
     return lines
 
 
@@ -1193,54 +1282,9 @@ def compiling(param):
     samples = param.get("samples") or _samples_from_directory(param["directory"])
     ordered, head, table = compile_table(samples)
     run_stats(run_headers(param), param, table, head, ordered)
-    csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}.csv"),
-               [head] + [[feature] + counts for feature, counts in table.items()])
-    if param.get("assign_samples"):                  # --as: the table Counter mode would have written for the same samples
-        _, ahead, atable = compile_table(param["assign_samples"])
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_features.csv"),
-                   [ahead] + [[feature] + counts for feature, counts in atable.items()])
-    if param.get("collapse_samples"):                # --ecm 1: <name>.csv's layout over the samples' centroids and their cluster reads
-        _, chead, ctable = compile_table({name: rec[0] for name, rec in param["collapse_samples"].items()})
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_collapsed.csv"),
-                   [chead] + [[feature] + counts for feature, counts in ctable.items()])
-    for kind, suffix, _, _, _ in UMI_TABLES:         # --umi / --mu 1 / --mur directional: <name>.csv's layout and row order per kind
-        per_sample = {name: rec[kind] for name, rec in param.get("umi_samples", {}).items() if kind in rec}
-        if per_sample:
-            _, uhead, utable = compile_table(per_sample)
-            csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}{suffix}.csv"),
-                       [uhead] + [[feature] + counts for feature, counts in utable.items()])
-    if param.get("demux_samples"):                   # --sb: per file, in <name>.csv's column order, a column per barcode, then the unassigned reads
-        dhead, dtable = _table_of([column for s in ordered for column in param["demux_samples"].get(s.name, ((), ()))[0]])
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_demux.csv"),
-                   [dhead] + [[feature] + counts for feature, counts in dtable.items()])
-    if param.get("strand_samples"):                  # --strand rev / both: per file, in <name>.csv's column order, the forward and the reverse column
-        shead, stable = _table_of([column for s in ordered for column in param["strand_samples"].get(s.name, ((), ()))[0]])
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_strand.csv"),
-                   [shead] + [[feature] + counts for feature, counts in stable.items()])
-    if param.get("stagger_samples"):                 # --stagger N: a row per offset; per file, in <name>.csv's column order, its perfect and its imperfect reads
-        stag = param["stagger_samples"]
-        names = [s.name for s in ordered if s.name in stag]
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stagger.csv"),
-                   [["#Offset", "Start"] + [f"{name}:{kind}" for name in names for kind in ("perfect", "imperfect")]] +
-                   [[d, int(param['start']) + d] + [stag[name][k][d] for name in names for k in (0, 1)] for d in range(param['stagger'] + 1)])
-    if param.get("indel_samples"):                   # --indel: per file, in <name>.csv's column order, its deletion and its insertion column; a row per position
-        ind = param["indel_samples"]
-        ihead, itable = _table_of([column for s in ordered for column in ind.get(s.name, ((),))[0]])
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_indel.csv"),
-                   [ihead] + [[feature] + counts for feature, counts in itable.items()])
-        names = [s.name for s in ordered if s.name in ind]
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_indel_positions.csv"),
-                   [["#Position"] + [f"{name}:{kind}" for name in names for kind in ("del", "ins")]] +
-                   [[p] + [ind[name][k][p] for name in names for k in (1, 2)] for p in range(param['length'])])
-    if param.get("parts_samples"):                   # --parts: <name>.csv's layout and row order holding parts_counts; the recombinant pairs of any sample
-        parts = param["parts_samples"]
-        _, phead, ptable = compile_table({name: rec[0] for name, rec in parts.items()})
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_parts.csv"),
-                   [phead] + [[feature] + counts for feature, counts in ptable.items()])
-        columns = [parts[s.name][1] for s in ordered if s.name in parts]
-        pairs = sorted({pair for column in columns for pair in column}, key=lambda pair: (-sum(column.get(pair, 0) for column in columns), pair))
-        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_recombinants.csv"),
-                   [["#Part1", "Part2"] + [s.name for s in ordered if s.name in parts]] + [[a, b] + [column.get((a, b), 0) for column in columns] for a, b in pairs])
+    tables = [_table("", ordered)] + [t for opt in OPTIONS if opt.found(ordered) for t in opt.tables(param, opt.found(ordered))]
+    for suffix, rows in tables:                      # <name>.csv, then <name><suffix>.csv of every option that has numbers of these samples
+        csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}{suffix}.csv"), rows)
     if param["delete"]:
         for path in path_finder(param["directory"], ['*reads.csv']):
             os.remove(path[0])
@@ -1257,41 +1301,28 @@ STATS_HEAD = ["#Sample name", "Running Time", "Running Time unit", "Total number
               'Number of reads that did not pass quality filtering.']
 
 
+# the heads of the options' blocks of <name>_stats.csv
 UMI_STATS_HEAD = ["#Sample name (UMI)", "Number of aligned reads with a valid UMI", "Number of aligned reads with an invalid UMI"]
-UMI_COLLAPSE_STATS_HEAD = ["#Sample name (UMI collapsed)", "Number of distinct (feature, UMI) pairs", "Number of pairs of them that differ in one base",
-                           "Number of molecules"]
-UMI_DIRECTIONAL_STATS_HEAD = ["#Sample name (UMI directional)", "Number of distinct (feature, UMI) pairs", "Number of pairs of them that differ in one base",
-                              "Number of pairs a neighbour absorbs directly", "Number of molecules", "Number of reads of all pairs"]
-# what a UMI run reports, one record per sample (param["umi_samples"][name][kind], a SampleResult): kind, suffix of the run's
+UMI_COLLAPSE_STATS_HEAD = ["#Sample name (UMI collapsed)", "Number of distinct (feature, UMI) pairs", "Number of pairs of them that differ in one base", "Number of molecules"]
+UMI_DIRECTIONAL_STATS_HEAD = ["#Sample name (UMI directional)", "Number of distinct (feature, UMI) pairs", "Number of pairs of them that differ in one base", "Number of pairs a neighbour absorbs directly", "Number of molecules", "Number of reads of all pairs"]
+# what a UMI run reports, one column per sample (sample.extras['umi'][kind], a SampleResult): kind, suffix of the run's
 # table, column of <sample>_umi_reads.csv, head and counters of its block of <name>_stats.csv.  --umi gives the first,
 # --mu 1 the second, --mur directional the third
 UMI_TABLES = (("umis", "_umi", "UMIs", UMI_STATS_HEAD, ("umi_reads", "umi_failed")),
               ("molecules", "_umi_collapsed", "Molecules", UMI_COLLAPSE_STATS_HEAD, ("umi_pairs", "umi_edges", "umi_molecules")),
               ("directional", "_umi_directional", "Directional", UMI_DIRECTIONAL_STATS_HEAD,
                ("umi_pairs", "umi_edges", "umi_dominated", "umi_molecules", "umi_pair_reads")))
-
-
-DEMUX_VERDICT_STATS_HEAD = ["#Sample name (sample barcodes)", "Number of reads with a barcode read without mismatches", "Number of reads with a barcode read with one mismatch",
-                            "Number of reads one mismatch away from several barcodes", "Number of reads that match no barcode",
+DEMUX_VERDICT_STATS_HEAD = ["#Sample name (sample barcodes)", "Number of reads with a barcode read without mismatches", "Number of reads with a barcode read with one mismatch", "Number of reads one mismatch away from several barcodes", "Number of reads that match no barcode",
                             "Number of reads whose barcode is cut off or did not pass quality filtering"]
 DEMUX_SAMPLE_STATS_HEAD = ["#Sample name:sample barcode"] + STATS_HEAD[3:]
-
-
-STRAND_STATS_HEAD = ["#Sample name (strands)", "Number of reads assigned on the forward strand", "Number of reads assigned on the reverse strand without mismatches",
-                     "Number of reads assigned on the reverse strand with mismatches", "Number of reads whose reverse strand was examined"]
-
-
+STRAND_STATS_HEAD = ["#Sample name (strands)", "Number of reads assigned on the forward strand", "Number of reads assigned on the reverse strand without mismatches", "Number of reads assigned on the reverse strand with mismatches", "Number of reads whose reverse strand was examined"]
 STAGGER_STATS_HEAD = ["#Sample name (stagger)", "Number of reads assigned at offset 0", "Number of reads assigned at a later offset", "Offset with the most assigned reads"]
-
-
-INDEL_STATS_HEAD = ["#Sample name (indel)", "Number of reads that were assigned no feature and tried", "Number of reads with a one-base deletion of a feature",
-                    "Number of reads with a one-base insertion into a feature", "Number of reads that fit two or more features with one indel"]
-
-
-PARTS_STATS_HEAD = ["#Sample name (parts)", "Number of reads whose two parts are a library pair, both without mismatches",
-                    "Number of reads whose two parts are a library pair, at least one with mismatches", "Number of recombinant reads (two assigned parts the library does not pair)",
+INDEL_STATS_HEAD = ["#Sample name (indel)", "Number of reads that were assigned no feature and tried", "Number of reads with a one-base deletion of a feature", "Number of reads with a one-base insertion into a feature", "Number of reads that fit two or more features with one indel"]
+PARTS_STATS_HEAD = ["#Sample name (parts)", "Number of reads whose two parts are a library pair, both without mismatches", "Number of reads whose two parts are a library pair, at least one with mismatches", "Number of recombinant reads (two assigned parts the library does not pair)",
                     "Number of distinct recombinant pairs", "Number of reads with part 1 assigned only", "Number of reads with part 2 assigned only",
                     "Number of reads with no part assigned"]
+EC_COLLAPSE_STATS_HEAD = ["#Sample name (collapsed sequences)", "Number of distinct sequences", "Number of sequences that can be collapsed", "Number of sequences absorbed by another", "Number of centroids", "Number of reads of the absorbed sequences",
+                          "Longest chain of absorbed sequences"]
 
 
 def run_stats(headers, param, compiled, head, ordered):
@@ -1301,38 +1332,8 @@ def run_stats(headers, param, compiled, head, ordered):
              s.stats["perfect_counter"], s.stats["imperfect_counter"], s.stats["non_aligned_counter"],
              s.stats["quality_failed"]] for s in ordered]
     global_stat = [[line] for line in headers] + [STATS_HEAD] + rows
-    umi = param.get("umi_samples", {})
-    for kind, _, _, stats_head, columns in UMI_TABLES:       # per kind: its head, then one line of counters per sample
-        if any(kind in rec for rec in umi.values()):
-            global_stat += [stats_head] + [[s.name] + [umi[s.name][kind].stats[c] for c in columns] for s in ordered if kind in umi.get(s.name, {})]
-    demux = param.get("demux_samples", {})
-    if demux:                                                    # --sb: the verdicts per file, then the counters per (file, barcode)
-        global_stat += [DEMUX_VERDICT_STATS_HEAD] + [[s.name] + demux[s.name][1] for s in ordered if s.name in demux]
-        global_stat += [DEMUX_SAMPLE_STATS_HEAD] + [
-            [c.name, c.stats["reads"], c.stats["perfect_counter"] + c.stats["imperfect_counter"], c.stats["perfect_counter"],
-             c.stats["imperfect_counter"], c.stats["non_aligned_counter"], c.stats["quality_failed"]]
-            for s in ordered if s.name in demux for c in demux[s.name][0]]
-    strands = param.get("strand_samples", {})
-    if strands:                                                  # --strand rev / both: the four strand counters per file
-        global_stat += [STRAND_STATS_HEAD] + [[s.name] + strands[s.name][1] for s in ordered if s.name in strands]
-    stag = param.get("stagger_samples", {})
-    if stag:                                                     # --stagger N: where the reads of each file were assigned
-        global_stat.append(STAGGER_STATS_HEAD)
-        for s in ordered:
-            if s.name in stag:
-                both = [a + b for a, b in zip(*stag[s.name])]
-                global_stat.append([s.name, both[0], sum(both[1:]), both.index(max(both))])
-    ind = param.get("indel_samples", {})
-    if ind:                                                      # --indel: the four totals per file
-        global_stat += [INDEL_STATS_HEAD] + [[s.name] + ind[s.name][3] for s in ordered if s.name in ind]
-    parts = param.get("parts_samples", {})
-    if parts:                                                    # --parts: the six read classes per file, the distinct recombinant pairs next to their reads
-        global_stat += [PARTS_STATS_HEAD] + [
-            [s.name, c["pair_perfect"], c["pair_imperfect"], c["recombinant"], len(parts[s.name][1]), c["part1_only"], c["part2_only"], c["neither"]]
-            for s in ordered if s.name in parts for c in [parts[s.name][2]]]
-    coll = param.get("collapse_samples", {})
-    if coll:                                                     # --ecm 1: the collapse of each file
-        global_stat += [EC_COLLAPSE_STATS_HEAD] + [[s.name] + coll[s.name][1] for s in ordered if s.name in coll]
+    for opt in OPTIONS:                                          # its blocks: a head, then a row per sample (or column) it has numbers of
+        global_stat += opt.stats(param, opt.found(ordered)) if opt.found(ordered) else []
     csv_writer(os.path.join(param["directory"], f"{param['out_file_name']}_stats.csv"), global_stat)
     try:
         import matplotlib
@@ -1408,16 +1409,12 @@ def run_stats(headers, param, compiled, head, ordered):
 
 def main(argv=None):
     param = file_sizer_split(initializer(input_parser(argv)))
-    features = {}
-    if param['Running Mode'] == 'C':
-        features = features_loader(param["feature"])
-        if param.get('parts'):                       # refused before the output directory exists
-            wrong = check_parts_library(features)
-            if wrong:
-                colourful_errors("FATAL", f"--parts takes a library of pairs, --g {param['feature']}: {wrong}.")
-                sys.exit(2)
-    elif param.get('assign'):
-        param['assign_features'] = features_loader(param["feature"])
+    features = features_loader(param["feature"]) if param['Running Mode'] == 'C' else {}
+    for opt in _options_of(param):                   # refused before the output directory exists
+        refusal = opt.library(features, param)
+        if refusal:
+            colourful_errors("FATAL", refusal)
+            sys.exit(2)
     aligner_mp_dispenser(features, param)
     sharding.barrier()
     if sharding.world().rank == 0:

@@ -254,13 +254,13 @@ def test_output_contract_vs_reference(case, keep, tmp_path, monkeypatch):
     """aligner() -> compiling() of the harness against the bytes the REFERENCE's aligner/compiling/run_stats wrote for
     the same samples (tests/golden/compiling_cases.json): compiled.csv and compiled_stats.csv byte for byte, sample
     order, numeric vs alphabetical row order, zero back-fill, and -- with --k -- the <sample>_reads.csv files.
-    reads_counter is replaced by the reference's own per-sample result here (no GPU); tests/test_gpu_cli.py runs the
-    same cases through the device."""
+    The counting aligner() calls (_count_sample: reads_counter's three values, then what the options read) is replaced by
+    the reference's own per-sample result here (no GPU); tests/test_gpu_cli.py runs the same cases through the device."""
     exp = case["expected"]
     by_file = {s["file"]: s["rows"] for s in exp["samples"]}
     stats_rows = {r[0]: r for r in csv.reader(exp["compiled_stats.csv"].splitlines()) if len(r) == 9 and not r[0].startswith("#")}
 
-    def fake_reads_counter(i, raw, features, param, reads_stats, preprocess=False):
+    def fake_count_sample(i, raw, features, param, reads_stats, preprocess=False):
         name = fast2q._sample_name(raw)
         r = stats_rows[name]
         for fname, seq, n in by_file[os.path.basename(raw)]:
@@ -269,9 +269,9 @@ def test_output_contract_vs_reference(case, keep, tmp_path, monkeypatch):
             else:
                 features[seq] = fast2q.Features(fname, n)
         local = dict(zip(binding.STAT_NAMES, (int(r[3]), int(r[5]), int(r[6]), int(r[7]), int(r[8]))))
-        return features, reads_stats, local
+        return features, reads_stats, local, {}
 
-    monkeypatch.setattr(fast2q, "reads_counter", fake_reads_counter)
+    monkeypatch.setattr(fast2q, "_count_sample", fake_count_sample)
     monkeypatch.setattr(fast2q.time, "perf_counter", _Clock(_golden_compiling_cases()[1]))
     param = golden_param(case, tmp_path, keep)
     lib = {}
